@@ -1,8 +1,11 @@
 #!/usr/bin/env python
 """Headline benchmark: RLEPSO rollout throughput on bbob d=10 pop=100, 4096 lock-step instances per MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+--dump-outputs DIR writes what the timed path handed its caller after the last timed step as DIR/<name>.npy (see dump_outputs); the last
+timed repeat starts from the inputs of the first (mbx_batch_rebind), so two builds run with the same arguments can be compared output for output.
 
 A *step* is one lock-step generation of the whole instance batch: agent.act (the actor's (mu, sigma) looked up in the per-state table that ONE
 mbx_rlepso_policy_table launch builds per weight set, sampled inside the generation kernel) + RLEPSO_Optimizer.update + problem.eval, i.e. one
@@ -328,6 +331,27 @@ def valu_roofline(live_per_gen, avg_gen_s, resident=False):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(batch, out_dir, suffix=''):
+    """What the timed path handed its caller after its last step: the (state, reward, done) tensors the last generation launch returned
+    (reward: summed over that launch's generations) and the per-instance results a rollout caller reads (Batch.results: cost curve, fes,
+    return, steps, cost_len), as out_dir/<name><suffix>.npy in float64 (done: float32).  instance_index holds the instances the rows
+    belong to: all of them, or a fixed seeded sample when the arrays would exceed 64 MB in all."""
+    arrays = {'state': batch.state, 'reward': batch.reward, 'done': batch.done}
+    arrays.update({f'results_{k}': v for k, v in batch.results().items()})
+    arrays = {k: v.cpu().numpy().astype(np.float32 if k == 'done' else np.float64) for k, v in arrays.items()}
+    idx = np.arange(batch.B)
+    row_bytes = 8 + sum(a[0].nbytes for a in arrays.values())
+    if row_bytes * batch.B > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.RandomState(0).choice(batch.B, (DUMP_LIMIT_BYTES - 4096) // row_bytes, replace=False))    # 4 KB: the .npy headers
+    arrays['instance_index'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{k}{suffix}.npy'), a if k == 'instance_index' else np.ascontiguousarray(a[idx]))
+
+
 def _bracket(fn, steps, stream_sync=True):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -561,9 +585,13 @@ def main():
     ap.add_argument('--dist-backend', default='nccl', help='process-group backend (nccl = RCCL; gloo only for single-GPU plumbing tests)')
     ap.add_argument('--same-device', action='store_true', help='plumbing test: every rank uses cuda:0')
     ap.add_argument('--qnet-child', action='store_true', help='(internal) config 4\'s Q-network launch alone, for the MFMA counter pass of roofline.policy_mfma')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed repeats, write the outputs of the last timed step to DIR/<name>.npy (dump_outputs; <name>_rank<r>.npy when N > 1)')
     args = ap.parse_args()
     if args.qnet_child:
         return qnet_child()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('bench.py needs --steps >= 1 and --warmup >= 0')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -766,8 +794,16 @@ def main():
         repeats = args.repeats
     elif first_elapsed < 0.5:
         repeats = int(min(200, max(30, np.ceil(2.0 / max(first_elapsed, 1e-4)))))
-    for _ in range(repeats - 1):
+    for r in range(1, repeats):
+        if r == repeats - 1:
+            # the last repeat computes what the first one did: episode counters as a new batch has them (mbx_batch_rebind) + the set-up's reset, so what
+            # it leaves behind (--dump-outputs) does not depend on how many repeats ran.  Only this window follows the rebind's device synchronisation:
+            # before every window, that idle gap lowered the clock of the short windows by ~1 %.
+            env.batch.rebind(pidx, seeds)
+            env.reset()
         windows.append(timed_window())
+    if args.dump_outputs:
+        dump_outputs(env.batch, args.dump_outputs, f'_rank{rank}' if world > 1 else '')
     per_repeat = [over_ranks(w[0], w[1]) for w in windows]            # (wall time max over ranks, live env-steps over all ranks) of every repeat
     order = sorted(range(repeats), key=lambda r: per_repeat[r][0])
     med = order[(repeats - 1) // 2]

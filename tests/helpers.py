@@ -31,6 +31,15 @@ def load(name):
     return np.load(os.path.join(GOLDEN, name))
 
 
+def free_port():
+    """A TCP port on 127.0.0.1 that the OS reports unused right now (bind to port 0), for a process-group rendezvous started right after.
+    A port derived from the pid would sit in the ephemeral range, where any outgoing connection on a shared machine can already hold it."""
+    import socket
+    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
+        s.bind(('127.0.0.1', 0))
+        return s.getsockname()[1]
+
+
 # ------------------------------------------------------------------------------------------------ branch divergences, proven
 # The reference and this build compute the same float64 objective with different instruction sequences (numpy's SIMD transcendentals /
 # BLAS vs libm or the kernels' own routines): costs agree to ~1e-15 at first and, because a PSO amplifies perturbations, to 1e-13 .. 1e-10

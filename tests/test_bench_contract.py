@@ -6,6 +6,7 @@ import sys
 
 import numpy as np
 import pytest
+from helpers import free_port
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -88,6 +89,33 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_do_not_depend_on_the_repeats(tmp_path):
+    """--dump-outputs DIR: what the timed path returned after its last step, written as .npy files.  The window measured once or three times
+    leaves the same arrays bit for bit (the last repeat starts from the first one's inputs), and --steps sets how far the instances got."""
+    K, W = 12, 3
+    dirs = []
+    for rep in (1, 3):
+        d = tmp_path / f'repeats{rep}'
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(K), '--warmup', str(W), '--repeats', str(rep),
+                              '--no-cpu-baseline', '--no-other-configs', '--no-pmc', '--no-fdr-fast', '--dump-outputs', str(d)],
+                             capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert out.returncode == 0, out.stderr[-600:]
+        assert json.loads([l for l in out.stdout.splitlines() if l.strip()][0])['repeats'] == rep
+        dirs.append(d)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert {'state.npy', 'reward.npy', 'done.npy', 'results_cost.npy', 'results_fes.npy', 'results_steps.npy', 'instance_index.npy'} <= set(names)
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 4096, (n, a.dtype, a.shape)
+        assert np.array_equal(a, b, equal_nan=True), n
+    steps = np.load(dirs[0] / 'results_steps.npy')
+    assert steps.max() == W + K and steps.min() >= 1                          # W + K generations of one episode; early-stopped instances fewer
+    assert np.array_equal(np.load(dirs[0] / 'instance_index.npy'), np.arange(4096))
+
+
+@pytest.mark.gpu
 def test_bench_one_launch_per_generation_route():
     """--policy fused: one mbx_rlepso_act_step launch per generation (the route the resident kernel is bit-identical to); a launch is a
     generation, so the per-launch and per-generation figures coincide and the traffic is the state block's round trip."""
@@ -107,7 +135,7 @@ def test_bench_under_torchrun_two_ranks_one_device():
     """The driver's multi-GPU launch line (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N`) with N = 2
     ranks sharing the one GPU of the test box (--same-device; gloo, because RCCL rejects two ranks on one device): rank 0 prints ONE line,
     the aggregate counts both ranks' instances, weak scaling."""
-    port = 36500 + os.getpid() % 2000
+    port = free_port()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                           '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '12', '--warmup', '3',

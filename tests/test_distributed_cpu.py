@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+from helpers import free_port
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -39,7 +40,7 @@ def test_gather_equals_unsharded(n_total):
     from metabox_amd.distributed import pack_rows, unpack_rows
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    port = 29500 + (os.getpid() + n_total) % 2000
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, n_total, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -72,7 +73,7 @@ def _grad_worker(rank, world, port, q):
 def test_gradient_averaging_world2():
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    port = 31500 + os.getpid() % 2000
+    port = free_port()
     procs = [ctx.Process(target=_grad_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -130,7 +131,7 @@ def test_batched_training_with_unequal_episode_lengths_world2():
     global now: both ranks run 3 segments x 3 optimizer steps (the finished rank contributes zero gradients) and end with identical weights."""
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    port = 33500 + os.getpid() % 2000
+    port = free_port()
     procs = [ctx.Process(target=_train_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -207,7 +208,7 @@ def test_gradient_of_unequal_shards_equals_the_single_rank_gradient_world2():
     want = _first_ppo_gradient(range(7))
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    port = 38500 + os.getpid() % 2000
+    port = free_port()
     procs = [ctx.Process(target=_weighted_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -273,7 +274,7 @@ def test_cost_weighted_shards_gather_to_the_unsharded_table_world8():
     from metabox_amd.distributed import pack_rows, unpack_rows
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    port = 35500 + os.getpid() % 2000
+    port = free_port()
     procs = [ctx.Process(target=_c5_worker, args=(r, 8, port, q)) for r in range(8)]
     for p in procs:
         p.start()
@@ -404,7 +405,7 @@ def test_save_class_writes_replicated_agents_once_and_per_rank_state_per_rank(tm
     """save_class used to return silently on every rank != 0 whenever a process group was up.  Now only objects that declare themselves
     replicated (the gradient-synchronised train_batch paths set `_mbx_replicated`) are left to rank 0; anything else is written by every rank."""
     ctx = mp.get_context('spawn')
-    port = 37500 + os.getpid() % 2000
+    port = free_port()
     out_dir = str(tmp_path) + '/'
     procs = [ctx.Process(target=_save_worker, args=(r, 2, port, out_dir)) for r in range(2)]
     for p in procs:

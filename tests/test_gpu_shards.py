@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
+from helpers import free_port
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,7 +103,7 @@ def test_two_ranks_on_one_gpu_gather_the_unsharded_table(n_total):
     torch.cuda.synchronize()
     used, outs = None, None
     for backend in ('nccl', 'gloo'):
-        outs = _spawn(n_total, backend, 35500 + (os.getpid() + n_total + (7 if backend == 'gloo' else 0)) % 2000)
+        outs = _spawn(n_total, backend, free_port())
         if all(o[1] == 'ok' for o in outs) and len(outs) == 2:
             used = backend
             break
@@ -165,7 +166,7 @@ def test_rccl_world_size_one_runs_every_collective_of_the_framework():
     through RCCL's all_gather / all_reduce on device tensors."""
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    p = ctx.Process(target=_nccl1_worker, args=(39500 + os.getpid() % 2000, q))
+    p = ctx.Process(target=_nccl1_worker, args=(free_port(), q))
     p.start()
     try:
         out = q.get(timeout=300)
@@ -184,7 +185,7 @@ def test_bench_under_torchrun_one_rank_nccl():
     sum-over-ranks reductions and the per-rank diagnostics run through RCCL on device tensors (over_ranks), and the line says `"backend": "nccl"`."""
     import json
     import subprocess
-    port = 41500 + os.getpid() % 2000
+    port = free_port()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                           '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '12', '--warmup', '3',
