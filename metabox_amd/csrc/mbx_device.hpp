@@ -542,7 +542,9 @@ __device__ __forceinline__ double block_sum(double v, double* red)
 // ceil(n / 2) x (n - 1): row a holds the n - 1 - a pairs of atom a followed by the a pairs of atom n - 1 - a.
 // sqrt and the two divisions by the distance (the reference's `r / pair_dis` and `q / (4 pair_dis)`) come from ONE v_rsq_f64 estimate:
 // two coupled Goldschmidt steps give sqrt(s) and 1 / (2 sqrt(s)), one residual correction each brings both to <= 1 ulp -- 13 instructions
-// instead of a library sqrt and two IEEE divisions (~70).  The energy is pinned at 1e-9 relative against the reference's own outputs.
+// instead of a library sqrt and two IEEE divisions (~70).  The energy is pinned at 1e-9 relative against the reference's own outputs, and every
+// route that evaluates it (both summation forms) against an extended-precision energy within a derived per-candidate allowance, ~1e-11 relative
+// on the real tables and a few ulp per term near the origin (tests/protein_exact.py, tests/test_protein_exact.py).
 // pairs in flight per lane in eval_rows_protein: 4 for the D = 12 instantiation (k_dq_step<100, 12>, two waves per instance), the plain loop elsewhere
 // (the generation kernels that can meet a protein problem run under a 96-register cap)
 #ifndef MBX_PROTEIN_PF
