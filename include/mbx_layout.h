@@ -320,6 +320,57 @@
 #define MBX_SC_CMA_SIGMA   10
 #define MBX_SC_CMA_UPDATES 11
 
+/* ---------------------------------------------------------------- 11. GL-PSO (gl_pso.py) layouts
+ * No agent: mbx_reset is init_population (:76-107: random swarm, one evaluation, then one exemplar update with init = True -- 2 NP FEs),
+ * every mbx_step (actions = NULL) is one __update (:118-177: velocity / position, evaluation, pbest / gbest, logging, exemplar update,
+ * termination -- 2 NP FEs).  NP 100, pm 0.01, nsel 10, w 0.7298, c1 1.49618, sg 7, velocity cap 0.2 (ub - lb).  state [1] = fes / maxFEs.
+ * state block: X[NP*D] V[NP*D] pbest_pos[NP*D] pbest[NP] exemplar[NP*D] exemplar_cost[NP] stag[NP] gbest_pos[D] scalars[16] cost_curve[nlog+1].
+ * stag (exemplar_stag) lives on the reference's optimizer object and is never reset by init_population: mbx_reset leaves it alone, so a
+ * batch carries it from episode to episode (mbx_batch_rebind included); a new batch starts at zero.
+ * tape per reset: pos_u[NP*D] | vel_u[NP*D] | noise[3*NP] | <exemplar block>
+ * tape per step:  rand[NP*D] | noise[3*NP] | <exemplar block>
+ *   exemplar block (:22-66): cross_idx[NP*D] | cross_u[NP*D] | mut_u[NP*D] | mut_test_u[NP*D] | noise[3*NP] | tour_idx[NP*10]
+ *   (randint values stored as doubles; tour_idx is read only when some stag > sg, i.e. when the reference draws it).
+ * Philox, counter (index, site, gen, episode); reset gen = 0, step gen = number of the step:
+ *   MBX_SITE_ELEM_R(e)       reset: u53(w0,w1) = pos_u, u53(w2,w3) = vel_u
+ *   MBX_SITE_ELEM_A(e)       step:  u53(w0,w1) = rand
+ *   MBX_SITE_NOISE1_A/B(i)   reset: evaluation of the swarm        MBX_SITE_NOISE0_A/B(i)  step: evaluation of the swarm
+ *   MBX_SITE_GL_CROSS(e)     mulhi(w0, NP) = cross_idx, u53(w2,w3) = cross_u
+ *   MBX_SITE_GL_MUT(e)       u53(w0,w1) = mut_u, u53(w2,w3) = mut_test_u
+ *   MBX_SITE_GL_NOISE_A/B(i) evaluation of the new exemplars (reset and step)
+ *   MBX_SITE_GL_TOUR(i*10+j) mulhi(w0, NP) = tour_idx[i][j]                                                                            */
+#define MBX_GLPSO_NSEL 10
+#define MBX_GLPSO_TAPE_POS(NP, D)        ((int64_t)0)
+#define MBX_GLPSO_TAPE_VEL(NP, D)        ((int64_t)(NP) * (D))
+#define MBX_GLPSO_TAPE_NOISE_INIT(NP, D) (2 * (int64_t)(NP) * (D))
+#define MBX_GLPSO_TAPE_XB_INIT(NP, D)    (2 * (int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_GLPSO_TAPE_RAND(NP, D)       ((int64_t)0)
+#define MBX_GLPSO_TAPE_NOISE(NP, D)      ((int64_t)(NP) * (D))
+#define MBX_GLPSO_TAPE_XB(NP, D)         ((int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+/* offsets inside the exemplar block */
+#define MBX_GLPSO_XB_CIDX(NP, D)         ((int64_t)0)
+#define MBX_GLPSO_XB_CU(NP, D)           ((int64_t)(NP) * (D))
+#define MBX_GLPSO_XB_MU(NP, D)           (2 * (int64_t)(NP) * (D))
+#define MBX_GLPSO_XB_MTEST(NP, D)        (3 * (int64_t)(NP) * (D))
+#define MBX_GLPSO_XB_NOISE(NP, D)        (4 * (int64_t)(NP) * (D))
+#define MBX_GLPSO_XB_TOUR(NP, D)         (4 * (int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_GLPSO_TAPE_STRIDE(NP, D)     (6 * (int64_t)(NP) * (D) + 6 * (int64_t)(NP) + (int64_t)MBX_GLPSO_NSEL * (NP))
+#define MBX_GLPSO_ST_X(NP, D)            ((int64_t)0)
+#define MBX_GLPSO_ST_V(NP, D)            ((int64_t)(NP) * (D))
+#define MBX_GLPSO_ST_PBPOS(NP, D)        (2 * (int64_t)(NP) * (D))
+#define MBX_GLPSO_ST_PBEST(NP, D)        (3 * (int64_t)(NP) * (D))
+#define MBX_GLPSO_ST_EX(NP, D)           (3 * (int64_t)(NP) * (D) + (NP))
+#define MBX_GLPSO_ST_EXCOST(NP, D)       (4 * (int64_t)(NP) * (D) + (NP))
+#define MBX_GLPSO_ST_STAG(NP, D)         (4 * (int64_t)(NP) * (D) + 2 * (int64_t)(NP))
+#define MBX_GLPSO_ST_GBPOS(NP, D)        (4 * (int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_GLPSO_ST_SCALARS(NP, D)      (4 * (int64_t)(NP) * (D) + 3 * (int64_t)(NP) + (D))
+#define MBX_GLPSO_STATE_DOUBLES(NP, D, NLOG) (MBX_GLPSO_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)
+#define MBX_SITE_GL_CROSS    18u
+#define MBX_SITE_GL_MUT      19u
+#define MBX_SITE_GL_NOISE_A  20u
+#define MBX_SITE_GL_NOISE_B  21u
+#define MBX_SITE_GL_TOUR     22u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

@@ -32,6 +32,7 @@
 #include "mbx_qlpso.hpp"
 #include "mbx_gleet_policy.hpp"
 #include "mbx_classic.hpp"
+#include "mbx_glpso.hpp"
 // k_rlepso_run / k_lde_run are compiled in translation units of their own (mbx_run_rlepso.hip, mbx_run_lde.hip) and only declared here;
 // -DMBX_SINGLE_TU (instrumented builds: the phase counters are a __device__ array, one copy per translation unit) instantiates them in this file instead
 #ifndef MBX_SINGLE_TU
@@ -158,6 +159,12 @@ static AlgoGeom geom_of(const mbx_algo_cfg& c)
         g.sc_off = c.algo == MBX_ALGO_DE ? MBX_DE_ST_SCALARS(c.np, c.dim) : c.algo == MBX_ALGO_PSO ? MBX_PSO_ST_SCALARS(c.np, c.dim) : MBX_CMA_ST_SCALARS(c.np, c.dim);
         g.tape_stride = 0;
         g.lds_doubles = cl_lds_doubles(c.np, c.np, c.dim, 0, c.algo == MBX_ALGO_CMAES);       // the largest carve-up of the family
+        g.state_dim = 1; g.action_dim = 0;
+    } else if (c.algo == MBX_ALGO_GLPSO) {
+        g.state_doubles = MBX_GLPSO_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
+        g.sc_off = MBX_GLPSO_ST_SCALARS(c.np, c.dim);
+        g.tape_stride = MBX_GLPSO_TAPE_STRIDE(c.np, c.dim);
+        g.lds_doubles = gp_lds_doubles(c.np, c.dim);
         g.state_dim = 1; g.action_dim = 0;
     }
     return g;
@@ -449,7 +456,7 @@ extern "C" int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, dou
 static int check_cfg(const mbx_algo_cfg* c)
 {
     if (!c) return fail(MBX_E_ARG, "null cfg");
-    if (c->algo < MBX_ALGO_RLEPSO || c->algo > MBX_ALGO_CMAES)
+    if (c->algo < MBX_ALGO_RLEPSO || c->algo > MBX_ALGO_GLPSO)
         return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
     if (c->np < 4 || c->np > kThreads) return fail(MBX_E_ARG, "np %d outside [4, %d]", c->np, kThreads);
     if (c->dim < 2 || c->dim > 64) return fail(MBX_E_ARG, "dim %d outside [2, 64]", c->dim);
@@ -651,6 +658,9 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
         HIP_TRY(hipFuncSetAttribute((const void*)k_de_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_pso_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_cmaes_generation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    } else if (cfg->algo == MBX_ALGO_GLPSO) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_glpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_glpso_generation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     } else if (cfg->algo == MBX_ALGO_QLPSO) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -759,6 +769,8 @@ extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
     else if (b->cfg.algo == MBX_ALGO_DE || b->cfg.algo == MBX_ALGO_PSO || b->cfg.algo == MBX_ALGO_CMAES)
         hipLaunchKernelGGL(k_classic_reset, dim3(b->B), dim3(kThreads), (size_t)cl_lds_doubles(b->cfg.np, b->cfg.np, b->cfg.dim, 0, 0) * sizeof(double),
                            (hipStream_t)stream, make_params(b), (int)b->cfg.algo, d_state_out);
+    else if (b->cfg.algo == MBX_ALGO_GLPSO)
+        hipLaunchKernelGGL(k_glpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_GLEET)
@@ -784,7 +796,7 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
                         void* stream)
 {
     const bool no_agent = b && (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH || b->cfg.algo == MBX_ALGO_DE || b->cfg.algo == MBX_ALGO_PSO ||
-                                b->cfg.algo == MBX_ALGO_CMAES);
+                                b->cfg.algo == MBX_ALGO_CMAES || b->cfg.algo == MBX_ALGO_GLPSO);
     if (!b || (!d_actions && !no_agent)) return fail(MBX_E_ARG, "mbx_step: bad arguments");
     if (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH)
         hipLaunchKernelGGL(k_rs_population, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), 0, d_state_out,
@@ -800,6 +812,9 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
     else if (b->cfg.algo == MBX_ALGO_CMAES)
         hipLaunchKernelGGL(k_cmaes_generation, dim3(b->B), dim3(kThreads), (size_t)cl_lds_doubles(b->cfg.np, b->cfg.np, b->cfg.dim, 0, 1) * sizeof(double),
                            (hipStream_t)stream, make_params(b), d_state_out, d_reward_out, d_done_out);
+    else if (b->cfg.algo == MBX_ALGO_GLPSO)
+        hipLaunchKernelGGL(k_glpso_generation, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
+                           d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_step<false>, dim3(b->B), dim3(kThreads), (size_t)ql_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double),
                            (hipStream_t)stream, make_params(b), (const int32_t*)d_actions, (const double*)nullptr, 1, d_state_out,

@@ -3,7 +3,7 @@
 
 Runs only in the build container (needs /root/reference); the fixtures it writes are data
 (inputs + expected outputs), never reference source.  Re-run: `python tools/gen_golden.py [section ...]`
-with sections in {instances, kat, noise, policy, rlepso, lde, protein, ddqn, harness, stats}.
+with sections in {instances, kat, noise, policy, rlepso, lde, protein, ddqn, harness, stats, glpso, ...} (SECTIONS below).
 
 What is recorded
   instances : per (suite, dim) the problem names, biases, optima, a sha256 over every constructor-made
@@ -1284,8 +1284,83 @@ def gen_train():
     np.savez_compressed(os.path.join(OUT, 'train_updates.npz'), **data)
 
 
+def run_glpso_episode(problem, config, opt=None):
+    """One reference GL_PSO episode on the global numpy stream (the caller seeds it).  Row 0 of every per-generation array is the state
+    after init_population, row g + 1 the state after update() number g."""
+    from optimizer import GL_PSO
+    import copy
+    opt = opt if opt is not None else GL_PSO(copy.deepcopy(config))
+    problem.reset()
+    rec = dict(gbest=[], fes=[], pbest=[], exemplar_cost=[], stag=[])
 
-SECTIONS = {'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+    def snap():
+        pt = opt._GL_PSO__particles
+        rec['gbest'].append(float(pt['gbest_val']))
+        rec['fes'].append(float(opt._GL_PSO__fes))
+        rec['pbest'].append(np.array(pt['pbest'], dtype=np.float64))
+        rec['exemplar_cost'].append(np.array(opt._GL_PSO__exemplar_cost, dtype=np.float64))
+        rec['stag'].append(np.array(opt._GL_PSO__exemplar_stag).astype(np.int16))
+    opt._GL_PSO__init_population(problem)
+    snap()
+    done = False
+    while not done:
+        done, info = opt._GL_PSO__update(problem)
+        snap()
+    out = {k: np.stack(v) if k in ('pbest', 'exemplar_cost', 'stag') else np.array(v) for k, v in rec.items()}
+    out['cost'] = np.array(opt.cost, dtype=np.float64)
+    return out, opt
+
+
+def gen_glpso():
+    """GL-PSO (src/optimizer/gl_pso.py): seeded reference episodes.  The numpy draws are NOT stored: the tests regenerate them from the
+    seed in the reference's draw order.  `max_fes` is reduced where a whole episode would make the fixture large."""
+    scratch = tempfile.mkdtemp()
+    data, cases = {}, []
+
+    def put(key, rec, max_fes, extra=None):
+        cases.append(key)
+        for k, v in rec.items():
+            data[f'{key}/{k}'] = v
+        data[f'{key}/max_fes'] = np.float64(max_fes)
+        data[f'{key}/next_rand'] = np.float64(np.random.rand())      # stream position after the episode(s)
+        print(key, len(rec['gbest']) - 1, rec['fes'][-1], rec['gbest'][-1], int(rec['stag'][-1].max()))
+
+    def config_for(suite, dim, max_fes):
+        argv = ['--problem', suite] + ([] if suite == 'protein' else ['--dim', str(dim)])
+        config = ref_import.ref_config(argv, scratch)
+        config.maxFEs = max_fes
+        config.log_interval = max_fes // config.n_logpoint
+        return config
+    jobs = [('bbob', 10, 1, 31, 30000), ('bbob', 10, 5, 32, 8000), ('bbob', 10, 15, 33, 8000), ('bbob', 10, 20, 34, 8000),
+            ('bbob', 10, 24, 35, 8000), ('bbob', 30, 10, 36, 4000),
+            ('bbob-noisy', 10, 101, 37, 6000), ('bbob-noisy', 10, 102, 38, 6000), ('bbob-noisy', 10, 103, 39, 6000)]
+    for suite, dim, fid, seed, max_fes in jobs:
+        tr, te, _ = all_problems(suite, dim)
+        byfid = {fid_of(p): p for p in tr + te}
+        config = config_for(suite, dim, max_fes)
+        np.random.seed(seed)
+        rec, _ = run_glpso_episode(byfid[fid], config)
+        put(f'{suite}/{dim}/{fid}/{seed}', rec, max_fes)
+    byid, _, _ = protein_problems()
+    config = config_for('protein', 12, 1000)
+    np.random.seed(40)
+    rec, _ = run_glpso_episode(byid['1ATN_7'], config)
+    put('protein/12/1ATN_7/40', rec, 1000)
+    # a second episode on the same optimizer object (another problem, the stream continues): exemplar_stag carries over (:19)
+    tr, te, _ = all_problems('bbob', 10)
+    byfid = {fid_of(p): p for p in tr + te}
+    config = config_for('bbob', 10, 6000)
+    np.random.seed(41)
+    first, opt = run_glpso_episode(byfid[3], config)
+    second, _ = run_glpso_episode(byfid[7], config, opt)
+    for k, v in first.items():
+        data[f'second/10/3-7/41/first/{k}'] = v
+    put('second/10/3-7/41', second, 6000)
+    data['cases'] = np.array(cases)
+    np.savez_compressed(os.path.join(OUT, 'glpso_traces.npz'), **data)
+
+
+SECTIONS = {'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

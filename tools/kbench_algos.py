@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -152,3 +152,22 @@ if 'qlpso' in which:
     print(json.dumps({'path': 'QLPSO bbob d=10 NP=30, 4096 instances, tabular policy in the kernel, 256 steps per launch', 'us_per_step': dt / 2048 * 1e6,
                       'env_steps_per_s': B * 2048 / dt}))
     env.close()
+if 'glpso' in which:
+    # GL-PSO (one mbx_step = one generation, two NP = 100 evaluations) next to Random_search's one-population kernel in the same process:
+    # 4096 instances, bbob round-robin, fixed horizon so that every instance stays live.  Under rocprofv3 --kernel-trace --stats the
+    # per-launch times of k_glpso_generation and k_rs_population come from the trace; the wall times here include the launch gaps.
+    from metabox_amd._abi import ALGO_GLPSO, ALGO_RANDOM_SEARCH
+    from metabox_amd.suite import Batch, Suite
+    for dim in (10, 30):
+        cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+        tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+        s = Suite(ps); B = 4096
+        for algo, name in ((ALGO_GLPSO, 'k_glpso_generation'), (ALGO_RANDOM_SEARCH, 'k_rs_population')):
+            b = Batch(s, algo, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, 100, 10 ** 8, 10 ** 6, 50, early_stop=False)
+            b.reset()
+            def run(n):
+                for _ in range(n): b.step(None)
+            run(3); dt = timed(run, 40)
+            print(json.dumps({'path': f'{name} bbob d={dim} NP=100, {B} instances, one launch per generation', 'us_per_step': dt / 40 * 1e6,
+                              'launch_info': b.launch_info()}))
+            b.close()
