@@ -60,11 +60,14 @@ struct DevProblem {
 typedef const DevProblem __attribute__((address_space(4))) ConstProblem;
 
 // Division of small non-negative integers by a loop-invariant divisor without the ~35-instruction software divide:
-// e / D == umulhi(e, floor((2^32-1)/D) + 1) for e < 2^20, D <= 256 (checked exhaustively on the host).
+// e / D == umulhi(e, floor((2^32-1)/D) + 1) for e < 2^20, 2 <= D <= 256 (checked exhaustively on the host).  At D = 1 the multiplier wraps
+// to 0, so the dividend is added back through a mask that is 0 for every other D (constant-folded wherever D is known at compile time).
+// D = 1 is reached as the half dimension of the 2-wide tiles at D = 2: without the mask every tile read row pair 0 and the columns past the
+// map (tests/test_bbob_exact.py evaluates D = 2 against the extended-precision objective).
 struct FastDiv {
-    uint32_t m; int D;
-    __device__ __forceinline__ explicit FastDiv(int D_) : m(0xFFFFFFFFu / (uint32_t)D_ + 1u), D(D_) {}
-    __device__ __forceinline__ int div(int e) const { return (int)__umulhi((uint32_t)e, m); }
+    uint32_t m, one; int D;
+    __device__ __forceinline__ explicit FastDiv(int D_) : m(0xFFFFFFFFu / (uint32_t)D_ + 1u), one(D_ == 1 ? 0xFFFFFFFFu : 0u), D(D_) {}
+    __device__ __forceinline__ int div(int e) const { return (int)(__umulhi((uint32_t)e, m) + ((uint32_t)e & one)); }
     __device__ __forceinline__ int mod(int e) const { return e - div(e) * D; }
 };
 
