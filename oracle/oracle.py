@@ -721,6 +721,8 @@ def _classic_lib():
         L.orc_classic_step.argtypes = [C.c_void_p]
         L.orc_classic_result.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int), _dp, _dp]
         L.orc_classic_population.argtypes = [C.c_void_p, _dp, _dp]
+        L.orc_classic_cma_state.argtypes = [C.c_void_p, _dp]
+        L.orc_classic_set_cma_state.argtypes = [C.c_void_p, _dp]
         L._classic_ready = True
     return L
 
@@ -755,3 +757,31 @@ class ClassicOracle:
         X, c = np.empty((self.cfg.np, self.cfg.dim)), np.empty(self.cfg.np)
         _classic_lib().orc_classic_population(self._h, _p(X), _p(c))
         return X, c
+
+    def cma_state(self):
+        """CMA-ES only: the state block in the kernel's layout (include/mbx_layout.h §10)."""
+        out = np.zeros(cma_state_doubles(self.cfg.np, self.cfg.dim, self.cfg.n_logpoint))
+        _classic_lib().orc_classic_cma_state(self._h, _p(out))
+        return out
+
+    def set_cma_state(self, block):
+        """CMA-ES only: adopt a state block in the kernel's layout (the inverse of cma_state)."""
+        block = np.ascontiguousarray(block, dtype=np.float64)
+        assert block.shape == (cma_state_doubles(self.cfg.np, self.cfg.dim, self.cfg.n_logpoint),)
+        _classic_lib().orc_classic_set_cma_state(self._h, _p(block))
+
+
+def cma_state_doubles(NP, D, nlog):
+    return 4 * D + 2 * D * D + 16 + nlog + 1
+
+
+def split_cma_state(st, NP, D, nlog):
+    """MBX_CMA_ST_* views of one CMA-ES state block."""
+    o = 0
+    out = {}
+    for name, n in (('centroid', D), ('C', D * D), ('B', D * D), ('diagD', D), ('ps', D), ('pc', D), ('scalars', 16), ('cost', nlog + 1)):
+        out[name] = st[o:o + n]
+        o += n
+    out['C'] = out['C'].reshape(D, D)
+    out['B'] = out['B'].reshape(D, D)
+    return out

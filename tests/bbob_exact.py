@@ -157,6 +157,8 @@ class Exact:
         return R(np.asarray(a, dtype=np.float64).astype(LD))
 
     def x(self, X):
+        if isinstance(X, R):                    # a position known to (value, bound): its bound propagates
+            return X
         return R(np.asarray(X, dtype=np.float64).astype(LD))
 
     def dot(self, M, y):
@@ -496,6 +498,8 @@ def _core(ops, desc, X):
         if k == 4:
             f = f + ops.lit('100') * _pen(ops, x, ub)
     elif k == 5:
+        if isinstance(X, R):
+            raise NotImplementedError('Linear Slope takes float64 positions only (its box clip is decided on X itself)')
         sh = np.asarray(d['dshift'], dtype=np.float64)
         v0, v1 = tab('v0'), tab('v1')
         X64 = np.asarray(X, dtype=np.float64)
@@ -788,8 +792,11 @@ def _desc(problem):
 
 
 def _eval(problem, X, draws=None, ops=None):
+    """X: float64 rows, or (Exact back-end only) an R [m, D] of positions known to within X.e: the allowance then covers any float64
+    evaluation at any float64 point within that bound."""
     d = _desc(problem)
-    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    if not isinstance(X, R):
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
     ops = ops or Exact()
     with np.errstate(over='ignore', invalid='ignore'):
         c = _core(ops, d, X)
