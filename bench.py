@@ -1,8 +1,11 @@
 #!/usr/bin/env python
 """Headline benchmark: RLEPSO rollout throughput on bbob d=10 pop=100, 4096 lock-step instances per MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line; everything else it can measure is a side
+leg that runs only with --full (see below), after the timed repeats, so the headline figures are the same with and without it.
 
 --dump-outputs DIR writes what the timed path handed its caller after the last timed step as DIR/<name>.npy (see dump_outputs); the last
 timed repeat starts from the inputs of the first (mbx_batch_rebind), so two builds run with the same arguments can be compared output for output.
@@ -19,15 +22,20 @@ timed region.
 
 Also reported on the same JSON line:
   roofline     — fused generation kernel: algorithmic bytes (54.0 KB per env-step) x live instances
-                 per launch / average kernel duration measured with HIP events on the launch stream, vs 8 TB/s.
-  roofline.valu — the kernel is VALU-issue bound, not bandwidth bound: wave-instructions per generation (one rocprofv3 --pmc child pass) priced at 4 cycles each
-                 against the SIMD cycles of the TIMED window, whose shader clock is sampled by a probe wave beside the kernel, no profiler attached
-                 (frac_timed_window; useful_f64_frac = that x float64 share x active lanes / 64); the profiled launch's own ratio stays as frac_profiled_launch.
+                 per launch / average kernel duration measured with HIP events on the launch stream, vs 8 TB/s.  traffic, valu and
+                 policy_mfma come from the newest committed profiles unless --full collects them in the run.
+With --full (rank 0, N = 1 only; each leg can still be left out with its --no-* option):
+  roofline.traffic, roofline.valu — the kernel is VALU-issue bound, not bandwidth bound: HBM bytes and wave-instructions per generation from rocprofv3 --pmc
+                 child passes, the instructions priced at 4 cycles each against the SIMD cycles of the TIMED window, whose shader clock the timed launches stamp
+                 themselves, no profiler attached (useful_f64_frac = frac x float64 share x active lanes / 64); the profiled launch's own ratio stays as
+                 frac_profiled_launch.  roofline.policy_mfma: a rocprofv3 --pmc child pass over config 4's Q-network launch.
+  roofline.fdr_fast_ms_per_step — the same window on a batch created with MBX_F_FDR_FAST.
+  plugin_view  — the single-instance compatibility view (PBO_Env + RLEPSO_Optimizer, B = 1).
   other_configs — one GPU's share of BASELINE.json configs 3 (LDE, NP = 50 and NP = 100), 4 (DE-DDQN on protein docking) and
-                 5 (RLEPSO D = 40, NP = 128): ms per lock-step step, env-steps/s, algorithmic bytes and roofline fraction (N = 1 only).
+                 5 (RLEPSO D = 40, NP = 128), and the reference's default settings: ms per lock-step step, env-steps/s, algorithmic bytes
+                 and roofline fraction.
   cpu_baseline — the C oracle (a float64 port of the reference path, oracle/mbx_oracle.c) on all host cores (one
-                 single-threaded worker per core) and on one core, on a bounded sample of the same workload
-                 (rank 0, N = 1 only).
+                 single-threaded worker per core) and on one core, on a bounded sample of the same workload.
 """
 import argparse
 import json
@@ -561,10 +569,13 @@ def main():
     ap.add_argument('--repeats', type=int, default=0,
                     help='how often the (warm-up + K timed generations) window is measured; 0 (default): once when it takes >= 0.5 s, else 30-200 times '
                          '(~2 s of timed windows), the line reports the median repeat')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the configs 3 / 4 / 5 legs (other_configs)')
-    ap.add_argument('--no-fdr-fast', action='store_true', help='skip the side leg that times the MBX_F_FDR_FAST kernels on the same window (roofline.fdr_fast_ms_per_step); kernel traces of the headline alone')
-    ap.add_argument('--no-pmc', action='store_true', help='do not collect roofline.traffic in this run (two rocprofv3 --pmc child passes, ~40 s); use the newest committed profile')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed repeats, also run the side legs: fdr_fast, plugin_view + other_configs, the rocprofv3 child passes '
+                         '(roofline.traffic / valu / policy_mfma measured in the run) and cpu_baseline.  Off: the headline window alone')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the cpu_baseline leg')
+    ap.add_argument('--no-other-configs', action='store_true', help='with --full: skip the plugin_view and configs 3 / 4 / 5 legs (other_configs)')
+    ap.add_argument('--no-fdr-fast', action='store_true', help='with --full: skip the side leg that times the MBX_F_FDR_FAST kernels on the same window (roofline.fdr_fast_ms_per_step)')
+    ap.add_argument('--no-pmc', action='store_true', help='with --full: do not collect roofline.traffic / valu / policy_mfma in this run (rocprofv3 --pmc child passes, ~40 s); use the newest committed profiles')
     ap.add_argument('--functions', default='all24',
                     help="all24 (default: every bbob function round-robin), train18 (the bbob-easy train split), or a comma list of "
                          "function ids (SURVEY §8(d) C2 asks for the split and per-function figures next to the headline)")
@@ -592,6 +603,8 @@ def main():
         return qnet_child()
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit('bench.py needs --steps >= 1 and --warmup >= 0')
+    if not args.full:                       # a plain run: the headline window alone, every side leg off
+        args.no_cpu_baseline = args.no_other_configs = args.no_fdr_fast = args.no_pmc = True
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))

@@ -1,4 +1,5 @@
-"""bench.py's output contract: one JSON line with the driver's keys plus `roofline` and `cpu_baseline`."""
+"""bench.py's output contract: one JSON line with the driver's keys plus `roofline`; with --full also the side legs (`other_configs`, in-run
+profiler figures, `cpu_baseline`)."""
 import json
 import os
 import subprocess
@@ -26,7 +27,7 @@ def test_cpu_baseline_worker_runs_whole_episodes(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '40', '--warmup', '4', '--no-cpu-baseline'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '40', '--warmup', '4', '--full', '--no-cpu-baseline'],
                          capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-600:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -86,6 +87,26 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     for e in oc:
         assert e['ms_per_step'] > 0 and abs(e['env_steps_per_s'] - e['instances'] / (e['ms_per_step'] * 1e-3)) <= 1e-6 * e['env_steps_per_s']
         assert 0 < e['roofline_frac'] < 1
+
+
+@pytest.mark.gpu
+def test_plain_bench_runs_the_headline_window_alone():
+    """Without --full the line carries the headline window and nothing that needs a run of its own: no side legs, no profiler children, no
+    CPU baseline; the roofline figures that need profiler counters come from the committed profiles."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5'],
+                         capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert out.returncode == 0, out.stderr[-600:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['n_gpus'] == 1 and d['steps'] == 20 and d['warmup'] == 5 and d['unit'] == 'env-steps/s' and d['higher_is_better'] is True and d['dtype'] == 'f64'
+    assert abs(d['value'] - d['config']['live_env_steps'] / (d['ms_per_step'] * 1e-3 * d['steps'])) <= 1e-6 * d['value']
+    assert not {'plugin_view', 'other_configs', 'cpu_baseline'} & set(d), sorted(d)
+    r = d['roofline']
+    assert r['fdr_fast_ms_per_step'] is None and r['traffic_measured_in_run'] is False
+    assert r['valu'] is None or not r['valu']['measured_in_run']
+    assert r['policy_mfma'] is None or r['policy_mfma']['measured_in_run'] is False
+    assert r['kernel'].startswith('k_rlepso_run') and r['generations_per_launch'] == 20 and 0 < r['frac'] < 1
 
 
 @pytest.mark.gpu

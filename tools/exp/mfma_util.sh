@@ -5,7 +5,7 @@
 OUT=gpurun_out/${1:-mfma}; mkdir -p $OUT
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_F64 GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d /tmp/mfma_pmc -o p -- python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > /tmp/mfma_pmc.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_F64 GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d "$TMPDIR/mfma_pmc" -o p -- python $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-pmc > "$TMPDIR/mfma_pmc.log" 2>&1
 python - "$ROOT/$OUT/mfma_utilisation.json" <<'PY'
 import csv, glob, json, re, sys, collections
 v = collections.defaultdict(lambda: collections.defaultdict(list))
