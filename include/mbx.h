@@ -107,6 +107,7 @@ int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, double* d_f,
 #define MBX_ALGO_PSO    9   /* src/optimizer/deap_pso.py           one step = one sweep (np moves)    -- classic baseline, no agent */
 #define MBX_ALGO_CMAES  10  /* src/optimizer/deap_cmaes.py         one step = one generation          -- classic baseline, no agent */
 #define MBX_ALGO_GLPSO  11  /* src/optimizer/gl_pso.py             one step = one generation (2 NP FEs) -- classic baseline, no agent */
+#define MBX_ALGO_JDE21  13  /* src/optimizer/jde21.py              one step = one update (2 bNP FEs), np = 170 -- classic baseline, no agent (12 is not assigned) */
 
 typedef struct mbx_algo_cfg {
     int32_t algo;          /* MBX_ALGO_*                                                          */
@@ -145,7 +146,7 @@ int mbx_batch_flags(const mbx_batch* b);
  *   GLEET         : state [np*27]  (gleet_optimizer.py:111-124),            action [np] float32
  *   QLPSO         : state [1]      (qlpso_optimizer.py:89-90,125),          action [1] int32 in {0..3}
  *   DE, PSO, CMAES: state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
- *   GLPSO         : state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step) */
+ *   GLPSO, JDE21  : state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step) */
 int mbx_state_dim(const mbx_algo_cfg* cfg);
 int mbx_action_dim(const mbx_algo_cfg* cfg);
 /* number of doubles of external random numbers one instance consumes per step (see mbx_set_tape) */

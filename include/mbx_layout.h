@@ -371,6 +371,66 @@
 #define MBX_SITE_GL_NOISE_B  21u
 #define MBX_SITE_GL_TOUR     22u
 
+/* ---------------------------------------------------------------- 12. JDE21 (jde21.py) layouts
+ * No agent: mbx_reset is __init_population (:68-81: NP = 170 random rows, one evaluation, F = 0.5, Cr = 0.9 -- 170 FEs), every mbx_step
+ * (actions = NULL) is one __update (:83-265): a big-population pass of bNP trials with crowding, then bNP / 10 small-population passes of 10
+ * trials -- 2 bNP FEs; bNP = 160 halves up to three times.  cfg.np must be 170.  state [1] = fes / maxFEs.
+ * state block: pop[NP*D] cost[NP] F[NP] Cr[NP] crowd[NP] scalars[16] cost_curve[nlog+1].  Rows [0, bNP) are the big population, rows
+ * [bNP, bNP + 10) the small one, rows beyond are dead after a halving.  crowd[i], i < bNP: the crowding target of trial i in the last step
+ * (diagnostic).  scalars beyond the common ones: bNP, cbest, cbest_id and the counters nReset / sReset / cCopy (zeroed by mbx_reset).
+ * A step has R = 2 (NP - 10) = 320 trial rows: row i < 160 is trial i of the big pass, row 160 + 10 p + i trial i of small pass p.
+ * tape per reset: pos_u[NP*D] | noise[3*NP]
+ * tape per step (per-row slots are [R] each; index values are the RESOLVED ones, after the reference's rejection loops, as doubles; the
+ *   small passes' indices are absolute rows bNP + k):
+ *   r1 | r2 | r3 | randF_u | randCr_u | rvsF | rvsCr | jrand | noise[3*R] | cross_u[R*D] | reseed_big_u[(NP-10)*D] | reseed_small_u[10*D]
+ *   (the kernel applies u * Fu + Fl etc.; reseed_* are read only when the reset branch fires, i.e. when the reference draws them).
+ * Philox, counter (index, site, gen, episode); reset gen = 0, step gen = number of the step; t = trial row:
+ *   MBX_SITE_JD_IDX(t*32+a)  attempt a = 0..25 of the bounded redraw: mulhi(w0, n) = r1, mulhi(w1, n') = r2, mulhi(w2, n') = r3, each with
+ *                            its own attempt counter (a draw is redrawn while the reference's test rejects it, 25 times at most, and
+ *                            then kept); a = 0: mulhi(w3, D) = jrand
+ *   MBX_SITE_JD_PART(t)      u53(w0,w1) = randF_u, u53(w2,w3) = randCr_u        MBX_SITE_JD_PART2(t)  u53(w0,w1) = rvsF, u53(w2,w3) = rvsCr
+ *   MBX_SITE_JD_CROSS(t*D+d) u53(w0,w1) = cross_u;  reset: index e, u53(w0,w1) = pos_u
+ *   MBX_SITE_JD_RESEED(e)    u53(w0,w1) = reseed_big_u[e], u53(w2,w3) = reseed_small_u[e]
+ *   MBX_SITE_JD_NOISE_A/B(t) evaluation of trial row t;  reset: MBX_SITE_NOISE1_A/B(i)                                                      */
+#define MBX_JDE21_NP   170
+#define MBX_JDE21_SNP  10
+#define MBX_JDE21_ROWS(NP)               (2 * ((int64_t)(NP) - MBX_JDE21_SNP))
+#define MBX_JDE21_TAPE_POS(NP, D)        ((int64_t)0)
+#define MBX_JDE21_TAPE_NOISE_INIT(NP, D) ((int64_t)(NP) * (D))
+#define MBX_JDE21_TAPE_R1(NP, D)         ((int64_t)0)
+#define MBX_JDE21_TAPE_R2(NP, D)         (MBX_JDE21_ROWS(NP))
+#define MBX_JDE21_TAPE_R3(NP, D)         (2 * MBX_JDE21_ROWS(NP))
+#define MBX_JDE21_TAPE_RANDF(NP, D)      (3 * MBX_JDE21_ROWS(NP))
+#define MBX_JDE21_TAPE_RANDCR(NP, D)     (4 * MBX_JDE21_ROWS(NP))
+#define MBX_JDE21_TAPE_RVSF(NP, D)       (5 * MBX_JDE21_ROWS(NP))
+#define MBX_JDE21_TAPE_RVSCR(NP, D)      (6 * MBX_JDE21_ROWS(NP))
+#define MBX_JDE21_TAPE_JRAND(NP, D)      (7 * MBX_JDE21_ROWS(NP))
+#define MBX_JDE21_TAPE_NOISE(NP, D)      (8 * MBX_JDE21_ROWS(NP))
+#define MBX_JDE21_TAPE_CROSS(NP, D)      (11 * MBX_JDE21_ROWS(NP))
+#define MBX_JDE21_TAPE_RESEED_B(NP, D)   (11 * MBX_JDE21_ROWS(NP) + MBX_JDE21_ROWS(NP) * (D))
+#define MBX_JDE21_TAPE_RESEED_S(NP, D)   (MBX_JDE21_TAPE_RESEED_B(NP, D) + ((int64_t)(NP) - MBX_JDE21_SNP) * (D))
+#define MBX_JDE21_TAPE_STRIDE(NP, D)     (MBX_JDE21_TAPE_RESEED_S(NP, D) + (int64_t)MBX_JDE21_SNP * (D))
+#define MBX_JDE21_ST_POP(NP, D)          ((int64_t)0)
+#define MBX_JDE21_ST_COST(NP, D)         ((int64_t)(NP) * (D))
+#define MBX_JDE21_ST_F(NP, D)            ((int64_t)(NP) * (D) + (NP))
+#define MBX_JDE21_ST_CR(NP, D)           ((int64_t)(NP) * (D) + 2 * (int64_t)(NP))
+#define MBX_JDE21_ST_CROWD(NP, D)        ((int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_JDE21_ST_SCALARS(NP, D)      ((int64_t)(NP) * (D) + 4 * (int64_t)(NP))
+#define MBX_JDE21_STATE_DOUBLES(NP, D, NLOG) (MBX_JDE21_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)
+#define MBX_SC_JD_BNP      10
+#define MBX_SC_JD_CBEST    11
+#define MBX_SC_JD_CBEST_ID 12
+#define MBX_SC_JD_NRESET   13
+#define MBX_SC_JD_SRESET   14
+#define MBX_SC_JD_CCOPY    15
+#define MBX_SITE_JD_IDX      23u
+#define MBX_SITE_JD_PART     24u
+#define MBX_SITE_JD_PART2    25u
+#define MBX_SITE_JD_CROSS    26u
+#define MBX_SITE_JD_RESEED   27u
+#define MBX_SITE_JD_NOISE_A  28u
+#define MBX_SITE_JD_NOISE_B  29u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

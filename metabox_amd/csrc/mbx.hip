@@ -33,6 +33,7 @@
 #include "mbx_gleet_policy.hpp"
 #include "mbx_classic.hpp"
 #include "mbx_glpso.hpp"
+#include "mbx_jde21.hpp"
 // k_rlepso_run / k_lde_run are compiled in translation units of their own (mbx_run_rlepso.hip, mbx_run_lde.hip) and only declared here;
 // -DMBX_SINGLE_TU (instrumented builds: the phase counters are a __device__ array, one copy per translation unit) instantiates them in this file instead
 #ifndef MBX_SINGLE_TU
@@ -165,6 +166,12 @@ static AlgoGeom geom_of(const mbx_algo_cfg& c)
         g.sc_off = MBX_GLPSO_ST_SCALARS(c.np, c.dim);
         g.tape_stride = MBX_GLPSO_TAPE_STRIDE(c.np, c.dim);
         g.lds_doubles = gp_lds_doubles(c.np, c.dim);
+        g.state_dim = 1; g.action_dim = 0;
+    } else if (c.algo == MBX_ALGO_JDE21) {
+        g.state_doubles = MBX_JDE21_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
+        g.sc_off = MBX_JDE21_ST_SCALARS(c.np, c.dim);
+        g.tape_stride = MBX_JDE21_TAPE_STRIDE(c.np, c.dim);
+        g.lds_doubles = jd_lds_doubles(c.np, c.dim);
         g.state_dim = 1; g.action_dim = 0;
     }
     return g;
@@ -456,8 +463,10 @@ extern "C" int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, dou
 static int check_cfg(const mbx_algo_cfg* c)
 {
     if (!c) return fail(MBX_E_ARG, "null cfg");
-    if (c->algo < MBX_ALGO_RLEPSO || c->algo > MBX_ALGO_GLPSO)
+    // the ids this build has kernels for (12 is not assigned)
+    if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21))
         return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
+    if (c->algo == MBX_ALGO_JDE21 && c->np != MBX_JDE21_NP) return fail(MBX_E_ARG, "JDE21 runs np = %d (160 + 10 rows), not %d", MBX_JDE21_NP, c->np);
     if (c->np < 4 || c->np > kThreads) return fail(MBX_E_ARG, "np %d outside [4, %d]", c->np, kThreads);
     if (c->dim < 2 || c->dim > 64) return fail(MBX_E_ARG, "dim %d outside [2, 64]", c->dim);
     if (c->algo == MBX_ALGO_RLEPSO && (c->n_group < 1 || c->n_group > 16 || c->np / c->n_group < 1))
@@ -661,6 +670,10 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
     } else if (cfg->algo == MBX_ALGO_GLPSO) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_glpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_glpso_generation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    } else if (cfg->algo == MBX_ALGO_JDE21) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_jde21_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_jde21_generation<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_jde21_generation<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     } else if (cfg->algo == MBX_ALGO_QLPSO) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -771,6 +784,8 @@ extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
                            (hipStream_t)stream, make_params(b), (int)b->cfg.algo, d_state_out);
     else if (b->cfg.algo == MBX_ALGO_GLPSO)
         hipLaunchKernelGGL(k_glpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
+    else if (b->cfg.algo == MBX_ALGO_JDE21)
+        hipLaunchKernelGGL(k_jde21_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_GLEET)
@@ -796,7 +811,7 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
                         void* stream)
 {
     const bool no_agent = b && (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH || b->cfg.algo == MBX_ALGO_DE || b->cfg.algo == MBX_ALGO_PSO ||
-                                b->cfg.algo == MBX_ALGO_CMAES || b->cfg.algo == MBX_ALGO_GLPSO);
+                                b->cfg.algo == MBX_ALGO_CMAES || b->cfg.algo == MBX_ALGO_GLPSO || b->cfg.algo == MBX_ALGO_JDE21);
     if (!b || (!d_actions && !no_agent)) return fail(MBX_E_ARG, "mbx_step: bad arguments");
     if (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH)
         hipLaunchKernelGGL(k_rs_population, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), 0, d_state_out,
@@ -814,6 +829,12 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
                            (hipStream_t)stream, make_params(b), d_state_out, d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_GLPSO)
         hipLaunchKernelGGL(k_glpso_generation, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
+                           d_reward_out, d_done_out);
+    else if (b->cfg.algo == MBX_ALGO_JDE21 && jd_waves((int64_t)b->lds_bytes) == 3)
+        hipLaunchKernelGGL(k_jde21_generation<3>, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
+                           d_reward_out, d_done_out);
+    else if (b->cfg.algo == MBX_ALGO_JDE21)
+        hipLaunchKernelGGL(k_jde21_generation<2>, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
                            d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_step<false>, dim3(b->B), dim3(kThreads), (size_t)ql_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double),

@@ -734,6 +734,7 @@ __device__ void eval_rows_protein(const PT& P, const EvalLds& L, int n_rows)
 // caller passes it (population_costs): one barrier interval less than a pass of its own.
 struct RowPost {
     const Rng* rng; const double* tape_noise; uint32_t siteA, siteB; int n_total;
+    int row0 = 0;          // the rows evaluated are rows row0.. of a population of n_total (chunked evaluation): offset of the noise draws
 };
 
 // NOISE: what the caller knows at compile time -- -1 nothing (the problem record decides), 0 a noise-free function (the noise models are compiled out), 1 a noisy one
@@ -742,8 +743,9 @@ __device__ __forceinline__ double row_post(const PT& P, const RowPost& rp, int i
 {
     if (NOISE != 0 && (NOISE == 1 || P.noise_kind != MBX_NOISE_NONE)) {
         double a, b, c;
-        if (rp.tape_noise) { a = rp.tape_noise[i]; b = rp.tape_noise[rp.n_total + i]; c = rp.tape_noise[2 * rp.n_total + i]; }
-        else philox_noise(*rp.rng, (uint32_t)i, rp.siteA, rp.siteB, P.noise_kind, a, b, c);
+        const int r = i + rp.row0;
+        if (rp.tape_noise) { a = rp.tape_noise[r]; b = rp.tape_noise[rp.n_total + r]; c = rp.tape_noise[2 * rp.n_total + r]; }
+        else philox_noise(*rp.rng, (uint32_t)r, rp.siteA, rp.siteB, P.noise_kind, a, b, c);
         f = apply_noise(P, f, a, b, c);
     }
     return isnan(P.optimum) ? f : f - P.optimum;
@@ -1256,6 +1258,21 @@ __device__ __forceinline__ void population_costs(const PT& P, const EvalLds& L, 
     __syncthreads();
 #else
     eval_rows<DC, MD, PT, KC, KIND, NOISE>(P, L, n, &post);
+#endif
+}
+
+// The same for a chunk of a larger population: the n rows in L.X are rows row0 .. row0 + n - 1 of n_total, whose noise draws they take
+// (tape rows [3, n_total], Philox index row0 + i).
+template <class PT = DevProblem>
+__device__ __forceinline__ void population_costs(const PT& P, const EvalLds& L, int n, const Rng& rng, const double* tape_noise,
+                                                 uint32_t siteA, uint32_t siteB, int row0, int n_total)
+{
+    const RowPost post{&rng, tape_noise, siteA, siteB, n_total, row0};
+#ifdef MBX_ABLATE_EVAL
+    for (int i = threadIdx.x; i < n; i += MBX_NT) L.F[i] = row_post(P, post, i, L.X[i * P.dim] * L.X[i * P.dim] + P.bias);
+    __syncthreads();
+#else
+    eval_rows<0, 0, PT>(P, L, n, &post);
 #endif
 }
 

@@ -9,3 +9,4 @@ from .gleet_optimizer import GLEET_Optimizer
 from .qlpso_optimizer import QLPSO_Optimizer
 from .classic import DEAP_CMAES, DEAP_DE, DEAP_PSO
 from .gl_pso import GL_PSO
+from .jde21 import JDE21

@@ -1360,7 +1360,145 @@ def gen_glpso():
     np.savez_compressed(os.path.join(OUT, 'glpso_traces.npz'), **data)
 
 
-SECTIONS = {'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+def run_jde21_episode(problem, config, opt=None):
+    """One reference JDE21 episode on the global numpy stream (the caller seeds it).  Row 0 of every per-generation array is the state
+    after __init_population, row g + 1 the state after __update number g.  `cost` / `crowd` are ragged (bNP + 10 live costs, bNP crowding
+    targets per row) and stored flattened.  The counters are relative to the start of the episode (they live on the object).
+    `cid_r1` is cbest_id as the big pass's r1 rejection test sees it, `nreset` / `sreset` whether the reset branches of that update drew."""
+    from optimizer import JDE21
+    import copy
+    opt = opt if opt is not None else JDE21(copy.deepcopy(config))
+    problem.reset()
+    get = lambda name: getattr(opt, '_JDE21__' + name)          # noqa: E731
+    rec = dict(gbest=[], fes=[], cbest=[], cbest_id=[], bnp=[], counters=[], cid_r1=[0], nreset=[0], sreset=[0])
+    costs, crowd, snaps, seen = [], [], {}, {}
+    base = np.array([get('nReset'), get('sReset'), get('cCopy')])
+    orig_crowding, orig_reinit = get('crowding'), get('reinitialize')
+
+    def crowding(group, vs):
+        ids = orig_crowding(group, vs)
+        seen['crowd'] = np.asarray(ids).astype(np.uint8)
+        return ids
+
+    def reinitialize(size, ub, lb):
+        if size != 10:                                           # the big reset: cbest_id is recomputed before r1 is drawn (:161-162)
+            c = get('cost').copy()
+            c[:size] = 1e15
+            seen['cid_r1'] = int(np.argmin(c))
+        return orig_reinit(size, ub, lb)
+    setattr(opt, '_JDE21__crowding', crowding)
+    setattr(opt, '_JDE21__reinitialize', reinitialize)
+
+    def snap(full):
+        rec['gbest'].append(float(opt.gbest))
+        rec['fes'].append(float(get('FEs')))
+        rec['cbest'].append(float(get('cbest')))
+        rec['cbest_id'].append(int(get('cbest_id')))
+        rec['bnp'].append(int(get('bNP')))
+        rec['counters'].append(np.array([get('nReset'), get('sReset'), get('cCopy')]) - base)
+        costs.append(np.array(get('cost'), dtype=np.float64))
+        if full:
+            g = len(rec['gbest']) - 1
+            snaps[g] = (np.array(get('population'), dtype=np.float64), np.array(get('F'), dtype=np.float64), np.array(get('Cr'), dtype=np.float64))
+    getattr(opt, '_JDE21__init_population')(problem)
+    snap(False)
+    done = False
+    while not done and get('FEs') < config.maxFEs:
+        before = rec['counters'][-1].copy()
+        seen.clear()
+        seen['cid_r1'] = int(get('cbest_id'))
+        done = getattr(opt, '_JDE21__update')(problem)
+        fired = np.array([get('nReset'), get('sReset'), get('cCopy')]) - base - before
+        rec['cid_r1'].append(seen['cid_r1']); rec['nreset'].append(int(fired[0])); rec['sreset'].append(int(fired[1]))
+        crowd.append(seen['crowd'])
+        snap(bool(fired[0] or fired[1]))
+    # what run_episode does after its loop (:273-276)
+    if len(opt.cost) >= config.n_logpoint + 1:
+        opt.cost[-1] = opt.gbest
+    else:
+        opt.cost.append(opt.gbest)
+    snap_g = sorted(set(snaps) | {len(rec['gbest']) - 1})
+    if snap_g[-1] not in snaps:
+        snaps[snap_g[-1]] = (np.array(get('population'), dtype=np.float64), np.array(get('F'), dtype=np.float64), np.array(get('Cr'), dtype=np.float64))
+    out = {k: np.array(v, dtype=np.float64 if k in ('gbest', 'fes', 'cbest') else np.int32) for k, v in rec.items()}
+    out['cost_rows'] = np.concatenate(costs)
+    out['crowd'] = np.concatenate(crowd) if crowd else np.zeros(0, np.uint8)
+    out['snap_gens'] = np.array(snap_g, dtype=np.int32)
+    for g in snap_g:
+        out[f'snap{g}/pop'], out[f'snap{g}/F'], out[f'snap{g}/Cr'] = snaps[g]
+    out['cost'] = np.array(opt.cost, dtype=np.float64)
+    out['max_abs_x'] = np.float64(max(np.abs(snaps[g][0]).max() for g in snap_g))
+    delattr(opt, '_JDE21__crowding'); delattr(opt, '_JDE21__reinitialize')
+    return out, opt
+
+
+def gen_jde21():
+    """JDE21 (src/optimizer/jde21.py): seeded reference episodes.  The numpy draws are NOT stored: the tests regenerate them from the seed
+    in the reference's draw order.  `max_fes` is reduced where a whole episode would make the fixture large.
+    The big-population reset (nReset, :154-162) fired in none of these episodes nor in the bounded search below (bbob F7 at D 10 and the
+    protein instance, NRESET_SEARCH seeds each); when a searched seed does fire it, it is added as a case of its own.  The branch is
+    covered by a crafted-state test (tests/test_jde21.py)."""
+    scratch = tempfile.mkdtemp()
+    data, cases = {}, []
+
+    def put(key, rec, max_fes):
+        cases.append(key)
+        for k, v in rec.items():
+            data[f'{key}/{k}'] = v
+        data[f'{key}/max_fes'] = np.float64(max_fes)
+        data[f'{key}/next_rand'] = np.float64(np.random.rand())      # stream position after the episode(s)
+        print(key, len(rec['gbest']) - 1, rec['fes'][-1], rec['gbest'][-1], int(rec['bnp'][-1]) + 10, rec['counters'][-1], float(rec['max_abs_x']), len(rec['cost']))
+
+    def config_for(suite, dim, max_fes):
+        argv = ['--problem', suite] + ([] if suite == 'protein' else ['--dim', str(dim)])
+        config = ref_import.ref_config(argv, scratch)
+        config.maxFEs = max_fes
+        config.log_interval = max_fes // config.n_logpoint
+        return config
+    # (suite, dim, function, seed, maxFEs): early stops (F1, F101), the missed third halving (F15 at the full budget), three halvings
+    # (D 30 F10), small-population resets and out-of-box rows (F7), repeated elite copies (F22), every noise kind
+    jobs = [('bbob', 10, 1, 51, 20000), ('bbob', 10, 15, 53, 20000), ('bbob', 30, 10, 54, 12000), ('bbob', 10, 7, 58, 20000),
+            ('bbob', 10, 22, 2, 8000), ('bbob', 10, 24, 55, 6000),
+            ('bbob-noisy', 10, 101, 52, 20000), ('bbob-noisy', 10, 102, 56, 6000), ('bbob-noisy', 10, 103, 57, 6000)]
+    problems = {}
+    for suite, dim, fid, seed, max_fes in jobs:
+        if (suite, dim) not in problems:
+            tr, te, _ = all_problems(suite, dim)
+            problems[(suite, dim)] = {fid_of(p): p for p in tr + te}
+        config = config_for(suite, dim, max_fes)
+        np.random.seed(seed)
+        rec, _ = run_jde21_episode(problems[(suite, dim)][fid], config)
+        put(f'{suite}/{dim}/{fid}/{seed}', rec, max_fes)
+    byid, _, _ = protein_problems()
+    config = config_for('protein', 12, 1000)
+    np.random.seed(59)
+    rec, _ = run_jde21_episode(byid['1ATN_7'], config)
+    put('protein/12/1ATN_7/59', rec, 1000)
+    # a second episode on the same optimizer object (another problem, the stream continues): nothing observable carries over
+    config = config_for('bbob', 10, 6000)
+    np.random.seed(60)
+    first, opt = run_jde21_episode(problems[('bbob', 10)][3], config)
+    second, _ = run_jde21_episode(problems[('bbob', 10)][7], config, opt)
+    for k, v in first.items():
+        data[f'second/10/3-7/60/first/{k}'] = v
+    put('second/10/3-7/60', second, 6000)
+    # bounded search for an episode in which the big-population reset fires
+    NRESET_SEARCH = 12
+    for suite, dim, fid, max_fes in (('bbob', 10, 7, 20000), ('protein', 12, '1ATN_7', 1000)):
+        config = config_for(suite, dim, max_fes)
+        for seed in range(200, 200 + NRESET_SEARCH):
+            np.random.seed(seed)
+            rec, _ = run_jde21_episode(byid[fid] if suite == 'protein' else problems[(suite, dim)][fid], config)
+            if rec['counters'][-1][0] > 0:
+                put(f'{suite}/{dim}/{fid}/{seed}', rec, max_fes)
+                break
+        else:
+            print('nReset: no seed of', suite, fid, 'fires it')
+    data['cases'] = np.array(cases)
+    np.savez_compressed(os.path.join(OUT, 'jde21_traces.npz'), **data)
+
+
+SECTIONS = {'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

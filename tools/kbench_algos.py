@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -169,5 +169,26 @@ if 'glpso' in which:
                 for _ in range(n): b.step(None)
             run(3); dt = timed(run, 40)
             print(json.dumps({'path': f'{name} bbob d={dim} NP=100, {B} instances, one launch per generation', 'us_per_step': dt / 40 * 1e6,
+                              'launch_info': b.launch_info()}))
+            b.close()
+if 'jde21' in which:
+    # JDE21 (one mbx_step = one update: 160 big trials with crowding + 16 x 10 small trials = 320 evaluated rows) next to Random_search's
+    # 100-row kernel in the same process: 4096 instances, bbob round-robin, a horizon long enough that no halving is met (bNP stays 160)
+    # and every instance stays live.  Under rocprofv3 --kernel-trace --stats the per-launch times of k_jde21_generation and
+    # k_rs_population come from the trace; the wall times here include the launch gaps.  A library built with -DMBX_ABLATE_CROWD (MBX_LIB)
+    # gives the step without the crowding search.
+    from metabox_amd._abi import ALGO_JDE21, ALGO_RANDOM_SEARCH
+    from metabox_amd.suite import Batch, Suite
+    for dim in (10, 30):
+        cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+        tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+        s = Suite(ps); B = 4096
+        for algo, name, np_ in ((ALGO_JDE21, 'k_jde21_generation', 170), (ALGO_RANDOM_SEARCH, 'k_rs_population', 100)):
+            b = Batch(s, algo, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, np_, 10 ** 8, 10 ** 6, 50, early_stop=False)
+            b.reset()
+            def run(n):
+                for _ in range(n): b.step(None)
+            run(3); dt = timed(run, 40)
+            print(json.dumps({'path': f'{name} bbob d={dim} NP={np_}, {B} instances, one launch per generation', 'us_per_step': dt / 40 * 1e6,
                               'launch_info': b.launch_info()}))
             b.close()
