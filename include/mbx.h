@@ -108,6 +108,7 @@ int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, double* d_f,
 #define MBX_ALGO_CMAES  10  /* src/optimizer/deap_cmaes.py         one step = one generation          -- classic baseline, no agent */
 #define MBX_ALGO_GLPSO  11  /* src/optimizer/gl_pso.py             one step = one generation (2 NP FEs) -- classic baseline, no agent */
 #define MBX_ALGO_JDE21  13  /* src/optimizer/jde21.py              one step = one update (2 bNP FEs), np = 170 -- classic baseline, no agent (12 is not assigned) */
+#define MBX_ALGO_MADDE  15  /* src/optimizer/madde.py              one step = one update (NP FEs), np = 2 dim^2, dim <= 40 -- classic baseline, no agent (12 and 14 are not assigned and stay rejected) */
 
 typedef struct mbx_algo_cfg {
     int32_t algo;          /* MBX_ALGO_*                                                          */

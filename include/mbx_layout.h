@@ -431,6 +431,82 @@
 #define MBX_SITE_JD_NOISE_A  28u
 #define MBX_SITE_JD_NOISE_B  29u
 
+/* ---------------------------------------------------------------- 13. MadDE (madde.py) layouts
+ * No agent: mbx_reset is __init_population (:179-195: N0 = 2 D^2 random rows, one evaluation, MF = MCr = 0.2, empty archive -- N0 FEs),
+ * every mbx_step (actions = NULL) is one __update (:197-272), NP FEs; NP shrinks linearly from N0 to 4, the archive holds at most
+ * NA = int(2.3 NP) rows.  cfg.np must be 2 D^2, D <= 40.  state [1] = fes / maxFEs.  A0 = int(2.3 N0), H = 10 D.
+ * state block: pop[2][N0*D] cost[N0] archive[A0*D] MF[H] MCr[H] u[N0*D] ncost[N0] F[N0] Cr[N0] z[N0] c[N0] pm[4] scalars[16] cost_curve[nlog+1].
+ *   pop: two buffers, scalars[MBX_SC_MD_LIVE] names the live one; its rows [0, NP) are sorted by (cost, row before the sort), i.e. numpy's
+ *   kind='stable' order (the reference's introsort is not reproducible among equal keys); the sort runs at the end of reset and of every
+ *   update and moves the rows into the other buffer.  cost: the live costs in that order.  u / ncost / F / Cr: trial rows, their costs and
+ *   the F / Cr they were made with, of the last update (after reset: the initial rows in draw order and their costs); rows [0, NP before
+ *   the update).  z / c: the standard normal / Cauchy variates behind Cr / F of the last update (diagnostic: the Philox route makes them
+ *   with the device's log / cos / tan, which the host does not reproduce to the bit; a tape rebuilt from a Philox step takes them from here).  pm[0..2]: strategy probabilities; mbx_reset leaves them alone (the reference sets them in __init__ only), a new batch
+ *   starts at 1/3.  scalars beyond the common ones: NP, archive rows, NA, k (memory slot), live buffer.
+ * tape per reset: pos_u[N0*D] | noise[3*N0]
+ * tape per step, slots of [N0] indexed by the row i of the sorted population (index values as doubles, RESOLVED, i.e. after the
+ *   reference's bounded redraws, and LOCAL as the reference draws them: rb a row of pbest / qbest, r1 a rank inside the row's strategy
+ *   group, r2 a rank inside the group or, from the group's size on, an archive row):
+ *   mem_idx | z | c | choice_u | rb | r1 | r2 | rvs | qpick | jrand | noise[3*N0] | arc_idx[N0] | cross_u[N0*D]
+ *   z / c are STANDARD normal / Cauchy variates (the kernel forms MCr + 0.1 z and c 0.1 + MF); qpick is the row of the qBX pool a row with
+ *   rvs <= 0.01 crosses with; arc_idx[k] is the archive row that the improved row of rank k overwrites (read for ranks past the appends).
+ * Philox, counter (index, site, gen, episode); reset gen = 0, step gen = number of the step; i = row:
+ *   MBX_SITE_MD_PAR(i)       mulhi(w0, H) = mem_idx, mulhi(w1, pool) = qpick, mulhi(w2, D) = jrand, w3 / 2^32 = rvs
+ *   MBX_SITE_MD_NORM(i)      Box-Muller of u53(w0,w1), u53(w2,w3): the cosine half = z
+ *   MBX_SITE_MD_CAUCHY(i)    tan(pi (u53(w0,w1) - 0.5)) = c, u53(w2,w3) = choice_u
+ *   MBX_SITE_MD_IDX(i*32+a)  attempt a = 0..25 of the bounded redraw: mulhi(w0, n_b) = rb, mulhi(w1, n) = r1, mulhi(w2, n') = r2, each with
+ *                            its own attempt counter
+ *   MBX_SITE_MD_CROSS(i*D+d) u53(w0,w1) = cross_u;  reset: index e, u53(w0,w1) = pos_u
+ *   MBX_SITE_MD_ARC(k)       mulhi(w0, archive rows) = arc_idx[k]
+ *   MBX_SITE_MD_NOISE_A/B(i) evaluation of trial row i;  reset: MBX_SITE_NOISE1_A/B(i)                                                      */
+#define MBX_MADDE_NP(D)                  (2 * (D) * (D))
+#define MBX_MADDE_DIM_MAX                40
+#define MBX_MADDE_ARC(NP)                ((int64_t)(2.3 * (double)(NP)))
+#define MBX_MADDE_H(D)                   (10 * (int64_t)(D))
+#define MBX_MADDE_TAPE_POS(NP, D)        ((int64_t)0)
+#define MBX_MADDE_TAPE_NOISE_INIT(NP, D) ((int64_t)(NP) * (D))
+#define MBX_MADDE_TAPE_MEM(NP, D)        ((int64_t)0)
+#define MBX_MADDE_TAPE_Z(NP, D)          ((int64_t)(NP))
+#define MBX_MADDE_TAPE_C(NP, D)          (2 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_CHOICE(NP, D)     (3 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_RB(NP, D)         (4 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_R1(NP, D)         (5 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_R2(NP, D)         (6 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_RVS(NP, D)        (7 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_QPICK(NP, D)      (8 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_JRAND(NP, D)      (9 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_NOISE(NP, D)      (10 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_ARC(NP, D)        (13 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_CROSS(NP, D)      (14 * (int64_t)(NP))
+#define MBX_MADDE_TAPE_STRIDE(NP, D)     (14 * (int64_t)(NP) + (int64_t)(NP) * (D))
+#define MBX_MADDE_ST_POP(NP, D)          ((int64_t)0)
+#define MBX_MADDE_ST_COST(NP, D)         (2 * (int64_t)(NP) * (D))
+#define MBX_MADDE_ST_ARC(NP, D)          (MBX_MADDE_ST_COST(NP, D) + (NP))
+#define MBX_MADDE_ST_MF(NP, D)           (MBX_MADDE_ST_ARC(NP, D) + MBX_MADDE_ARC(NP) * (D))
+#define MBX_MADDE_ST_MCR(NP, D)          (MBX_MADDE_ST_MF(NP, D) + MBX_MADDE_H(D))
+#define MBX_MADDE_ST_U(NP, D)            (MBX_MADDE_ST_MCR(NP, D) + MBX_MADDE_H(D))
+#define MBX_MADDE_ST_NCOST(NP, D)        (MBX_MADDE_ST_U(NP, D) + (int64_t)(NP) * (D))
+#define MBX_MADDE_ST_F(NP, D)            (MBX_MADDE_ST_NCOST(NP, D) + (NP))
+#define MBX_MADDE_ST_CR(NP, D)           (MBX_MADDE_ST_F(NP, D) + (NP))
+#define MBX_MADDE_ST_Z(NP, D)            (MBX_MADDE_ST_CR(NP, D) + (NP))
+#define MBX_MADDE_ST_C(NP, D)            (MBX_MADDE_ST_Z(NP, D) + (NP))
+#define MBX_MADDE_ST_PM(NP, D)           (MBX_MADDE_ST_C(NP, D) + (NP))
+#define MBX_MADDE_ST_SCALARS(NP, D)      (MBX_MADDE_ST_PM(NP, D) + 4)
+#define MBX_MADDE_STATE_DOUBLES(NP, D, NLOG) (MBX_MADDE_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)
+#define MBX_SC_MD_NP       10
+#define MBX_SC_MD_ARC      11
+#define MBX_SC_MD_NA       12
+#define MBX_SC_MD_K        13
+#define MBX_SC_MD_LIVE     14
+#define MBX_SITE_MD_PAR      30u
+#define MBX_SITE_MD_NORM     31u
+#define MBX_SITE_MD_CAUCHY   32u
+#define MBX_SITE_MD_IDX      33u
+#define MBX_SITE_MD_CROSS    34u
+#define MBX_SITE_MD_ARC      35u
+#define MBX_SITE_MD_NOISE_A  36u
+#define MBX_SITE_MD_NOISE_B  37u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

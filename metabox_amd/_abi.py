@@ -60,6 +60,7 @@ class GleetActor(C.Structure):
 ALGO_RLEPSO, ALGO_LDE, ALGO_DEDDQN, ALGO_RANDOM_SEARCH, ALGO_RLPSO, ALGO_GLEET, ALGO_QLPSO, ALGO_DE, ALGO_PSO, ALGO_CMAES = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 ALGO_GLPSO = 11
 ALGO_JDE21 = 13      # (12 is not assigned)
+ALGO_MADDE = 15      # (14 is not assigned)
 POLICY_RLEPSO, POLICY_RLPSO = 0, 1
 _ARRAY_FIELDS = ('dshift', 'm1', 'm2', 'v0', 'v1', 'v2', 'py', 'pc', 'pw')
 

@@ -34,6 +34,7 @@
 #include "mbx_classic.hpp"
 #include "mbx_glpso.hpp"
 #include "mbx_jde21.hpp"
+#include "mbx_madde.hpp"
 // k_rlepso_run / k_lde_run are compiled in translation units of their own (mbx_run_rlepso.hip, mbx_run_lde.hip) and only declared here;
 // -DMBX_SINGLE_TU (instrumented builds: the phase counters are a __device__ array, one copy per translation unit) instantiates them in this file instead
 #ifndef MBX_SINGLE_TU
@@ -172,6 +173,12 @@ static AlgoGeom geom_of(const mbx_algo_cfg& c)
         g.sc_off = MBX_JDE21_ST_SCALARS(c.np, c.dim);
         g.tape_stride = MBX_JDE21_TAPE_STRIDE(c.np, c.dim);
         g.lds_doubles = jd_lds_doubles(c.np, c.dim);
+        g.state_dim = 1; g.action_dim = 0;
+    } else if (c.algo == MBX_ALGO_MADDE) {
+        g.state_doubles = MBX_MADDE_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
+        g.sc_off = MBX_MADDE_ST_SCALARS(c.np, c.dim);
+        g.tape_stride = MBX_MADDE_TAPE_STRIDE(c.np, c.dim);
+        g.lds_doubles = md_lds_doubles(c.np, c.dim);
         g.state_dim = 1; g.action_dim = 0;
     }
     return g;
@@ -463,11 +470,15 @@ extern "C" int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, dou
 static int check_cfg(const mbx_algo_cfg* c)
 {
     if (!c) return fail(MBX_E_ARG, "null cfg");
-    // the ids this build has kernels for (12 is not assigned)
-    if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21))
+    // the ids this build has kernels for (12 and 14 are not assigned)
+    if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21 || c->algo == MBX_ALGO_MADDE))
         return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
     if (c->algo == MBX_ALGO_JDE21 && c->np != MBX_JDE21_NP) return fail(MBX_E_ARG, "JDE21 runs np = %d (160 + 10 rows), not %d", MBX_JDE21_NP, c->np);
-    if (c->np < 4 || c->np > kThreads) return fail(MBX_E_ARG, "np %d outside [4, %d]", c->np, kThreads);
+    if (c->algo == MBX_ALGO_MADDE) {
+        // the one algorithm whose rows are strided over the lanes: np is 2 dim^2, and LDS is sized for at most 3200 rows
+        if (c->dim < 2 || c->dim > MBX_MADDE_DIM_MAX) return fail(MBX_E_ARG, "MadDE runs dim in [2, %d], not %d", MBX_MADDE_DIM_MAX, c->dim);
+        if (c->np != MBX_MADDE_NP(c->dim)) return fail(MBX_E_ARG, "MadDE runs np = 2 dim^2 = %d, not %d", MBX_MADDE_NP(c->dim), c->np);
+    } else if (c->np < 4 || c->np > kThreads) return fail(MBX_E_ARG, "np %d outside [4, %d]", c->np, kThreads);
     if (c->dim < 2 || c->dim > 64) return fail(MBX_E_ARG, "dim %d outside [2, 64]", c->dim);
     if (c->algo == MBX_ALGO_RLEPSO && (c->n_group < 1 || c->n_group > 16 || c->np / c->n_group < 1))
         return fail(MBX_E_ARG, "bad n_group %d", c->n_group);
@@ -674,6 +685,9 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
         HIP_TRY(hipFuncSetAttribute((const void*)k_jde21_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_jde21_generation<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_jde21_generation<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    } else if (cfg->algo == MBX_ALGO_MADDE) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_madde_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_madde_generation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     } else if (cfg->algo == MBX_ALGO_QLPSO) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -786,6 +800,8 @@ extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
         hipLaunchKernelGGL(k_glpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_JDE21)
         hipLaunchKernelGGL(k_jde21_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
+    else if (b->cfg.algo == MBX_ALGO_MADDE)
+        hipLaunchKernelGGL(k_madde_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_GLEET)
@@ -811,7 +827,8 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
                         void* stream)
 {
     const bool no_agent = b && (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH || b->cfg.algo == MBX_ALGO_DE || b->cfg.algo == MBX_ALGO_PSO ||
-                                b->cfg.algo == MBX_ALGO_CMAES || b->cfg.algo == MBX_ALGO_GLPSO || b->cfg.algo == MBX_ALGO_JDE21);
+                                b->cfg.algo == MBX_ALGO_CMAES || b->cfg.algo == MBX_ALGO_GLPSO || b->cfg.algo == MBX_ALGO_JDE21 ||
+                                b->cfg.algo == MBX_ALGO_MADDE);
     if (!b || (!d_actions && !no_agent)) return fail(MBX_E_ARG, "mbx_step: bad arguments");
     if (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH)
         hipLaunchKernelGGL(k_rs_population, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), 0, d_state_out,
@@ -835,6 +852,9 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
                            d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_JDE21)
         hipLaunchKernelGGL(k_jde21_generation<2>, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
+                           d_reward_out, d_done_out);
+    else if (b->cfg.algo == MBX_ALGO_MADDE)
+        hipLaunchKernelGGL(k_madde_generation, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
                            d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_step<false>, dim3(b->B), dim3(kThreads), (size_t)ql_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double),

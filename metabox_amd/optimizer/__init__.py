@@ -10,3 +10,4 @@ from .qlpso_optimizer import QLPSO_Optimizer
 from .classic import DEAP_CMAES, DEAP_DE, DEAP_PSO
 from .gl_pso import GL_PSO
 from .jde21 import JDE21
+from .madde import MadDE

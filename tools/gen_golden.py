@@ -1498,7 +1498,196 @@ def gen_jde21():
     np.savez_compressed(os.path.join(OUT, 'jde21_traces.npz'), **data)
 
 
-SECTIONS = {'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+def run_madde_episode(problem, config, opt=None, fcr=False):
+    """One reference MadDE episode on the global numpy stream (the caller seeds it).  Row 0 of every per-update array is the state after
+    __init_population, row g the state after __update number g.  `ncost` is ragged and stored flattened: the costs of the initial rows in
+    draw order, then the NP trial costs of every update as the reference computed them (one double per FE).  `pm0` is the strategy
+    probabilities the episode started with (they live on the object).  `tie` says whether any vector handed to np.argsort during the
+    step held two equal values.  Full snapshots (population, costs, archive, MF, MCr) after the reset where they are small, at four
+    updates spread over the episode where population + archive stay below SNAP_DOUBLES, and at the end."""
+    from optimizer import MadDE
+    import copy
+    SNAP_DOUBLES = 8000
+    opt = opt if opt is not None else MadDE(copy.deepcopy(config))
+    problem.reset()
+    get = lambda name: getattr(opt, '_MadDE__' + name)          # noqa: E731
+    rec = dict(gbest=[], fes=[], np=[], narc=[], na=[], k=[], pm=[], mem=[], n_opt=[], n_over=[], cmin=[], csum=[], tie=[])
+    ncost, snaps, seen, fcrs = [], {}, {'tie': 0}, []
+    pm0 = np.array(get('pm'), dtype=np.float64)
+    orig_eval, orig_arc, orig_fcr, orig_argsort = problem.eval, get('update_archive'), get('choose_F_Cr'), np.argsort
+
+    def ev(x):
+        y = orig_eval(x)
+        seen['eval'] = np.array(y, dtype=np.float64) - (0. if problem.optimum is None else problem.optimum)
+        return y
+
+    def upd(i):
+        seen['n_opt'] += 1
+        seen['n_over'] += int(get('archive').shape[0] >= get('NA'))
+        return orig_arc(i)
+
+    def choose():
+        cr, f = orig_fcr()
+        if fcr:
+            fcrs.append(np.stack([f, cr]))
+        return cr, f
+
+    def argsort(a, *args, **kw):
+        a = np.asarray(a)
+        if len(np.unique(a)) < a.size:
+            seen['tie'] = 1
+        return orig_argsort(a, *args, **kw)
+    problem.eval = ev
+    setattr(opt, '_MadDE__update_archive', upd)
+    setattr(opt, '_MadDE__choose_F_Cr', choose)
+    np.argsort = argsort
+
+    def state():
+        arc = np.array(get('archive'), dtype=np.float64).reshape(-1, config.dim)
+        return (np.array(get('population'), dtype=np.float64), np.array(get('cost'), dtype=np.float64), arc,
+                np.array(get('MF'), dtype=np.float64), np.array(get('MCr'), dtype=np.float64))
+
+    def snap(k_before):
+        cost = np.array(get('cost'), dtype=np.float64)
+        rec['gbest'].append(float(opt.gbest)); rec['fes'].append(float(get('FEs'))); rec['np'].append(int(get('NP')))
+        rec['narc'].append(int(np.array(get('archive')).reshape(-1, config.dim).shape[0])); rec['na'].append(int(get('NA'))); rec['k'].append(int(get('k')))
+        rec['pm'].append(np.array(get('pm'), dtype=np.float64))
+        rec['mem'].append(np.array([get('MF')[k_before], get('MCr')[k_before]], dtype=np.float64))
+        rec['n_opt'].append(seen.get('n_opt', 0)); rec['n_over'].append(seen.get('n_over', 0))
+        rec['cmin'].append(float(cost.min())); rec['csum'].append(float(np.sum(cost))); rec['tie'].append(seen['tie'])
+        ncost.append(seen['eval'])
+    try:
+        getattr(opt, '_MadDE__init_population')(problem)
+        snap(0)
+        if get('NP') * config.dim <= SNAP_DOUBLES:
+            snaps[0] = state()
+        done = False
+        while not done and get('FEs') < config.maxFEs:
+            seen.update(tie=0, n_opt=0, n_over=0)
+            k_before = int(get('k'))
+            done = getattr(opt, '_MadDE__update')(problem)
+            snap(k_before)
+            g = len(rec['gbest']) - 1
+            if g % 29 == 0 and (get('NP') + rec['narc'][-1]) * config.dim <= SNAP_DOUBLES and len(snaps) < 5:
+                snaps[g] = state()
+    finally:
+        problem.eval = orig_eval
+        np.argsort = orig_argsort
+        delattr(opt, '_MadDE__update_archive'); delattr(opt, '_MadDE__choose_F_Cr')
+    # what run_episode does after its loop (:280-283)
+    if len(opt.cost) >= config.n_logpoint + 1:
+        opt.cost[-1] = opt.gbest
+    else:
+        opt.cost.append(opt.gbest)
+    snaps[len(rec['gbest']) - 1] = state()
+    out = {k: np.array(v, dtype=np.float64 if k in ('gbest', 'fes', 'pm', 'mem', 'cmin', 'csum') else np.int32) for k, v in rec.items()}
+    out['ncost'] = np.concatenate(ncost)
+    out['pm0'] = pm0
+    out['snap_gens'] = np.array(sorted(snaps), dtype=np.int32)
+    for g in sorted(snaps):
+        for name, a in zip(('pop', 'cost', 'arc', 'MF', 'MCr'), snaps[g]):
+            out[f'snap{g}/{name}'] = a
+    out['cost'] = np.array(opt.cost, dtype=np.float64)
+    if fcr:
+        out['fcr'] = np.concatenate(fcrs, axis=1)
+    return out, opt
+
+
+def gen_madde():
+    """MadDE (src/optimizer/madde.py): seeded reference episodes, recorded per update (run_madde_episode).  The numpy draws are NOT stored:
+    the tests regenerate them from the seed in the reference's draw order.  `max_fes` is reduced where a whole episode would make the
+    fixture large.  Every case must be free of equal values in every vector it sorts (the reference's argsort is not reproducible among
+    equal keys): the generator fails loudly otherwise, pick another seed then.  F and Cr of every update are recorded for the two shortest
+    cases, so that a difference in scipy's Cauchy quantile on another machine shows up in a CPU test.
+    Every branch the tests' quirk list names is reached by some case (tests/test_madde.py::test_fixture_covers_the_quirks asserts it, updates
+    in which no row improved and improved rows that draw the same archive row included); crafted states add the extremes: every row
+    improved, the archive exactly full / one short / empty, NP = 4 in every group shape, equal costs.
+    `finals/<suite>/<dim>/<fid>`: final gbest and fes of 51 episodes (seeds 1..51, full budget), each on a fresh optimizer object.
+    The arrays are spread over madde_traces.npz, madde_traces_b.npz, ... so that no file exceeds 1 MiB; the tests read them all."""
+    scratch = tempfile.mkdtemp()
+    data, cases, owner = {}, [], {}
+
+    def put(key, rec, max_fes, first=None):
+        cases.append(key)
+        assert not rec['tie'].any() and (first is None or not first['tie'].any()), (key, 'sorts equal values: pick another seed')
+        for k, v in rec.items():
+            data[f'{key}/{k}'] = v
+        for k, v in (first or {}).items():
+            data[f'{key}/first/{k}'] = v
+        data[f'{key}/max_fes'] = np.float64(max_fes)
+        data[f'{key}/next_rand'] = np.float64(np.random.rand())      # stream position after the episode(s)
+        print(key, len(rec['gbest']) - 1, rec['fes'][-1], rec['gbest'][-1], int(rec['np'][-1]), rec['pm'][-1], int(rec['n_over'].sum()), len(rec['cost']))
+
+    def config_for(suite, dim, max_fes):
+        argv = ['--problem', suite] + ([] if suite == 'protein' else ['--dim', str(dim)])
+        config = ref_import.ref_config(argv, scratch)
+        config.maxFEs = max_fes
+        config.log_interval = max_fes // config.n_logpoint
+        return config
+    jobs = [('bbob', 10, 1, 61, 20000), ('bbob', 10, 15, 63, 20000), ('bbob', 10, 22, 64, 8000), ('bbob', 10, 24, 65, 6000), ('bbob', 10, 3, 71, 6000),
+            ('bbob', 10, 7, 62, 6000), ('bbob-noisy', 10, 101, 66, 20000), ('bbob-noisy', 10, 102, 72, 6000), ('bbob-noisy', 10, 103, 73, 6000),
+            ('bbob', 30, 10, 69, 20000)]
+    problems = {}
+    for suite, dim, fid, seed, max_fes in jobs:
+        if (suite, dim) not in problems:
+            tr, te, _ = all_problems(suite, dim)
+            problems[(suite, dim)] = {fid_of(p): p for p in tr + te}
+        config = config_for(suite, dim, max_fes)
+        np.random.seed(seed)
+        rec, _ = run_madde_episode(problems[(suite, dim)][fid], config)
+        put(f'{suite}/{dim}/{fid}/{seed}', rec, max_fes)
+    byid, _, _ = protein_problems()
+    config = config_for('protein', 12, 1000)
+    np.random.seed(70)
+    rec, _ = run_madde_episode(byid['1ATN_7'], config, fcr=True)
+    put('protein/12/1ATN_7/70', rec, 1000)
+    # two episodes on one optimizer object: pm carries over (F15 ends with pm != 1/3); F and Cr of every update recorded
+    config = config_for('bbob', 10, 3000)
+    for seed in range(74, 94):                                       # the first seed whose first episode ends with pm != 1/3
+        np.random.seed(seed)
+        first, opt = run_madde_episode(problems[('bbob', 10)][15], config, fcr=True)
+        if not np.allclose(first['pm'][-1], 1 / 3):
+            break
+    else:
+        raise AssertionError('no first episode ends with pm != 1/3')
+    second, _ = run_madde_episode(problems[('bbob', 10)][3], config, opt, fcr=True)
+    put(f'second/10/15-3/{seed}', second, 3000, first)
+    data['cases'] = np.array(cases)
+    # final results of free-running episodes, a fresh object each
+    for suite, fid in (('bbob', 1), ('bbob', 15), ('bbob', 24), ('bbob-noisy', 101)):
+        from optimizer import MadDE
+        import copy
+        config = config_for(suite, 10, 20000)
+        fin = []
+        for seed in range(1, 52):
+            np.random.seed(seed)
+            p = problems[(suite, 10)][fid]
+            p.reset()
+            r = MadDE(copy.deepcopy(config)).run_episode(p)
+            fin.append((r['cost'][-1], r['fes']))
+        data[f'finals/{suite}/10/{fid}'] = np.array(fin, dtype=np.float64)
+        print('finals', suite, fid, np.median(np.array(fin), 0))
+    # several files, none above 1 MiB (the trial costs do not compress): whole cases to the first file that has room
+    parts, sizes = [], []
+    for key in data:
+        prefix = '/'.join(key.split('/')[:4])
+        if prefix not in owner:
+            need = sum(data[k].nbytes for k in data if '/'.join(k.split('/')[:4]) == prefix)
+            for n in range(len(parts) + 1):
+                if n == len(parts):
+                    parts.append({}); sizes.append(0)
+                if sizes[n] + need <= 800 * 1024:
+                    break
+            owner[prefix] = n
+            sizes[n] += need
+        parts[owner[prefix]][key] = data[key]
+    for n, d in enumerate(parts):
+        path = os.path.join(OUT, 'madde_traces%s.npz' % ('' if n == 0 else '_' + 'abcdefgh'[n]))
+        np.savez_compressed(path, **d)
+        print(os.path.basename(path), os.path.getsize(path))
+        assert os.path.getsize(path) < 1024 * 1024
+
+SECTIONS = {'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

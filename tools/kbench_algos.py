@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -190,5 +190,26 @@ if 'jde21' in which:
                 for _ in range(n): b.step(None)
             run(3); dt = timed(run, 40)
             print(json.dumps({'path': f'{name} bbob d={dim} NP={np_}, {B} instances, one launch per generation', 'us_per_step': dt / 40 * 1e6,
+                              'launch_info': b.launch_info()}))
+            b.close()
+if 'madde' in which:
+    # MadDE (one mbx_step = one update: NP trials, NP = 2 D^2 at the start) next to Random_search's 100-row kernel in the same process: bbob
+    # round-robin, 4096 instances at D = 10 and 256 at D = 30 (2.3 MB of state each), a budget so large that NP stays at its start
+    # value and every instance stays live.  Under rocprofv3 --kernel-trace --stats the per-launch times of k_madde_generation and
+    # k_rs_population come from the trace; the wall times here include the launch gaps.  A library built with -DMBX_ABLATE_MD_SORT /
+    # -DMBX_ABLATE_MD_ARC / -DMBX_ABLATE_MD_SUMS (MBX_LIB) gives the step without the sort and row move / the archive update / the pairwise sums.
+    from metabox_amd._abi import ALGO_MADDE, ALGO_RANDOM_SEARCH
+    from metabox_amd.suite import Batch, Suite
+    for dim, B in ((10, 4096), (30, 256)):
+        cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+        tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+        s = Suite(ps)
+        for algo, name, np_ in ((ALGO_MADDE, 'k_madde_generation', 2 * dim * dim), (ALGO_RANDOM_SEARCH, 'k_rs_population', 100)):
+            b = Batch(s, algo, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, np_, 10 ** 9, 10 ** 7, 50, early_stop=False)
+            b.reset()
+            def run(n):
+                for _ in range(n): b.step(None)
+            run(2); dt = timed(run, 10)
+            print(json.dumps({'path': f'{name} bbob d={dim} NP={np_}, {B} instances, one launch per update', 'us_per_step': dt / 10 * 1e6,
                               'launch_info': b.launch_info()}))
             b.close()
