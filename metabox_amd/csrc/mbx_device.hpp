@@ -115,6 +115,9 @@ struct Rng {                      // per-instance stream: key = seed, counter = 
 #ifdef MBX_ABLATE_RNG
         return U4{idx * 2654435761u, site + 0x9E3779B9u * idx, gen ^ (idx << 7), episode + idx};   // timing experiments only
 #else
+#ifdef MBX_ABLATE_RNG_SITES                                                                       // the same for the draw sites of a bit mask (1 << site; sites below 32)
+        if (site < 32u && ((MBX_ABLATE_RNG_SITES) >> site & 1u)) return U4{idx * 2654435761u, site + 0x9E3779B9u * idx, gen ^ (idx << 7), episode + idx};
+#endif
         uint32_t a = k0, b = k1;
         if (uniform_fresh) {
             // (readfirstlane: a no-op when the key already sits in SGPRs; instrumented builds load it with vector loads)

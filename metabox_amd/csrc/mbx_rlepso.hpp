@@ -299,6 +299,22 @@ __device__ __forceinline__ float fdr_min3_abs(float m, float x, float y)
     asm("v_min3_f32 %[r], %[m], |%[x]|, |%[y]|" : [r] "=v"(r) : [m] "v"(m), [x] "v"(x), [y] "v"(y));
     return r;
 }
+// compile-time loop: f(IntC<K>{}) for K = FROM .. TO - 1 (the body sees K as a constant expression, e.g. for an instruction's immediate operand)
+template <int K> struct IntC { static constexpr int value = K; };
+template <int FROM, int TO, class F>
+__device__ __forceinline__ void static_for(F&& f)
+{
+    if constexpr (FROM < TO) { f(IntC<FROM>{}); static_for<FROM + 1, TO>(f); }
+}
+// old with lane LANE replaced by the wave-uniform value val (v_writelane_b32 with the lane as an immediate)
+template <int LANE>
+__device__ __forceinline__ int writelane_const(int val, int old)
+{
+    static_assert(LANE >= 0 && LANE < 64, "a lane of a wave");
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(old) : "s"(val), "n"(LANE));
+    return old;
+}
+
 // Rows of the rank-ordered pbest table that are bitwise copies of the row one rank up -- same cost, same position: particles resting on the same corner of the box (linear
 // slope: most of the swarm, for dozens of generations) -- can never be np.argmin's choice (the copy with the lower index precedes them in rank order and ties with them in
 // every coordinate), but in the scan each of them is an exact tie with the running best: every item above them would be flagged.  The scan therefore reads their cost as 1e300
@@ -400,6 +416,9 @@ __device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0,
 #pragma unroll
     for (int q = 0; q < W; ++q) kb[q] = nless;                   // rank of the exemplar when nobody is strictly better
     if (nless <= 0) return false;
+#ifdef MBX_ABLATE_FDR_SCAN
+    nless = 1;                                                    // instruction-budget builds: the head and the tail of the scan without its loops
+#endif
     const double fi = L.NC[rk];
     double pp[W], ab[W], bb[W];
     const double a0 = L.NC[0] - fi;
@@ -1019,10 +1038,12 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
     const double lb = P.lb, ub = P.ub, vmax = 0.1 * (ub - lb);
     double gbest = sc[MBX_SC_GBEST];
     int gbest_idx = (int)sc[MBX_SC_GBEST_IDX];
-    double fes = sc[MBX_SC_FES];
-    int log_index = (int)sc[MBX_SC_LOG_INDEX], cost_len = (int)sc[MBX_SC_COST_LEN];
+    // fes, the curve's counters and the return are exact integers (fes <= maxFEs + 2 NP) and the same in every lane: they are carried on the scalar unit
+    // (integer adds and compares there instead of float64 ones in all four waves) and become float64 again only where a value is stored
+    int fes = __builtin_amdgcn_readfirstlane((int)sc[MBX_SC_FES]);
+    int log_index = __builtin_amdgcn_readfirstlane((int)sc[MBX_SC_LOG_INDEX]), cost_len = __builtin_amdgcn_readfirstlane((int)sc[MBX_SC_COST_LEN]);
     double* cost = sc + MBX_NSCALAR;
-    double ret = 0.;
+    int ret = 0;
     int n_reinit = 0;
 
     // ---- load the state block once: positions -> X (LDS), velocities / pbest positions -> registers of the element's owner
@@ -1055,6 +1076,8 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
     int* RANK = L.RANK;
     float* ACT = (float*)L.R1;    // sampled action; R1 is not written before the ranking barrier
     int* EQC = (int*)(L.RED + 14);  // equal-cost flag of the ranking (block_argmin uses RED[0..1] only)
+    int* RCNT = (int*)(L.RED + 2);  // re-initialisation count of each wave that holds particles (RED[2..9]: up to 16 waves)
+    constexpr int PW = (NP + 63) / 64;      // waves that hold particles
 
     // pbest / gbest bookkeeping of update() and __reinit() (rl_commit with c_cost and the pbest positions in registers)
     auto commit = [&](bool stagnation, int tid) {
@@ -1076,7 +1099,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
             if (it < NI && L.IMPR[fh.div(it)]) { const double2 x2 = *(const double2*)(L.X + 2 * it); pbp[j][0] = x2.x; pbp[j][1] = x2.y; }
         }
         if (better && tid < D) L.GB[tid] = L.X[cb * D + tid];
-        __syncthreads();
+        if (!stagnation) __syncthreads();                // update()'s commit is followed by the barrier of the re-initialisation count, with nothing shared in between
     };
 
     bool done = false;
@@ -1092,14 +1115,18 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         const double pre_gbest = gbest;
         // ---- agent.act: the action of this generation from row fes of the actor table (same draws as mbx_gauss_policy)
         if (tid < A) {
-            int row = (int)fes;
+            int row = fes;
             row = row < ar().table_rows ? row : ar().table_rows - 1;
             const float* ms = ar().policy_table + (int64_t)row * 2 * A;
+#ifndef MBX_ABLATE_POLICY
             const float a = sample_action(rng, tid, ms[tid], ms[A + tid], MBX_POLICY_RLEPSO);
+#else
+            const float a = ms[tid];
+#endif
             ACT[tid] = a;
             if (ar().out.traj_actions) ar().out.traj_actions[((int64_t)g * B + b) * A + tid] = a;
         }
-        if (tid < NP) { NLESS[tid] = 0; ORDER[tid] = tid; }
+        if (tid < NP) ORDER[tid] = tid;
         if (tid == 0) { *EQC = 0; *L.FLN = 0; }
         __syncthreads();
         if (tid < G) {                                            // __get_coe (:112-132), float32 like k_rlepso_step
@@ -1121,21 +1148,28 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         // (ORDER[rank] != i), raises the workgroup's equal-cost flag, and the workgroup -- uniformly -- redoes the per-particle step with the index
         // tie-break and restages the rows.  Same ranks as k_rlepso_step in every case; the slow path only runs for instances that really hold
         // equal costs (collapsed swarms on F5 / F7 plateaus).
+        // The count itself is done ACROSS the lanes: lane l of every wave holds the costs of particles l and l + 64; for each particle i of the wave's share (NP / waves,
+        // rounded up) its cost is read once for all lanes (same address: an LDS broadcast), two compares answer all NP pairs, the scalar unit counts the bits of the two
+        // masks, and the count is parked in lane k of a result register (v_writelane): 3 vector instructions per particle (the per-lane count it replaced: a compare and
+        // an add-with-carry per PAIR, then an atomic), -48 % of the ranking's instructions.  A NaN cost compares false both ways, as in k_rlepso_step.
         {
-            constexpr int parts = THREADS / NP > 0 ? THREADS / NP : 1;
-            for (int w = tid; w < parts * NP; w += THREADS) {
-                const int part = w / NP, i = w - part * NP;
-                const int j0 = part * NP / parts, j1 = (part + 1) * NP / parts;
-                const double fi = L.PBC[i];
-                int nless = 0;
+            static_assert(NP <= 128, "k_rlepso_run: the ranking holds two costs per lane");
+            constexpr int WAVES = THREADS / 64, PER = (NP + WAVES - 1) / WAVES;
+            const int lane = tid & 63, i0 = (tid >> 6) * PER;
+            const double flo = NP >= 64 || lane < NP ? L.PBC[NP >= 64 || lane < NP ? lane : 0] : INFINITY;
+            const double fhi = lane + 64 < NP ? L.PBC[lane + 64 < NP ? lane + 64 : 0] : INFINITY;
+            int res = 0;
 #ifndef MBX_ABLATE_RANK
-#pragma unroll 5
-                for (int j = j0; j < j1; ++j) nless += L.PBC[j] < fi;
+            static_for<0, PER>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                const double fi = L.PBC[PER * WAVES == NP || i0 + k < NP ? i0 + k : NP - 1];      // (address: the wave's base + a constant)
+                const int n = __builtin_popcountll(__builtin_amdgcn_ballot_w64(flo < fi)) + __builtin_popcountll(__builtin_amdgcn_ballot_w64(fhi < fi));
+                res = writelane_const<k>(n, res);
+            });
 #else
-                if (part == 0) nless = i;
+            res = i0 + lane;
 #endif
-                atomicAdd(&NLESS[i], nless);
-            }
+            if (lane < PER && i0 + lane < NP) NLESS[i0 + lane] = res;
         }
         __syncthreads();
         if (tid < NP) {
@@ -1157,6 +1191,9 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
                 if (it < NI) { const int i = fh.div(it), d0 = 2 * (it - i * HD); *(double2*)(L.PB + RANK[i] * D + d0) = double2{pbp[j][0], pbp[j][1]}; }
             }
         };
+#ifdef MBX_ABLATE_STAGE
+        if (g == 0)
+#endif
         stage_pbest(tid);
         __syncthreads();
         if (*EQC) {                                               // workgroup-uniform: equal pbest costs exist, order them by index
@@ -1194,7 +1231,11 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
                     const int i = fh.div(it);
                     const double2 c2 = *(const double2*)(L.X + 2 * it);
                     double cur[2] = {c2.x, c2.y};
+#ifndef MBX_ABLATE_MOVE
                     rl_move<2, true>(mc, i, 2 * (it - i * HD), cur, vel[j]);
+#else
+                    (void)i; (void)cur;
+#endif
                 }
             }
         }
@@ -1202,16 +1243,30 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         // ---- evaluate, update pbest / gbest and the stagnation counters (:198-233)
         population_costs<eval_dc(DC), eval_md(DC), ConstProblem, rl_run_matvec_chunk(DC), KIND, NOISE>(P, L.eval(), NP, rng, nullptr, MBX_SITE_NOISE0_A, MBX_SITE_NOISE0_B);
         fes += NP;
+#ifndef MBX_ABLATE_COMMIT
         commit(true, tid);
+#endif
         // ---- re-initialisation (:238-239, 134-168)
+        // the count: every wave that holds particles counts its lanes' flags on the scalar unit and publishes the sum; ONE barrier (which is also the one that ends
+        // update()'s commit) where __syncthreads_count spends three, a block-size look-up and a cross-lane add in all four waves
         int mine = 0;
         if (tid < NP) {
+#ifndef MBX_ABLATE_REINIT_DRAW
             const U4 w = rng.draw((uint32_t)tid, MBX_SITE_REINIT);
             const double u = u53(w.x, w.y);
             mine = u < L.CMUT[tid] * 0.01 * L.PNI[tid];
+#endif
             L.MASK[tid] = mine;
         }
-        n_reinit = __syncthreads_count(mine);
+        {
+            const int cnt = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine != 0));
+            if ((tid & 63) == 0 && tid < 64 * PW) RCNT[tid >> 6] = cnt;
+            __syncthreads();
+            int n = 0;
+#pragma unroll
+            for (int w = 0; w < PW; ++w) n += RCNT[w];
+            n_reinit = __builtin_amdgcn_readfirstlane(n);
+        }
         if (n_reinit > 0) {
 #pragma unroll
             for (int j = 0; j < IT; ++j) {
@@ -1232,21 +1287,24 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
             fes += n_reinit;
             commit(false, tid);
         }
-        // ---- logging, termination, reward (:241-261); every thread keeps the (block-uniform) counters, thread 0 writes the curve
-        if (fes >= (double)log_index * ar().bp.log_interval) { log_index += 1; if (tid == 0) cost[cost_len] = gbest; cost_len += 1; }
+        // ---- logging, termination, reward (:241-261): the counters are scalars (see above), the two float64 compares on gbest are made wave-uniform by a ballot;
+        // thread 0 writes the curve.  (fes and the log point are integers below 2^31 and 2^62: the integer compare is the reference's float64 one)
+#ifndef MBX_ABLATE_LOG
+        if ((int64_t)fes >= (int64_t)log_index * ar().bp.log_interval) { log_index += 1; if (tid == 0) cost[cost_len] = gbest; cost_len += 1; }
         done = fes >= ar().bp.max_fes;
-        if (!isnan(P.optimum) && ar().bp.early_stop) done = done || gbest <= 1e-8;
+        if (!isnan(P.optimum) && ar().bp.early_stop) done = done || __builtin_amdgcn_ballot_w64(gbest <= 1e-8) != 0ull;
         if (done) {
             if (cost_len >= ar().bp.n_logpoint + 1) { if (tid == 0) cost[cost_len - 1] = gbest; }
             else { if (tid == 0) cost[cost_len] = gbest; cost_len += 1; }
         }
-        const double reward = gbest < pre_gbest ? 1. : -1.;
-        ret += reward;
+        const bool improved = __builtin_amdgcn_ballot_w64(gbest < pre_gbest) != 0ull;
+        ret += improved ? 1 : -1;
         if (tid == 0) {
-            if (ar().out.traj_state) ar().out.traj_state[g * B + b] = fes / ar().bp.max_fes;
-            if (ar().out.traj_reward) ar().out.traj_reward[g * B + b] = reward;
+            if (ar().out.traj_state) ar().out.traj_state[g * B + b] = (double)fes / ar().bp.max_fes;
+            if (ar().out.traj_reward) ar().out.traj_reward[g * B + b] = improved ? 1. : -1.;
             if (ar().out.traj_done) ar().out.traj_done[g * B + b] = done ? 1 : 0;
         }
+#endif
     }
     // ---- store the state block once
 #pragma unroll
@@ -1264,7 +1322,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         S[MBX_RLEPSO_ST_CCOST(NP, D) + tid] = cc;
     }
     if (tid < D) S[MBX_RLEPSO_ST_GBPOS(NP, D) + tid] = L.GB[tid];
-    const double st = fes / ar().bp.max_fes;
+    const double st = (double)fes / ar().bp.max_fes;
     for (int t = g + tid; t < n_gens; t += THREADS) {            // generations after the instance finished
         if (ar().out.traj_state) ar().out.traj_state[t * B + b] = st;
         if (ar().out.traj_reward) ar().out.traj_reward[t * B + b] = 0.;
