@@ -109,6 +109,7 @@ int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, double* d_f,
 #define MBX_ALGO_GLPSO  11  /* src/optimizer/gl_pso.py             one step = one generation (2 NP FEs) -- classic baseline, no agent */
 #define MBX_ALGO_JDE21  13  /* src/optimizer/jde21.py              one step = one update (2 bNP FEs), np = 170 -- classic baseline, no agent (12 is not assigned) */
 #define MBX_ALGO_MADDE  15  /* src/optimizer/madde.py              one step = one update (NP FEs), np = 2 dim^2, dim <= 40 -- classic baseline, no agent (12 and 14 are not assigned and stay rejected) */
+#define MBX_ALGO_DEDQN  16  /* src/optimizer/dedqn_optimizer.py     one step = one trial vector + the landscape analysis (2 NP FEs), np in [4, 128], dim <= 40 */
 
 typedef struct mbx_algo_cfg {
     int32_t algo;          /* MBX_ALGO_*                                                          */
@@ -147,7 +148,8 @@ int mbx_batch_flags(const mbx_batch* b);
  *   GLEET         : state [np*27]  (gleet_optimizer.py:111-124),            action [np] float32
  *   QLPSO         : state [1]      (qlpso_optimizer.py:89-90,125),          action [1] int32 in {0..3}
  *   DE, PSO, CMAES: state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
- *   GLPSO, JDE21  : state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step) */
+ *   GLPSO, JDE21  : state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
+ *   DEDQN         : state [4]      (dedqn_optimizer.py:130-142: fdc, rie, acf, nop), action [1] int32 (0 rand_1, 1 cur_to_rand_1, anything else best_2) */
 int mbx_state_dim(const mbx_algo_cfg* cfg);
 int mbx_action_dim(const mbx_algo_cfg* cfg);
 /* number of doubles of external random numbers one instance consumes per step (see mbx_set_tape) */
@@ -354,6 +356,24 @@ int mbx_gleet_policy(mbx_batch* b, const mbx_gleet_actor* net, const double* d_s
  * the tape, so the reference's own decisions are reproduced.  Outputs as mbx_rlpso_rollout; d_actions_out [n_instances] int32. */
 int mbx_qlpso_rollout(mbx_batch* b, const double* d_q_table, int n_steps, int32_t* d_actions_out, double* d_state_out,
                       double* d_reward_out, uint8_t* d_done_out, void* stream);
+
+/* DEDQN with its Q-network inside the step kernel, `n_steps` env steps per launch: the loop of DEDQN_Agent.rollout_episode
+ * (src/agent/dedqn_agent.py:89-98) with the greedy __get_action (:44-53: Q = MLP(float32(state)), argmax) evaluated in the workgroup, while the
+ * population, the costs, the survival counters and the features stay in LDS from step to step.  Every step does exactly what mbx_step does with
+ * that action, with the same Philox counters: n_steps one-step calls, one n_steps call, and mbx_step fed the recorded actions leave bit-identical
+ * state blocks, states, rewards and cost curves.  d_weights (float32, 193 values), packed as mbx_qnet documents: per layer of the torch module
+ * the weight TRANSPOSED, Wt [in][out] row-major, then the bias -- W1t [4][10] | b1 [10] | W2t [10][10] | b2 [10] | W3t [10][3] | b3 [3]; one
+ * float32 fma chain per unit, k ascending, starting at the bias.  Only the reference's architecture (in 4, hidden 10, n_act 3) is built.
+ * Per-step records, each may be NULL (rows of steps after an instance's termination are not written):
+ *   d_traj_actions [n_steps, n_instances] int32, d_traj_state [n_steps, n_instances, 4] float64 (the state AFTER the step), d_traj_reward [n_steps, n_instances] float64.
+ * d_actions_out [n_instances] int32: the last action taken; d_state_out [n_instances, 4] / d_done_out: state / is_done after the last executed
+ * step; d_reward_out: SUM of the rewards of the executed steps (like mbx_rlpso_rollout).  With a replay tape n_steps must be 1. */
+typedef struct mbx_dedqn_net {
+    const float* d_weights;
+    int32_t in_dim, hidden, n_act;
+} mbx_dedqn_net;
+int mbx_dedqn_rollout(mbx_batch* b, const mbx_dedqn_net* net, int n_steps, int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward,
+                      int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream);
 
 /* Test / diagnostics: apply one of the device math routines the objectives are built from to n device values.
  * op: 0 log, 1 exp, 2 sin, 3 cos, 4 pow(x, y), 5 T_osz(x) (bbob.py:51-67), 6 T_asy(x; beta_lin = y) (bbob.py:70-82). */

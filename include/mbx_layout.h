@@ -507,6 +507,67 @@
 #define MBX_SITE_MD_NOISE_A  36u
 #define MBX_SITE_MD_NOISE_B  37u
 
+/* ---------------------------------------------------------------- 14. DEDQN (dedqn_optimizer.py) layouts
+ * One env step = ONE trial vector of the row `pointer` (round robin over NP = 100; the pointer is NOT reset by init_population, :118), built by
+ * rand_1_single / cur_to_rand_1_single / best_2_single (action 0 / 1 / anything else; F = 0.5), clipped, binomial crossover (Cr = 0.5), one
+ * evaluation, selection `u_cost <= cost[pointer]` -- and then __cal_feature (:130-142): the whole population is evaluated again and its costs
+ * are paired BY INDEX with a random walk of rwsteps = NP points through the population's bounding box.  A step bills 2 NP evaluations
+ * (:178, :141), a reset 2 NP as well (:153).  state [4] = fdc | rie | acf | nop (:8-76); action [1] int32; reward = cal_reward(survival) (:92-100).
+ * state block: pop[NP*D] cost[NP] survival[NP] scost[NP] gbest_pos[D] feat[16] scalars[16] cost_curve[nlog+1].
+ *   scost:     the samples_cost of the last __cal_feature (never written back to cost, :133-135).
+ *   gbest_pos: the best position once it is an array of its own; while MBX_SC_DEDQN_ALIAS is 1 gbest is still the numpy VIEW of row
+ *              MBX_SC_DEDQN_G0 taken by init_population (:151) and follows that row (an equal-cost trial overwrites it, :179-185).
+ *   feat:      the four features, then the diagnostics MBX_DEDQN_FEAT_*: the ruggedness level whose entropy is the maximum (first one) and
+ *              its six transition counts (:36-47, before the zero counts are replaced), the cost of the last trial, and the three Q values
+ *              behind the last action of the in-kernel policy (0 after mbx_step).
+ * tape per reset: pos_u[NP*D] | noise_init[3*NP] | walk_u[NP*D] | noise_feat[3*NP]
+ * tape per step:  r[4] | jrand | noise_trial[3] | cross_u[D] | walk_u[NP*D] | noise_feat[3*NP]
+ *   r: the ACCEPTED row of generate_random_int_single (operators/mutate.py:5-9; 3 columns for actions 0 / 1, 4 otherwise), as doubles;
+ *   walk_u[i*D+d]: the uniform of walk step i, coordinate d (random_walk_sampling :79-89).
+ * Philox, counter (index, site, gen, episode); reset gen = 0, step gen = number of the step:
+ *   MBX_SITE_LDE_ELEM(e)      reset: u53(w0,w1) = pos_u;  step, index d: u53(w0,w1) = cross_u
+ *   MBX_SITE_DD_NOISE_A/B(i)  reset: evaluation of the initial population
+ *   MBX_SITE_DD_R(a)          attempt a = 0, 1, ... of the redraw: mulhi(w0..w3, NP) = r[0..3]; all columns are redrawn while the pointer is
+ *                             among the columns in use (1024 attempts at most, then kept)
+ *   MBX_SITE_DQ_JRAND(0)      mulhi(w0, D) = jrand
+ *   MBX_SITE_NOISE0_A/B(0)    evaluation of the trial
+ *   MBX_SITE_DD_WALK(i*D+d)   u53(w0,w1) = walk_u
+ *   MBX_SITE_NOISE1_A/B(i)    __cal_feature's evaluation of row i (reset and step)                                                       */
+#define MBX_DEDQN_NP_MAX   128
+#define MBX_DEDQN_DIM_MAX  40
+#define MBX_DEDQN_NFEAT    4
+#define MBX_DEDQN_TAPE_POS(NP, D)         ((int64_t)0)
+#define MBX_DEDQN_TAPE_NOISE_INIT(NP, D)  ((int64_t)(NP) * (D))
+#define MBX_DEDQN_TAPE_WALK_INIT(NP, D)   ((int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_DEDQN_TAPE_NOISE_FEAT0(NP, D) (2 * (int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_DEDQN_TAPE_R(NP, D)           ((int64_t)0)
+#define MBX_DEDQN_TAPE_JRAND(NP, D)       ((int64_t)4)
+#define MBX_DEDQN_TAPE_NOISE(NP, D)       ((int64_t)5)
+#define MBX_DEDQN_TAPE_CROSS(NP, D)       ((int64_t)8)
+#define MBX_DEDQN_TAPE_WALK(NP, D)        ((int64_t)8 + (D))
+#define MBX_DEDQN_TAPE_NOISE_FEAT(NP, D)  ((int64_t)8 + (D) + (int64_t)(NP) * (D))
+#define MBX_DEDQN_TAPE_STRIDE(NP, D)      (2 * (int64_t)(NP) * (D) + 6 * (int64_t)(NP) + 8)
+#define MBX_DEDQN_ST_POP(NP, D)           ((int64_t)0)
+#define MBX_DEDQN_ST_COST(NP, D)          ((int64_t)(NP) * (D))
+#define MBX_DEDQN_ST_SURVIVAL(NP, D)      ((int64_t)(NP) * (D) + (NP))
+#define MBX_DEDQN_ST_SCOST(NP, D)         ((int64_t)(NP) * (D) + 2 * (int64_t)(NP))
+#define MBX_DEDQN_ST_GBPOS(NP, D)         ((int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_DEDQN_ST_FEAT(NP, D)          ((int64_t)(NP) * (D) + 3 * (int64_t)(NP) + (D))
+#define MBX_DEDQN_FEAT_SLOTS 16
+#define MBX_DEDQN_ST_SCALARS(NP, D)       (MBX_DEDQN_ST_FEAT(NP, D) + MBX_DEDQN_FEAT_SLOTS)
+#define MBX_DEDQN_STATE_DOUBLES(NP, D, NLOG) (MBX_DEDQN_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)
+#define MBX_DEDQN_FEAT_LEVEL  4   /* feat[4]: winning ruggedness level 0..8; feat[5..10]: its six transition counts */
+#define MBX_DEDQN_FEAT_COUNTS 5
+#define MBX_DEDQN_FEAT_UCOST  11  /* feat[11]: u_cost of the last update() */
+#define MBX_DEDQN_FEAT_Q      12  /* feat[12..14]: Q(state) of the last in-kernel decision */
+#define MBX_SC_DEDQN_POINTER 10
+#define MBX_SC_DEDQN_G0      11
+#define MBX_SC_DEDQN_ALIAS   12
+#define MBX_SITE_DD_R        38u
+#define MBX_SITE_DD_WALK     39u
+#define MBX_SITE_DD_NOISE_A  40u
+#define MBX_SITE_DD_NOISE_B  41u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

@@ -52,6 +52,11 @@ class QNet(C.Structure):
     _fields_ = [('d_weights', C.c_void_p), ('in_dim', C.c_int32), ('width', C.c_int32), ('depth', C.c_int32), ('n_act', C.c_int32)]
 
 
+class DedqnNet(C.Structure):
+    """mbx_dedqn_net"""
+    _fields_ = [('d_weights', C.c_void_p), ('in_dim', C.c_int32), ('hidden', C.c_int32), ('n_act', C.c_int32)]
+
+
 class GleetActor(C.Structure):
     """mbx_gleet_actor"""
     _fields_ = [('d_weights', C.c_void_p), ('n_floats', C.c_int32), ('min_sigma', C.c_float), ('max_sigma', C.c_float)]
@@ -61,6 +66,7 @@ ALGO_RLEPSO, ALGO_LDE, ALGO_DEDDQN, ALGO_RANDOM_SEARCH, ALGO_RLPSO, ALGO_GLEET, 
 ALGO_GLPSO = 11
 ALGO_JDE21 = 13      # (12 is not assigned)
 ALGO_MADDE = 15      # (14 is not assigned)
+ALGO_DEDQN = 16
 POLICY_RLEPSO, POLICY_RLPSO = 0, 1
 _ARRAY_FIELDS = ('dshift', 'm1', 'm2', 'v0', 'v1', 'v2', 'py', 'pc', 'pw')
 
@@ -149,6 +155,7 @@ def load_lib():
         'mbx_lde_rollout': (C.c_int, [vp, C.POINTER(LstmPolicy), vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
         'mbx_rlpso_rollout': (C.c_int, [vp, C.POINTER(GaussMlp), C.c_int, vp, vp, vp, vp, vp]),
         'mbx_qlpso_rollout': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+        'mbx_dedqn_rollout': (C.c_int, [vp, C.POINTER(DedqnNet), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
         'mbx_gleet_policy': (C.c_int, [vp, C.POINTER(GleetActor), vp, vp, vp, vp]),
         'mbx_debug_math': (C.c_int, [C.c_int, vp, vp, vp, C.c_int, vp]),
         'mbx_debug_rlepso_draws': (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
@@ -176,7 +183,7 @@ EXPORTED_SYMBOLS = ('mbx_suite_create', 'mbx_suite_destroy', 'mbx_suite_size', '
                     'mbx_tape_stride', 'mbx_batch_create', 'mbx_batch_destroy', 'mbx_batch_flags', 'mbx_set_tape', 'mbx_reset', 'mbx_step', 'mbx_results',
                     'mbx_gauss_policy', 'mbx_lde_policy', 'mbx_ddqn_qnet', 'mbx_rlepso_policy_table_rows', 'mbx_rlepso_policy_table', 'mbx_rlepso_act_step',
                     'mbx_rlepso_rollout_resident', 'mbx_rlepso_rollout', 'mbx_lde_rollout_resident', 'mbx_lde_rollout', 'mbx_rlpso_rollout',
-                    'mbx_qlpso_rollout', 'mbx_gleet_policy', 'mbx_debug_math', 'mbx_debug_rlepso_draws', 'mbx_batch_launch_info', 'mbx_instance_state_doubles',
+                    'mbx_qlpso_rollout', 'mbx_dedqn_rollout', 'mbx_gleet_policy', 'mbx_debug_math', 'mbx_debug_rlepso_draws', 'mbx_batch_launch_info', 'mbx_instance_state_doubles',
                     'mbx_debug_read_state', 'mbx_debug_write_state', 'mbx_debug_clock_probe', 'mbx_debug_clock_mark', 'mbx_debug_clock_slots',
                     'mbx_batch_rebind', 'mbx_read_public', 'mbx_last_error', 'mbx_version')
 

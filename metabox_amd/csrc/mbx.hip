@@ -1,5 +1,5 @@
 // mbx.hip — libmbx.so: kernels' launch code and the C-ABI of include/mbx.h.
-// Build: make -C metabox_amd/csrc  (six translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
+// Build: make -C metabox_amd/csrc  (seven translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -41,6 +41,9 @@
 #define MBX_RUN_KERNELS_EXTERN
 #endif
 #include "mbx_run_kernels.hpp"
+#ifdef MBX_SINGLE_TU
+#include "mbx_run_dedqn.hip"           // the DEDQN kernels and their launch code, in this file as well
+#endif
 
 using namespace mbx;
 
@@ -82,7 +85,7 @@ struct mbx_batch {
     uint64_t* d_seeds = nullptr;
     double* d_state = nullptr;
     int32_t* d_order = nullptr;
-    double* d_pci = nullptr;
+    double* d_pci = nullptr;               // RLEPSO: learning-probability curve [np]; DEDQN: correctly rounded log(n / np), n = 0 .. np
     unsigned long long* d_clk = nullptr;   // mbx_debug_clock_slots: the caller's slot block for the NEXT resident RLEPSO launches (not owned)
     double* d_scratch = nullptr; // [B] per-generation rewards of mbx_rlepso_rollout's host-loop route (RLEPSO batches; allocated by mbx_batch_create)
     float* d_lstm_pack = nullptr;          // k-blocked copy of the PolicyNet weights for k_lde_run (k_lde_repack at every mbx_lde_rollout call)
@@ -180,6 +183,12 @@ static AlgoGeom geom_of(const mbx_algo_cfg& c)
         g.tape_stride = MBX_MADDE_TAPE_STRIDE(c.np, c.dim);
         g.lds_doubles = md_lds_doubles(c.np, c.dim);
         g.state_dim = 1; g.action_dim = 0;
+    } else if (c.algo == MBX_ALGO_DEDQN) {
+        g.state_doubles = MBX_DEDQN_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
+        g.sc_off = MBX_DEDQN_ST_SCALARS(c.np, c.dim);
+        g.tape_stride = MBX_DEDQN_TAPE_STRIDE(c.np, c.dim);
+        g.lds_doubles = dedqn_lds_doubles(c.np, c.dim);
+        g.state_dim = MBX_DEDQN_NFEAT; g.action_dim = 1;
     }
     return g;
 }
@@ -471,13 +480,17 @@ static int check_cfg(const mbx_algo_cfg* c)
 {
     if (!c) return fail(MBX_E_ARG, "null cfg");
     // the ids this build has kernels for (12 and 14 are not assigned)
-    if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21 || c->algo == MBX_ALGO_MADDE))
+    if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21 || c->algo == MBX_ALGO_MADDE || c->algo == MBX_ALGO_DEDQN))
         return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
     if (c->algo == MBX_ALGO_JDE21 && c->np != MBX_JDE21_NP) return fail(MBX_E_ARG, "JDE21 runs np = %d (160 + 10 rows), not %d", MBX_JDE21_NP, c->np);
     if (c->algo == MBX_ALGO_MADDE) {
         // the one algorithm whose rows are strided over the lanes: np is 2 dim^2, and LDS is sized for at most 3200 rows
         if (c->dim < 2 || c->dim > MBX_MADDE_DIM_MAX) return fail(MBX_E_ARG, "MadDE runs dim in [2, %d], not %d", MBX_MADDE_DIM_MAX, c->dim);
         if (c->np != MBX_MADDE_NP(c->dim)) return fail(MBX_E_ARG, "MadDE runs np = 2 dim^2 = %d, not %d", MBX_MADDE_NP(c->dim), c->np);
+    } else if (c->algo == MBX_ALGO_DEDQN) {
+        // the landscape analysis deals one row per lane of two waves, and LDS holds the population three times over
+        if (c->np < 4 || c->np > MBX_DEDQN_NP_MAX) return fail(MBX_E_ARG, "DEDQN runs np in [4, %d], not %d", MBX_DEDQN_NP_MAX, c->np);
+        if (c->dim < 2 || c->dim > MBX_DEDQN_DIM_MAX) return fail(MBX_E_ARG, "DEDQN runs dim in [2, %d], not %d", MBX_DEDQN_DIM_MAX, c->dim);
     } else if (c->np < 4 || c->np > kThreads) return fail(MBX_E_ARG, "np %d outside [4, %d]", c->np, kThreads);
     if (c->dim < 2 || c->dim > 64) return fail(MBX_E_ARG, "dim %d outside [2, 64]", c->dim);
     if (c->algo == MBX_ALGO_RLEPSO && (c->n_group < 1 || c->n_group > 16 || c->np / c->n_group < 1))
@@ -688,6 +701,15 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
     } else if (cfg->algo == MBX_ALGO_MADDE) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_madde_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_madde_generation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    } else if (cfg->algo == MBX_ALGO_DEDQN) {
+        HIP_TRY(dedqn_prepare(lds));
+        {   // cal_rie's frequencies are n / NP: their logarithms, correctly rounded (extended precision, then one rounding to double), so that the kernel's
+            // entropies do not depend on the device's log (mbx_dedqn.hpp: dd_features); the batch's table pointer `pci` carries them
+            std::vector<double> lt(cfg->np + 1, 0.);
+            for (int n = 1; n < cfg->np; ++n) lt[n] = (double)std::log((long double)((double)n / (double)cfg->np));
+            HIP_TRY(hipMalloc(&b->d_pci, lt.size() * sizeof(double)));
+            HIP_TRY(hipMemcpy(b->d_pci, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
     } else if (cfg->algo == MBX_ALGO_QLPSO) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -802,6 +824,8 @@ extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
         hipLaunchKernelGGL(k_jde21_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_MADDE)
         hipLaunchKernelGGL(k_madde_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
+    else if (b->cfg.algo == MBX_ALGO_DEDQN)
+        dedqn_launch_reset(make_params(b), b->lds_bytes, (hipStream_t)stream, d_state_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_GLEET)
@@ -856,6 +880,8 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
     else if (b->cfg.algo == MBX_ALGO_MADDE)
         hipLaunchKernelGGL(k_madde_generation, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
                            d_reward_out, d_done_out);
+    else if (b->cfg.algo == MBX_ALGO_DEDQN)
+        dedqn_launch_step(make_params(b), b->lds_bytes, (hipStream_t)stream, (const int32_t*)d_actions, d_state_out, d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_step<false>, dim3(b->B), dim3(kThreads), (size_t)ql_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double),
                            (hipStream_t)stream, make_params(b), (const int32_t*)d_actions, (const double*)nullptr, 1, d_state_out,
@@ -1176,6 +1202,22 @@ extern "C" int mbx_gleet_policy(mbx_batch* b, const mbx_gleet_actor* net, const 
     const GleetActor g{net->d_weights, net->min_sigma, net->max_sigma};
     hipLaunchKernelGGL(k_gleet_policy, dim3(b->B), dim3(kGpThreads), gleet_policy_lds_bytes(b->cfg.np), (hipStream_t)stream, make_params(b),
                        g, d_state, d_actions, d_mu_sigma);
+    HIP_TRY(hipGetLastError());
+    return MBX_OK;
+}
+
+extern "C" int mbx_dedqn_rollout(mbx_batch* b, const mbx_dedqn_net* net, int n_steps, int32_t* d_traj_actions, double* d_traj_state,
+                                 double* d_traj_reward, int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out,
+                                 void* stream)
+{
+    if (!b || !net || !net->d_weights) return fail(MBX_E_ARG, "mbx_dedqn_rollout: bad arguments");
+    if (b->cfg.algo != MBX_ALGO_DEDQN) return fail(MBX_E_UNSUPPORTED, "mbx_dedqn_rollout: the batch is not a DEDQN batch");
+    if (net->in_dim != MBX_DEDQN_NFEAT || net->hidden != 10 || net->n_act != 3)
+        return fail(MBX_E_UNSUPPORTED, "mbx_dedqn_rollout: only the reference's 4 -> 10 -> 10 -> 3 network is built");
+    if (n_steps < 1) return fail(MBX_E_ARG, "mbx_dedqn_rollout: n_steps must be >= 1");
+    if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_dedqn_rollout: a replay tape holds one step");
+    dedqn_launch_run(make_params(b), b->lds_bytes, (hipStream_t)stream, net->d_weights, n_steps, d_traj_actions, d_traj_state, d_traj_reward,
+                     d_actions_out, d_state_out, d_reward_out, d_done_out);
     HIP_TRY(hipGetLastError());
     return MBX_OK;
 }

@@ -10,6 +10,7 @@
 #pragma once
 #include "mbx_device.hpp"
 #include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_npsum.hpp"    // np_sum: numpy's pairwise summation order
 
 namespace mbx {
 // four waves per SIMD: left alone the compiler takes 126-160 VGPRs for the multi-step / sweep kernels (three resident workgroups per CU
@@ -17,34 +18,6 @@ namespace mbx {
 #ifndef MBX_N4_WAVES
 #define MBX_N4_WAVES __attribute__((amdgpu_waves_per_eu(4)))
 #endif
-
-// np.add.reduce over n <= 128 contiguous values produced by elem(k): 8 accumulators, then the tail (numpy's pairwise_sum).
-template <class F>
-__device__ __forceinline__ double np_sum_block(F elem, int n)
-{
-    if (n < 8) { double s = 0.; for (int k = 0; k < n; ++k) s += elem(k); return s; }
-    double r[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = elem(k);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] += elem(i + k);
-    }
-    double s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) s += elem(i);
-    return s;
-}
-
-// ... and for n <= 256 (one halving step above 128 elements)
-template <class F>
-__device__ __forceinline__ double np_sum(F elem, int n)
-{
-    if (n <= 128) return np_sum_block(elem, n);
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_sum_block(elem, n2) + np_sum_block([&](int k) { return elem(n2 + k); }, n - n2);
-}
 
 struct QlLds {
     double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *POP, *COST, *MEAN, *DIST, *SC;

@@ -26,3 +26,13 @@ extern template __global__ void k_lde_run<50, 10>(LdeRunArgs);
 extern template __global__ void k_lde_run<50, 30, 50, true>(LdeRunArgs);
 }  // namespace mbx
 #endif
+// DEDQN (mbx_dedqn.hpp): kernels AND launch code live in mbx_run_dedqn.hip; mbx.hip reaches them through these host functions
+namespace mbx {
+int64_t dedqn_lds_doubles(int np, int dim);
+hipError_t dedqn_prepare(size_t lds_bytes);         // the kernels' dynamic-LDS limit, once per batch
+void dedqn_launch_reset(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, double* d_state_out);
+void dedqn_launch_step(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, const int32_t* d_actions, double* d_state_out, double* d_reward_out,
+                       uint8_t* d_done_out);
+void dedqn_launch_run(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, const float* d_net, int n_steps, int32_t* d_traj_actions,
+                      double* d_traj_state, double* d_traj_reward, int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
+}  // namespace mbx

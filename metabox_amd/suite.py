@@ -142,7 +142,7 @@ class Batch:
         """actions: CUDA tensor [B, action_dim] (float32).  Returns (state, reward, done) device tensors that are
         overwritten by the next call."""
         if self.action_dim > 0:
-            want = torch.int32 if self.cfg.algo in (_abi.ALGO_DEDDQN, _abi.ALGO_QLPSO) else torch.float32
+            want = torch.int32 if self.cfg.algo in (_abi.ALGO_DEDDQN, _abi.ALGO_QLPSO, _abi.ALGO_DEDQN) else torch.float32
             assert actions.is_cuda and actions.is_contiguous() and actions.dtype == want
             assert actions.numel() == self.B * self.action_dim
         else:
@@ -192,6 +192,29 @@ class Batch:
         _abi.check(self.lib.mbx_qlpso_rollout(self._h, _ptr(q_table), int(n_steps), _ptr(acts), _ptr(self.state), _ptr(self.reward),
                                               _ptr(self.done), _stream()))
         return (self.state, self.reward, self.done, acts) if want_actions else (self.state, self.reward, self.done)
+
+    def dedqn_rollout(self, weights, n_steps, trajectory=False):
+        """`n_steps` DEDQN env steps of every instance in ONE launch, the 4 -> 10 -> 10 -> 3 Q-network evaluated in the kernel and the population
+        on chip in between (``mbx_dedqn_rollout``); bit-identical to `n_steps` one-step calls and to step() fed the same actions.  weights: packed
+        float32 CUDA tensor (``DEDQN_Agent.packed_weights``, 193 values).  Returns (state, reward summed over the executed steps, done, last actions
+        int32 [B]) and, with ``trajectory=True``, a dict of per-step records: actions [n_steps, B] int32 (-1 where not written), state
+        [n_steps, B, 4] / reward [n_steps, B] float64 (zero after an instance's termination)."""
+        assert weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous()
+        if weights.numel() != 193:
+            raise ValueError(f'packed Q-network has {weights.numel()} floats, 4 -> 10 -> 10 -> 3 needs 193')
+        n_steps = int(n_steps)
+        if getattr(self, '_iactions', None) is None:
+            self._iactions = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        traj = None
+        if trajectory:
+            traj = {'actions': torch.full((n_steps, self.B), -1, dtype=torch.int32, device=self.device),
+                    'state': torch.zeros(n_steps, self.B, self.state_dim, dtype=torch.float64, device=self.device),
+                    'reward': torch.zeros(n_steps, self.B, dtype=torch.float64, device=self.device)}
+        t = traj or {}
+        net = _abi.DedqnNet(weights.data_ptr(), self.state_dim, 10, 3)
+        _abi.check(self.lib.mbx_dedqn_rollout(self._h, C.byref(net), n_steps, _ptr(t.get('actions')), _ptr(t.get('state')), _ptr(t.get('reward')),
+                                              _ptr(self._iactions), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
+        return (self.state, self.reward, self.done, self._iactions, traj) if trajectory else (self.state, self.reward, self.done, self._iactions)
 
     def ddqn_qnet(self, weights, width=100, depth=4, n_act=4, want_q=False):
         """DE-DDQN's greedy action over the batch's own state tensor in one launch (``mbx_ddqn_qnet``: the Q-network on the float32

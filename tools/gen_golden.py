@@ -1687,7 +1687,219 @@ def gen_madde():
         print(os.path.basename(path), os.path.getsize(path))
         assert os.path.getsize(path) < 1024 * 1024
 
-SECTIONS = {'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+# ------------------------------------------------------------------------------------------------ DEDQN
+# dedqn_policy.npz : the shipped bbob_easy Q-network (4 -> 10 -> 10 -> 3) and 64 (state -> Q, argmax) pairs on recorded states.
+# dedqn_traces*.npz: whole reference episodes.  Per step: action, state[4], reward, done, gbest, fes, the trial's cost and the NP
+#                    `samples_cost` the features were computed from (the numpy draws are NOT stored: the test regenerates them from the
+#                    seed); at a few steps the population, cost and survival; the stream position after the episode.
+# dedqn_train.npz  : one DQN update from the agent's own train_episode: mini-batch, parameters before, gradients, parameters after.
+# NOT pinned against the reference: noisy behaviour beyond 9 steps.  A noisy function redraws every cost at every step, so every step meets the
+# ruggedness margins afresh and no 99-step noisy episode passes them all; the three noisy cases run a budget of 2000 FEs.
+# The generator asserts the margins the GPU tests rely on (the kernel's objective values agree with numpy's to the cost tolerance of
+# tests/helpers.py, not to the bit); a candidate episode that misses one is replaced by the next seed.
+DEDQN_RTOL, DEDQN_ATOL = 1e-5, 8 * 4.6e-13          # tests/helpers.py
+
+
+class _DedqnMargin(Exception):
+    pass
+
+
+def _dedqn_margins(samples, fitness):
+    """Distinct walk distances, an unambiguous best sample, every ruggedness comparison and every descent comparison clear of the
+    tolerance.  (No positive difference exceeds epsilon_star, so level 0 has no upper comparison to protect.)"""
+    tol = lambda a, b: 2 * (DEDQN_ATOL + DEDQN_RTOL * max(abs(a), abs(b)))      # noqa: E731
+    order = np.argsort(fitness, kind='stable')
+    if fitness[order[1]] - fitness[order[0]] <= tol(fitness[order[0]], fitness[order[1]]):
+        raise _DedqnMargin('best sample')
+    dist = np.linalg.norm(samples - samples[order[0]], axis=-1)
+    if len(np.unique(dist)) != len(dist):
+        raise _DedqnMargin('equal walk distances')
+    diff = fitness[1:] - fitness[:-1]
+    star = max(diff.max(), 0.)
+    for k in range(9):
+        eps = star / 2 ** k if k < 8 else 0.
+        gap = np.minimum(np.abs(diff + eps), np.abs(diff - eps) if k > 0 else np.where(diff > 0, np.inf, np.abs(diff - eps)))
+        if np.any(gap <= 1e-4 * star):
+            raise _DedqnMargin(f'ruggedness level {k}')
+    fs = fitness[np.argsort(dist, kind='stable')]
+    if any(abs(fs[i + 1] - fs[i]) <= tol(fs[i], fs[i + 1]) for i in range(len(fs) - 1)):
+        raise _DedqnMargin('descent comparison')
+
+
+def run_dedqn_episode(problem, seed, net, config, override, opt=None, snaps=6):
+    """One reference DEDQN rollout: greedy argmax of the shipped network, `override` of the actions replaced from a private RandomState."""
+    import copy
+    import optimizer.dedqn_optimizer as ref_mod
+    from environment import PBO_Env
+    opt = opt if opt is not None else ref_mod.DEDQN_Optimizer(copy.deepcopy(config))
+    get = lambda name: getattr(opt, '_DEDQN_Optimizer__' + name)          # noqa: E731
+    seen, evals = [], []
+    real_fdc, real_eval = ref_mod.cal_fdc, problem.eval
+
+    def fdc(sample, fitness):
+        seen.append((np.array(sample), np.array(fitness, dtype=np.float64)))
+        return real_fdc(sample, fitness)
+
+    def ev(x):
+        f = real_eval(x)
+        evals.append((np.ndim(x), np.array(f, dtype=np.float64)))
+        return f
+    ref_mod.cal_fdc, problem.eval = fdc, ev
+    try:
+        env = PBO_Env(problem, opt)
+        np.random.seed(seed)
+        ars = np.random.RandomState(70_000 + seed)
+        pointer0 = int(get('solution_pointer'))
+        state = env.reset()
+        _dedqn_margins(*seen[-1])
+        rec = dict(actions=[], states=[state], reward=[], done=[], gbest=[float(get('gbest_cost'))], fes=[opt.fes], ucost=[], scost=[seen[-1][1]])
+        snap = {0: (np.array(get('population')), np.array(get('cost')), np.array(get('survival')))}
+        done, g = False, 0
+        while not done:
+            with torch.no_grad():
+                a = int(torch.argmax(net(torch.Tensor(state))))
+            if override and ars.rand() < override:
+                a = int(ars.randint(0, 3))
+            state, r, done = env.step(a)
+            g += 1
+            _dedqn_margins(*seen[-1])
+            nd, f = evals[-2]
+            assert nd == 1
+            rec['actions'].append(a); rec['states'].append(state); rec['reward'].append(float(r)); rec['done'].append(bool(done))
+            rec['gbest'].append(float(get('gbest_cost'))); rec['fes'].append(opt.fes); rec['scost'].append(seen[-1][1])
+            rec['ucost'].append(float(f) if problem.optimum is None else float(f - problem.optimum))
+            snap[g] = (np.array(get('population')), np.array(get('cost')), np.array(get('survival')))
+    finally:
+        ref_mod.cal_fdc = real_fdc
+        del problem.eval
+    G = len(rec['actions'])
+    keep = sorted(set(int(v) for v in np.linspace(0, G, snaps)))
+    out = {'actions': np.array(rec['actions'], dtype=np.uint8), 'states': np.stack(rec['states']), 'reward': np.array(rec['reward']),
+           'done': np.array(rec['done']), 'gbest': np.array(rec['gbest']), 'fes': np.array(rec['fes'], dtype=np.int64), 'ucost': np.array(rec['ucost']),
+           'scost': np.stack(rec['scost']), 'cost': np.array(opt.cost, dtype=np.float64), 'pointer0': np.int64(pointer0),
+           'pointer': np.int64(get('solution_pointer')), 'snap_steps': np.array(keep), 'gbest_pos': np.array(get('gbest'), dtype=np.float64),
+           'next_rand': np.float64(np.random.rand())}
+    for s in keep:
+        out[f'snap{s}/pop'], out[f'snap{s}/cost'], out[f'snap{s}/survival'] = snap[s]
+    return opt, out
+
+
+def gen_dedqn():
+    import copy as _copy
+    import random as _random
+    import types
+    from agent import DEDQN_Agent
+    scratch = tempfile.mkdtemp()
+    agent = load_shipped(os.path.join(ref_import.REF_SRC, 'agent_model/test/bbob_easy/DEDQN_Agent.pkl'))
+    net = agent._DEDQN_Agent__dqn
+    pol = {'net/' + k: v.detach().cpu().numpy() for k, v in net.state_dict().items()}
+    assert [tuple(v.shape) for v in pol.values()] == [(10, 4), (10,), (10, 10), (10,), (3, 10), (3,)]
+
+    def config_for(suite, dim, max_fes=None):
+        c = ref_import.ref_config(['--problem', suite] + ([] if suite == 'protein' else ['--dim', str(dim)]), scratch)
+        if max_fes is not None:
+            c.maxFEs = max_fes
+            c.log_interval = c.maxFEs // c.n_logpoint
+        return c
+
+    def pick(suite, dim, fid):
+        if suite == 'protein':
+            return protein_problems()[0][fid]
+        tr, te, _ = all_problems(suite, dim)
+        return {fid_of(p): p for p in tr + te}[fid]
+    # (suite, dim, function, first seed, budget, share of overridden actions, a second episode on the same object).  A noisy function draws new
+    # costs at every step, so every step meets the ruggedness margins afresh: those episodes are 9 steps long (as many seeds as it takes).
+    jobs = [('bbob', 10, 1, 81, None, 0., False), ('bbob', 10, 7, 82, None, 0.35, False), ('bbob', 10, 15, 83, None, 0.35, False),
+            ('bbob', 10, 21, 84, None, 0.35, False), ('bbob-noisy', 10, 101, 85, 2000, 0.35, False), ('bbob-noisy', 10, 102, 86, 2000, 0.35, False),
+            ('bbob-noisy', 10, 103, 87, 2000, 0.35, False), ('bbob', 30, 10, 88, 5000, 0.35, False), ('protein', 12, '1ATN_7', 89, None, 0.35, False),
+            ('bbob', 10, 5, 90, 6000, 0.35, True)]
+    files, cases = [{}, {}, {}], []
+    for n, (suite, dim, fid, seed0, budget, override, second) in enumerate(jobs):
+        config = config_for(suite, dim, budget)
+        for seed in range(seed0, seed0 + 100000, 100):
+            p = pick(suite, dim, fid)
+            p.reset()
+            try:
+                opt, rec = run_dedqn_episode(p, seed, net, config, override)
+                rec2 = run_dedqn_episode(p, seed + 1, net, config, override, opt=opt)[1] if second else None
+                break
+            except _DedqnMargin as e:
+                print(f'  {suite}/{dim}/{fid} seed {seed}: margin missed ({e}); next seed')
+        else:
+            raise RuntimeError(f'no seed passes the margins for {suite}/{dim}/{fid}')
+        key = f'{suite}/{dim}/{fid}/{seed}'
+        cases.append(key)
+        out = files[n % len(files)]
+        out[f'{key}/max_fes'] = np.int64(config.maxFEs)
+        for k, v in rec.items():
+            out[f'{key}/{k}'] = v
+        if rec2 is not None:
+            for k, v in rec2.items():
+                out[f'{key}/second/{k}'] = v
+        print(key, 'steps', len(rec['actions']), 'fes', rec['fes'][-1], 'log points', len(rec['cost']), 'actions', np.bincount(rec['actions'], minlength=3),
+              'pointer', rec['pointer'], '' if rec2 is None else f"second: steps {len(rec2['actions'])} pointer {rec2['pointer0']} -> {rec2['pointer']}")
+    files[0]['cases'] = np.array(cases)
+    for n, out in enumerate(files):
+        path = os.path.join(OUT, 'dedqn_traces.npz' if n == 0 else f'dedqn_traces_{n}.npz')
+        np.savez_compressed(path, **out)
+        assert os.path.getsize(path) < 2 ** 20, (path, os.path.getsize(path))
+    # the policy fixture: 64 recorded states (float64 as the optimizer returns them) and the float32 network's answers
+    st = np.concatenate([files[n % len(files)][f'{c}/states'] for n, c in enumerate(cases)])
+    st = st[np.random.RandomState(5).permutation(len(st))[:64]]
+    with torch.no_grad():
+        q = net(torch.Tensor(st)).numpy()
+    pol.update({'io/x': st, 'io/q': q, 'io/argmax': np.argmax(q, axis=1).astype(np.int32)})
+    np.savez_compressed(os.path.join(OUT, 'dedqn_policy.npz'), **pol)
+    print('policy io: argmax counts', np.bincount(pol['io/argmax'], minlength=3))
+
+    # ---- one DQN update through the agent's own train_episode (warm-up 64 = batch 64): the TD target is NOT detached
+    config = ref_import.ref_config(['--problem', 'bbob', '--dim', '10', '--max_learning_step', '1'], scratch)
+    config.save_interval = 10 ** 9
+    torch.manual_seed(41)
+    ag = DEDQN_Agent(_copy.deepcopy(config))
+    dqn = ag._DEDQN_Agent__dqn
+    data = {f'init/net/{k}': v.cpu().numpy().copy() for k, v in dqn.state_dict().items()}
+    sink, batches = [], []
+    _hook_steps(ag._DEDQN_Agent__optimizer, list(dqn.named_parameters()), sink, 'net')
+    rb = ag._DEDQN_Agent__replay_buffer
+    orig_sample = rb.sample
+
+    def sample(n):
+        got = orig_sample(n)
+        batches.append([t.cpu().numpy().copy() for t in got])
+        return got
+    rb.sample = sample
+    rs = np.random.RandomState(6)
+
+    class DEnv:
+        optimizer = types.SimpleNamespace(cost=[1.0, 0.5])
+
+        def __init__(self):
+            self.t = 0
+
+        def reset(self):
+            self.t = 0
+            return rs.uniform(-1, 1, size=4)
+
+        def step(self, a):
+            self.t += 1
+            return rs.uniform(-1, 1, size=4), float(rs.uniform(0, 1)), self.t >= 9
+    _random.seed(13)
+    np.random.seed(13)
+    while not sink:                                  # episodes of 9 steps: the replay holds terminal transitions when it reaches 64
+        ag.train_episode(DEnv())
+    assert len(sink) == 1 and len(batches) == 1 and 0 < batches[0][4].sum() < 64
+    for name, arr in zip(('obs', 'act', 'rew', 'nxt', 'done'), batches[0]):
+        data[f'batch/{name}'] = arr
+    for k, g in sink[0][1].items():
+        data[f'grad/net/{k}'] = g
+    for k, v in dqn.state_dict().items():
+        data[f'post/net/{k}'] = v.cpu().numpy().copy()
+    np.savez_compressed(os.path.join(OUT, 'dedqn_train.npz'), **data)
+    print('dedqn train: batch', batches[0][0].shape, 'done in batch', batches[0][4].sum())
+
+
+SECTIONS = {'dedqn': gen_dedqn, 'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -213,3 +213,38 @@ if 'madde' in which:
             print(json.dumps({'path': f'{name} bbob d={dim} NP={np_}, {B} instances, one launch per update', 'us_per_step': dt / 10 * 1e6,
                               'launch_info': b.launch_info()}))
             b.close()
+if 'dedqn' in which:
+    # DEDQN (one env step = one trial row + the landscape analysis over a re-evaluation of all NP = 100 rows: 101 row evaluations) next to Random_search's
+    # 100-row kernel in the same process: bbob round-robin, 4096 instances at D = 10 and 1024 at D = 30, a budget so large that every instance stays live.
+    # k_dedqn_step: one launch per step with the action from the host side; k_dedqn_run: 32 steps per launch with the shipped Q-network in the kernel.
+    from metabox_amd._abi import ALGO_DEDQN, ALGO_RANDOM_SEARCH
+    from metabox_amd.agent import DEDQN_Agent
+    from metabox_amd.suite import Batch, Suite
+    acfg = get_config(['--problem', 'bbob', '--dim', '10', '--device', 'cuda']); acfg.agent_save_dir = None
+    agent = DEDQN_Agent(acfg).load_exported_weights(np.load(os.path.join(os.path.dirname(__file__), '..', 'tests', 'golden', 'dedqn_policy.npz')))
+    packed = agent.packed_weights().cuda()
+    for dim, B in ((10, 4096), (30, 1024)):
+        cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+        tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+        s = Suite(ps)
+        b = Batch(s, ALGO_RANDOM_SEARCH, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, 100, 10 ** 9, 10 ** 7, 50, early_stop=False)
+        b.reset()
+        def run(n):
+            for _ in range(n): b.step(None)
+        run(3); dt = timed(run, 30)
+        print(json.dumps({'path': f'k_rs_population bbob d={dim} NP=100, {B} instances', 'us_per_step': dt / 30 * 1e6, 'ns_per_row': dt / 30 / (100 * B) * 1e9}))
+        b.close()
+        b = Batch(s, ALGO_DEDQN, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, 100, 10 ** 9, 10 ** 7, 50, early_stop=False)
+        b.reset()
+        acts = torch.full((B,), 2, dtype=torch.int32, device='cuda')
+        def run_step(n):
+            for _ in range(n): b.step(acts)
+        run_step(3); dt = timed(run_step, 30)
+        print(json.dumps({'path': f'k_dedqn_step bbob d={dim} NP=100, {B} instances, one launch per env step', 'us_per_step': dt / 30 * 1e6,
+                          'ns_per_row': dt / 30 / (101 * B) * 1e9, 'launch_info': b.launch_info()}))
+        def run_res(n):
+            for _ in range(n): b.dedqn_rollout(packed, 32)
+        run_res(1); dt = timed(run_res, 3)
+        print(json.dumps({'path': f'k_dedqn_run bbob d={dim} NP=100, {B} instances, 32 env steps per launch, Q-network in the kernel', 'us_per_step': dt / 96 * 1e6,
+                          'ns_per_row': dt / 96 / (101 * B) * 1e9}))
+        b.close()
