@@ -109,6 +109,7 @@ int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, double* d_f,
 #define MBX_ALGO_GLPSO  11  /* src/optimizer/gl_pso.py             one step = one generation (2 NP FEs) -- classic baseline, no agent */
 #define MBX_ALGO_JDE21  13  /* src/optimizer/jde21.py              one step = one update (2 bNP FEs), np = 170 -- classic baseline, no agent (12 is not assigned) */
 #define MBX_ALGO_MADDE  15  /* src/optimizer/madde.py              one step = one update (NP FEs), np = 2 dim^2, dim <= 40 -- classic baseline, no agent (12 and 14 are not assigned and stay rejected) */
+#define MBX_ALGO_SDMSPSO 18 /* src/optimizer/sdms_pso.py           one step = one update (NP FEs), np = 99, dim <= 40, max_fes in (99, 103272] -- classic baseline, no agent (12, 14 and 17 are not assigned and stay rejected) */
 #define MBX_ALGO_DEDQN  16  /* src/optimizer/dedqn_optimizer.py     one step = one trial vector + the landscape analysis (2 NP FEs), np in [4, 128], dim <= 40 */
 
 typedef struct mbx_algo_cfg {
@@ -119,7 +120,7 @@ typedef struct mbx_algo_cfg {
     int32_t max_fes;       /* config.maxFEs       (src/config.py:74,88)                           */
     int32_t log_interval;  /* config.log_interval (src/config.py:102)                             */
     int32_t n_logpoint;    /* config.n_logpoint   (src/config.py:77,90)                           */
-    int32_t early_stop;    /* 1 = reference rule `done = fes>=maxFEs or gbest<=1e-8`; 0 = fixed horizon */
+    int32_t early_stop;    /* 1 = reference rule `done = fes>=maxFEs or gbest<=1e-8`; 0 = fixed horizon (SDMSPSO: no effect, the reference has no early stop there) */
     int32_t n_group;       /* RLEPSO: 5 (rlepso_optimizer.py:26)                                  */
     uint32_t flags;        /* MBX_F_* below, OR-ed; 0 = the defaults.  Per batch: two batches of one process may differ. */
 } mbx_algo_cfg;
@@ -149,6 +150,7 @@ int mbx_batch_flags(const mbx_batch* b);
  *   QLPSO         : state [1]      (qlpso_optimizer.py:89-90,125),          action [1] int32 in {0..3}
  *   DE, PSO, CMAES: state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
  *   GLPSO, JDE21  : state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
+ *   MADDE, SDMSPSO: state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
  *   DEDQN         : state [4]      (dedqn_optimizer.py:130-142: fdc, rie, acf, nop), action [1] int32 (0 rand_1, 1 cur_to_rand_1, anything else best_2) */
 int mbx_state_dim(const mbx_algo_cfg* cfg);
 int mbx_action_dim(const mbx_algo_cfg* cfg);

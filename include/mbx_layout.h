@@ -568,6 +568,80 @@
 #define MBX_SITE_DD_NOISE_A  40u
 #define MBX_SITE_DD_NOISE_B  41u
 
+/* ---------------------------------------------------------------- 15. sDMS_PSO (sdms_pso.py) layouts
+ * No agent: mbx_reset is __reset (:68-85: random swarm, one evaluation, regroup by a random permutation, lbest per sub-swarm -- NP FEs), every
+ * mbx_step (actions = NULL) is one __update (:135-183, NP FEs) plus, in the launch of a generation's tenth update, the generation's epilogue
+ * (:220-226: parameter-set push, every tenth generation a regroup with lbest from scratch) and the zeroing of success_num for the next
+ * generation.  NP = 99 in 33 sub-swarms of 3 (particle i belongs to sub-swarm i / 3), c1 = c2 = 1.49445, velocity cap 0.1 (ub - lb).
+ * cfg.np must be 99, dim <= 40, and max_fes inside the range described at mbx_batch_create's check.  state [1] = fes / maxFEs.
+ * state block: X[NP*D] V[NP*D] pbest_pos[NP*D] c_cost[NP] pbest[NP] lbest_pos[33*D] gbest_pos[D] lbest_cost[33] lbest_index[33] success_num[33]
+ *   success_last[33] iwt[33] iwt_z[33] parameter_set[8] scalars[16] cost_curve[nlog+1].
+ *   success_last:  success_num as the last parameter-set push saw it (success_num itself is zero again after that launch).
+ *   iwt / iwt_z:   the inertia weights of the last local-phase update, and the standard normals behind them when they were drawn from
+ *                  normal(median(parameter_set), 0.1) (diagnostic: the Philox route makes them with the device's log / cos, which the host does
+ *                  not reproduce to the bit; a tape rebuilt from a Philox step takes them from here).
+ *   parameter_set: oldest entry first, scalars[MBX_SC_SDMS_NPAR] entries in use (a FIFO of 8).
+ *   scalars beyond the common ones (MBX_SC_GEN counts the updates; it is the Philox generation word): the position inside the learning period
+ *   (0..9, the number of updates of the running generation already made), the mode (0 local phase, 1 global phase), the inertia weight w of the
+ *   global phase, the parameter-set count, how the last update drew iwt (0 uniform, 1 normal, 2 global phase: not drawn), the reference's `gen`.
+ * tape per reset: pos_u[NP*D] | vel_u[NP*D] | noise[3*NP] | perm[NP]
+ * tape per step:  rand1[NP] | rand2[NP] | iwt_u[33] | iwt_z[33] | noise[3*NP] | perm[NP]
+ *   iwt_u is read when __get_iwt draws uniforms, iwt_z (STANDARD normals; the kernel forms median + 0.1 z) when it draws normals, neither in the
+ *   global phase; perm (torch.randperm values as doubles, clamped to [0, NP)) in the step that ends a generation whose number is a multiple of 10.
+ * Philox, counter (index, site, gen, episode); reset gen = 0, step gen = number of the step:
+ *   MBX_SITE_ELEM_R(e)        reset: u53(w0,w1) = pos_u, u53(w2,w3) = vel_u
+ *   MBX_SITE_SD_PART(i)       u53(w0,w1) = rand1, u53(w2,w3) = rand2
+ *   MBX_SITE_SD_IWT_U(s)      u53(w0,w1) = iwt_u            MBX_SITE_SD_IWT_Z(s)  Box-Muller of u53(w0,w1), u53(w2,w3): the cosine half = iwt_z
+ *   MBX_SITE_SD_PERM(i)       w0 = the key of row i; perm[i] = the rank of key i among the NP keys (equal keys: the lower index first)
+ *   MBX_SITE_SD_NOISE_A/B(i)  evaluation of row i (reset and step)                                                                              */
+#define MBX_SDMS_NP   99
+#define MBX_SDMS_M    3
+#define MBX_SDMS_NS   33
+#define MBX_SDMS_LP   10
+#define MBX_SDMS_LA   8
+#define MBX_SDMS_R    10
+#define MBX_SDMS_L    100
+#define MBX_SDMS_DIM_MAX 40
+#define MBX_SDMS_TAPE_POS(NP, D)         ((int64_t)0)
+#define MBX_SDMS_TAPE_VEL(NP, D)         ((int64_t)(NP) * (D))
+#define MBX_SDMS_TAPE_NOISE_INIT(NP, D)  (2 * (int64_t)(NP) * (D))
+#define MBX_SDMS_TAPE_PERM_INIT(NP, D)   (2 * (int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_SDMS_TAPE_RAND1(NP, D)       ((int64_t)0)
+#define MBX_SDMS_TAPE_RAND2(NP, D)       ((int64_t)(NP))
+#define MBX_SDMS_TAPE_IWT_U(NP, D)       (2 * (int64_t)(NP))
+#define MBX_SDMS_TAPE_IWT_Z(NP, D)       (2 * (int64_t)(NP) + MBX_SDMS_NS)
+#define MBX_SDMS_TAPE_NOISE(NP, D)       (2 * (int64_t)(NP) + 2 * MBX_SDMS_NS)
+#define MBX_SDMS_TAPE_PERM(NP, D)        (5 * (int64_t)(NP) + 2 * MBX_SDMS_NS)
+#define MBX_SDMS_TAPE_STRIDE(NP, D)      (2 * (int64_t)(NP) * (D) + 4 * (int64_t)(NP))
+#define MBX_SDMS_ST_X(NP, D)             ((int64_t)0)
+#define MBX_SDMS_ST_V(NP, D)             ((int64_t)(NP) * (D))
+#define MBX_SDMS_ST_PBPOS(NP, D)         (2 * (int64_t)(NP) * (D))
+#define MBX_SDMS_ST_CCOST(NP, D)         (3 * (int64_t)(NP) * (D))
+#define MBX_SDMS_ST_PBEST(NP, D)         (3 * (int64_t)(NP) * (D) + (NP))
+#define MBX_SDMS_ST_LBPOS(NP, D)         (3 * (int64_t)(NP) * (D) + 2 * (int64_t)(NP))
+#define MBX_SDMS_ST_GBPOS(NP, D)         (MBX_SDMS_ST_LBPOS(NP, D) + (int64_t)MBX_SDMS_NS * (D))
+#define MBX_SDMS_ST_LBCOST(NP, D)        (MBX_SDMS_ST_GBPOS(NP, D) + (D))
+#define MBX_SDMS_ST_LBIDX(NP, D)         (MBX_SDMS_ST_LBCOST(NP, D) + MBX_SDMS_NS)
+#define MBX_SDMS_ST_SUCC(NP, D)          (MBX_SDMS_ST_LBIDX(NP, D) + MBX_SDMS_NS)
+#define MBX_SDMS_ST_SUCC_LAST(NP, D)     (MBX_SDMS_ST_SUCC(NP, D) + MBX_SDMS_NS)
+#define MBX_SDMS_ST_IWT(NP, D)           (MBX_SDMS_ST_SUCC_LAST(NP, D) + MBX_SDMS_NS)
+#define MBX_SDMS_ST_IWT_Z(NP, D)         (MBX_SDMS_ST_IWT(NP, D) + MBX_SDMS_NS)
+#define MBX_SDMS_ST_PSET(NP, D)          (MBX_SDMS_ST_IWT_Z(NP, D) + MBX_SDMS_NS)
+#define MBX_SDMS_ST_SCALARS(NP, D)       (MBX_SDMS_ST_PSET(NP, D) + MBX_SDMS_LA)
+#define MBX_SDMS_STATE_DOUBLES(NP, D, NLOG) (MBX_SDMS_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)
+#define MBX_SC_SDMS_STEP     10
+#define MBX_SC_SDMS_MODE     11
+#define MBX_SC_SDMS_W        12
+#define MBX_SC_SDMS_NPAR     13
+#define MBX_SC_SDMS_IWTMODE  14
+#define MBX_SC_SDMS_GEN      15
+#define MBX_SITE_SD_PART     42u
+#define MBX_SITE_SD_IWT_U    43u
+#define MBX_SITE_SD_IWT_Z    44u
+#define MBX_SITE_SD_PERM     45u
+#define MBX_SITE_SD_NOISE_A  46u
+#define MBX_SITE_SD_NOISE_B  47u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

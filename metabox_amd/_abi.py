@@ -66,6 +66,7 @@ ALGO_RLEPSO, ALGO_LDE, ALGO_DEDDQN, ALGO_RANDOM_SEARCH, ALGO_RLPSO, ALGO_GLEET, 
 ALGO_GLPSO = 11
 ALGO_JDE21 = 13      # (12 is not assigned)
 ALGO_MADDE = 15      # (14 is not assigned)
+ALGO_SDMSPSO = 18    # (17 is not assigned)
 ALGO_DEDQN = 16
 POLICY_RLEPSO, POLICY_RLPSO = 0, 1
 _ARRAY_FIELDS = ('dshift', 'm1', 'm2', 'v0', 'v1', 'v2', 'py', 'pc', 'pw')

@@ -35,6 +35,7 @@
 #include "mbx_glpso.hpp"
 #include "mbx_jde21.hpp"
 #include "mbx_madde.hpp"
+#include "mbx_sdmspso.hpp"
 // k_rlepso_run / k_lde_run are compiled in translation units of their own (mbx_run_rlepso.hip, mbx_run_lde.hip) and only declared here;
 // -DMBX_SINGLE_TU (instrumented builds: the phase counters are a __device__ array, one copy per translation unit) instantiates them in this file instead
 #ifndef MBX_SINGLE_TU
@@ -182,6 +183,12 @@ static AlgoGeom geom_of(const mbx_algo_cfg& c)
         g.sc_off = MBX_MADDE_ST_SCALARS(c.np, c.dim);
         g.tape_stride = MBX_MADDE_TAPE_STRIDE(c.np, c.dim);
         g.lds_doubles = md_lds_doubles(c.np, c.dim);
+        g.state_dim = 1; g.action_dim = 0;
+    } else if (c.algo == MBX_ALGO_SDMSPSO) {
+        g.state_doubles = MBX_SDMS_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
+        g.sc_off = MBX_SDMS_ST_SCALARS(c.np, c.dim);
+        g.tape_stride = MBX_SDMS_TAPE_STRIDE(c.np, c.dim);
+        g.lds_doubles = sd_lds_doubles(c.np, c.dim);
         g.state_dim = 1; g.action_dim = 0;
     } else if (c.algo == MBX_ALGO_DEDQN) {
         g.state_doubles = MBX_DEDQN_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
@@ -479,14 +486,24 @@ extern "C" int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, dou
 static int check_cfg(const mbx_algo_cfg* c)
 {
     if (!c) return fail(MBX_E_ARG, "null cfg");
-    // the ids this build has kernels for (12 and 14 are not assigned)
-    if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21 || c->algo == MBX_ALGO_MADDE || c->algo == MBX_ALGO_DEDQN))
+    // the ids this build has kernels for (12, 14 and 17 are not assigned)
+    if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21 || c->algo == MBX_ALGO_MADDE || c->algo == MBX_ALGO_DEDQN ||
+          c->algo == MBX_ALGO_SDMSPSO))
         return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
     if (c->algo == MBX_ALGO_JDE21 && c->np != MBX_JDE21_NP) return fail(MBX_E_ARG, "JDE21 runs np = %d (160 + 10 rows), not %d", MBX_JDE21_NP, c->np);
     if (c->algo == MBX_ALGO_MADDE) {
         // the one algorithm whose rows are strided over the lanes: np is 2 dim^2, and LDS is sized for at most 3200 rows
         if (c->dim < 2 || c->dim > MBX_MADDE_DIM_MAX) return fail(MBX_E_ARG, "MadDE runs dim in [2, %d], not %d", MBX_MADDE_DIM_MAX, c->dim);
         if (c->np != MBX_MADDE_NP(c->dim)) return fail(MBX_E_ARG, "MadDE runs np = 2 dim^2 = %d, not %d", MBX_MADDE_NP(c->dim), c->np);
+    } else if (c->algo == MBX_ALGO_SDMSPSO) {
+        // 33 sub-swarms of 3; the reference's generation 100 would call __quasi_Newton, which fails in the reference itself (sdms_pso.py:198 reads
+        // self.__problem, never assigned) and is not built here; with max_fes <= np the reference returns without its final log entry
+        if (c->np != MBX_SDMS_NP) return fail(MBX_E_ARG, "sDMS_PSO runs np = %d (33 sub-swarms of 3), not %d", MBX_SDMS_NP, c->np);
+        if (c->dim < 2 || c->dim > MBX_SDMS_DIM_MAX) return fail(MBX_E_ARG, "sDMS_PSO runs dim in [2, %d], not %d", MBX_SDMS_DIM_MAX, c->dim);
+        if (c->max_fes <= MBX_SDMS_NP) return fail(MBX_E_ARG, "sDMS_PSO needs max_fes > %d (the initial evaluation), not %d", MBX_SDMS_NP, c->max_fes);
+        if (sd_local_generations(c->max_fes) >= MBX_SDMS_L)
+            return fail(MBX_E_ARG, "sDMS_PSO: with max_fes %d the local phase reaches generation %d, where the reference calls its quasi-Newton refinement "
+                                   "(and fails in it); not built", c->max_fes, MBX_SDMS_L);
     } else if (c->algo == MBX_ALGO_DEDQN) {
         // the landscape analysis deals one row per lane of two waves, and LDS holds the population three times over
         if (c->np < 4 || c->np > MBX_DEDQN_NP_MAX) return fail(MBX_E_ARG, "DEDQN runs np in [4, %d], not %d", MBX_DEDQN_NP_MAX, c->np);
@@ -701,6 +718,9 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
     } else if (cfg->algo == MBX_ALGO_MADDE) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_madde_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_madde_generation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    } else if (cfg->algo == MBX_ALGO_SDMSPSO) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_sdmspso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_sdmspso_update, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     } else if (cfg->algo == MBX_ALGO_DEDQN) {
         HIP_TRY(dedqn_prepare(lds));
         {   // cal_rie's frequencies are n / NP: their logarithms, correctly rounded (extended precision, then one rounding to double), so that the kernel's
@@ -824,6 +844,8 @@ extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
         hipLaunchKernelGGL(k_jde21_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_MADDE)
         hipLaunchKernelGGL(k_madde_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
+    else if (b->cfg.algo == MBX_ALGO_SDMSPSO)
+        hipLaunchKernelGGL(k_sdmspso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_DEDQN)
         dedqn_launch_reset(make_params(b), b->lds_bytes, (hipStream_t)stream, d_state_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
@@ -852,7 +874,7 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
 {
     const bool no_agent = b && (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH || b->cfg.algo == MBX_ALGO_DE || b->cfg.algo == MBX_ALGO_PSO ||
                                 b->cfg.algo == MBX_ALGO_CMAES || b->cfg.algo == MBX_ALGO_GLPSO || b->cfg.algo == MBX_ALGO_JDE21 ||
-                                b->cfg.algo == MBX_ALGO_MADDE);
+                                b->cfg.algo == MBX_ALGO_MADDE || b->cfg.algo == MBX_ALGO_SDMSPSO);
     if (!b || (!d_actions && !no_agent)) return fail(MBX_E_ARG, "mbx_step: bad arguments");
     if (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH)
         hipLaunchKernelGGL(k_rs_population, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), 0, d_state_out,
@@ -879,6 +901,9 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
                            d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_MADDE)
         hipLaunchKernelGGL(k_madde_generation, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
+                           d_reward_out, d_done_out);
+    else if (b->cfg.algo == MBX_ALGO_SDMSPSO)
+        hipLaunchKernelGGL(k_sdmspso_update, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
                            d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_DEDQN)
         dedqn_launch_step(make_params(b), b->lds_bytes, (hipStream_t)stream, (const int32_t*)d_actions, d_state_out, d_reward_out, d_done_out);

@@ -12,3 +12,4 @@ from .classic import DEAP_CMAES, DEAP_DE, DEAP_PSO
 from .gl_pso import GL_PSO
 from .jde21 import JDE21
 from .madde import MadDE
+from .sdms_pso import sDMS_PSO

@@ -1899,7 +1899,175 @@ def gen_dedqn():
     print('dedqn train: batch', batches[0][0].shape, 'done in batch', batches[0][4].sum())
 
 
-SECTIONS = {'dedqn': gen_dedqn, 'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+def run_sdmspso_episode(problem, config):
+    """One reference sDMS_PSO episode on the global numpy and torch streams (the caller seeds both), driven by hand through the private
+    methods in run_episode's own order (src/optimizer/sdms_pso.py:207-243).  Row 0 of every per-update array is the state after __reset,
+    row u the state after __update number u -- and, for the tenth update of a generation, after the generation's epilogue (parameter-set
+    push, regroup), which is what one kernel launch covers.  `c_cost` is the exception: the new costs in the order the update computed
+    them, before any regroup.  `iwt_mode`: 0 uniform, 1 normal, 2 global phase (row 0: 0).  Per generation (row g - 1 = generation g):
+    parameter_set after the push (padded with NaN), w, success_num as the push saw it.  `perms`: every torch.randperm, the reset's first.
+    Snapshots of position / velocity / pbest position after reset, after the first update, after every regroup and at the end."""
+    from optimizer import sDMS_PSO
+    import copy
+    opt = sDMS_PSO(copy.deepcopy(config))
+    problem.reset()
+    get = lambda name: getattr(opt, '_sDMS_PSO__' + name)             # noqa: E731
+    put = lambda name, v: setattr(opt, '_sDMS_PSO__' + name, v)       # noqa: E731
+    NP, max_fes = 99, config.maxFEs
+    rec = dict(gbest=[], fes=[], pbest=[], lbest_cost=[], lbest_index=[], success_num=[], iwt=[], iwt_mode=[], c_cost=[])
+    gens = dict(parameter_set=[], w=[], success_end=[])
+    perms, snaps, snap_at = [], [], []
+
+    def snap(mode, c_cost=None):
+        pt = get('particles')
+        rec['gbest'].append(float(pt['gbest_val']))
+        rec['fes'].append(float(get('fes')))
+        rec['pbest'].append(np.array(pt['pbest'], dtype=np.float64))
+        rec['lbest_cost'].append(np.array(pt['lbest_cost'], dtype=np.float64))
+        rec['lbest_index'].append(np.array(get('lbest_index')).astype(np.int16))
+        rec['success_num'].append(np.array(get('success_num')).astype(np.int16))
+        rec['iwt'].append(np.array(get('iwt'), dtype=np.float64) if hasattr(opt, '_sDMS_PSO__iwt') else np.zeros(33))
+        rec['iwt_mode'].append(mode)
+        rec['c_cost'].append(np.array(pt['c_cost'] if c_cost is None else c_cost, dtype=np.float64))
+
+    def full():
+        pt = get('particles')
+        snaps.append(np.stack([pt['current_position'], pt['velocity'], pt['pbest_position']]).astype(np.float64))
+        snap_at.append(len(rec['gbest']) - 1)
+
+    def update(mode_name):
+        put('cur_mode', mode_name)
+        if mode_name == 'gs':
+            mode = 2
+        else:
+            mode = 0 if len(get('parameter_set')) < 8 or np.sum(get('success_num')) <= 10 else 1
+        getattr(opt, '_sDMS_PSO__update')(problem)
+        return mode, np.array(get('particles')['c_cost'], dtype=np.float64)
+
+    getattr(opt, '_sDMS_PSO__reset')(problem)
+    perms.append(get('regroup_index').numpy().astype(np.int16))
+    snap(0)
+    full()
+    while get('fes') < max_fes:
+        while get('fes') < 0.95 * max_fes:
+            put('gen', get('gen') + 1)
+            put('w', get('w') - 0.5 / (max_fes / NP))
+            ok = get('success_num'); ok -= ok
+            for j in range(10):
+                mode, cc = update('ls')
+                if j < 9:
+                    snap(mode)
+                    if len(rec['gbest']) == 2:
+                        full()
+            gens['success_end'].append(np.array(get('success_num')).astype(np.int16))
+            getattr(opt, '_sDMS_PSO__update_parameter_set')()
+            assert get('gen') % 100 != 0, 'the quasi-Newton generation is out of range of this build'
+            regroup = get('gen') % 10 == 0
+            if regroup:
+                getattr(opt, '_sDMS_PSO__random_regroup')()
+                getattr(opt, '_sDMS_PSO__update_lbest')(init=True)
+                perms.append(get('regroup_index').numpy().astype(np.int16))
+            snap(mode, cc)
+            if regroup:
+                full()
+            ps = np.full(8, np.nan)
+            ps[:len(get('parameter_set'))] = get('parameter_set')
+            gens['parameter_set'].append(ps)
+            gens['w'].append(float(get('w')))
+        while get('fes') < max_fes:
+            mode, _ = update('gs')
+            snap(mode)
+        if len(opt.cost) >= config.n_logpoint + 1:
+            opt.cost[-1] = get('particles')['gbest_val']
+        else:
+            opt.cost.append(get('particles')['gbest_val'])
+    if snap_at[-1] != len(rec['gbest']) - 1:
+        full()
+    out = {k: np.stack(v) if np.ndim(v[0]) else np.array(v) for k, v in rec.items()}
+    out['iwt_mode'] = out['iwt_mode'].astype(np.int8)
+    out.update({'gen_' + k: np.stack(v) if np.ndim(v[0]) else np.array(v) for k, v in gens.items()})
+    out['perms'] = np.stack(perms)
+    out['snaps'] = np.stack(snaps)
+    out['snap_at'] = np.array(snap_at, dtype=np.int32)
+    out['cost'] = np.array([float(c) for c in opt.cost], dtype=np.float64)
+    return out
+
+
+def gen_sdmspso():
+    """sDMS_PSO (src/optimizer/sdms_pso.py): seeded reference episodes (np.random.seed(s); torch.manual_seed(s)), recorded per update
+    (run_sdmspso_episode).  The numpy draws are NOT stored: the tests regenerate them from the seed in the reference's draw order; the
+    permutations come from torch's stream and are stored.  The cases at maxFEs = 10000 take the first seed, counted up from the one listed,
+    whose episode reaches the normal-draw mode of __get_iwt.  The arrays are spread over sdmspso_traces.npz, sdmspso_traces_b.npz, ... so that
+    no file exceeds 1 MiB; the tests read them all."""
+    scratch = tempfile.mkdtemp()
+    data, cases, owner = {}, [], {}
+
+    def config_for(suite, dim, max_fes, log_interval=None):
+        argv = ['--problem', suite] + ([] if suite == 'protein' else ['--dim', str(dim)])
+        config = ref_import.ref_config(argv, scratch)
+        config.maxFEs = max_fes
+        config.log_interval = log_interval or max_fes // config.n_logpoint
+        return config
+
+    def episode(problem, config, seed):
+        np.random.seed(seed)
+        torch.manual_seed(seed)
+        return run_sdmspso_episode(problem, config)
+
+    def put(key, rec, config):
+        cases.append(key)
+        for k, v in rec.items():
+            data[f'{key}/{k}'] = v
+        data[f'{key}/max_fes'] = np.float64(config.maxFEs)
+        data[f'{key}/log_interval'] = np.float64(config.log_interval)
+        data[f'{key}/n_logpoint'] = np.float64(config.n_logpoint)
+        data[f'{key}/next_rand'] = np.float64(np.random.rand())      # stream position after the episode
+        print(key, len(rec['gbest']) - 1, rec['fes'][-1], rec['gbest'][-1], len(rec['cost']), np.bincount(rec['iwt_mode'], minlength=3), len(rec['perms']))
+
+    # (suite, dim, function, first seed to try, maxFEs, log_interval or None, the normal-draw mode must occur)
+    jobs = [('bbob', 10, 1, 81, 20000, None, False), ('bbob', 10, 15, 82, 20000, None, False),
+            ('bbob', 10, 1, 83, 10000, None, True), ('bbob', 10, 5, 84, 10000, None, True), ('bbob', 10, 10, 85, 10000, None, True),
+            ('bbob', 10, 24, 86, 10000, None, True), ('bbob', 30, 8, 87, 10000, None, True),
+            ('bbob', 10, 3, 88, 2000, 40, False),
+            ('bbob-noisy', 10, 101, 89, 6000, None, False), ('bbob-noisy', 10, 102, 90, 6000, None, False), ('bbob-noisy', 10, 103, 91, 6000, None, False)]
+    problems = {}
+    for suite, dim, fid, seed, max_fes, log_interval, need_normal in jobs:
+        if (suite, dim) not in problems:
+            tr, te, _ = all_problems(suite, dim)
+            problems[(suite, dim)] = {fid_of(p): p for p in tr + te}
+        config = config_for(suite, dim, max_fes, log_interval)
+        for seed in range(seed, seed + 1000, 100):
+            rec = episode(problems[(suite, dim)][fid], config, seed)
+            if not need_normal or (rec['iwt_mode'] == 1).any():
+                break
+        else:
+            raise AssertionError((suite, dim, fid, 'no seed reaches the normal-draw mode'))
+        put(f'{suite}/{dim}/{fid}/{seed}', rec, config)
+    byid, _, _ = protein_problems()
+    config = config_for('protein', 12, 1000)
+    put('protein/12/1ATN_7/92', episode(byid['1ATN_7'], config, 92), config)
+    data['cases'] = np.array(cases)
+    parts, sizes = [], []
+    for key in data:
+        prefix = '/'.join(key.split('/')[:4])
+        if prefix not in owner:
+            need = sum(data[k].nbytes for k in data if '/'.join(k.split('/')[:4]) == prefix)
+            for n in range(len(parts) + 1):
+                if n == len(parts):
+                    parts.append({}); sizes.append(0)
+                if sizes[n] + need <= 900 * 1024:
+                    break
+            owner[prefix] = n
+            sizes[n] += need
+        parts[owner[prefix]][key] = data[key]
+    for n, d in enumerate(parts):
+        path = os.path.join(OUT, 'sdmspso_traces%s.npz' % ('' if n == 0 else '_' + 'abcdefgh'[n]))
+        np.savez_compressed(path, **d)
+        print(os.path.basename(path), os.path.getsize(path))
+        assert os.path.getsize(path) < 1000 * 1000
+
+
+SECTIONS = {'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -248,3 +248,31 @@ if 'dedqn' in which:
         print(json.dumps({'path': f'k_dedqn_run bbob d={dim} NP=100, {B} instances, 32 env steps per launch, Q-network in the kernel', 'us_per_step': dt / 96 * 1e6,
                           'ns_per_row': dt / 96 / (101 * B) * 1e9}))
         b.close()
+if 'sdmspso' in which:
+    # sDMS_PSO (one mbx_step = one update: 99 evaluated rows) next to GL-PSO (one generation: 200 evaluated rows and the exemplar breeding) in the
+    # same process, alternating: bbob round-robin, 4096 instances, every instance live for the whole window (sDMS_PSO has no early stop; its
+    # budget of 100 000 keeps it in the local phase, and the window of 3 + 7 x 40 updates meets two regroups).  Median of 7 windows of 40 steps,
+    # each ended by a device synchronise; the wall times include the launch gaps.
+    from metabox_amd._abi import ALGO_GLPSO, ALGO_SDMSPSO
+    from metabox_amd.suite import Batch, Suite
+    for dim in (10, 30):
+        cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+        tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+        s = Suite(ps); B = 4096
+        jobs = {'k_sdmspso_update': (Batch(s, ALGO_SDMSPSO, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, 99, 100000, 2000, 50), 99),
+                'k_glpso_generation': (Batch(s, ALGO_GLPSO, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, 100, 10 ** 8, 10 ** 6, 50, early_stop=False), 200)}
+        times = {k: [] for k in jobs}
+        for b, _ in jobs.values():
+            b.reset()
+            for _ in range(3): b.step(None)
+        for rep in range(7):
+            for name, (b, _) in jobs.items():
+                def run(n):
+                    for _ in range(n): b.step(None)
+                times[name].append(timed(run, 40) / 40)
+        for name, (b, rows) in jobs.items():
+            t = float(np.median(times[name]))
+            assert int((b.results()['steps'] > 0).sum()) == B and not bool(b.done.any())
+            print(json.dumps({'path': f'{name} bbob d={dim}, {B} instances, one launch per step', 'ms_per_step_median': t * 1e3, 'ms_per_step_min_max': [min(times[name]) * 1e3, max(times[name]) * 1e3],
+                              'rows_per_step': rows, 'row_evaluations_per_s': rows * B / t, 'launch_info': b.launch_info()}))
+            b.close()
