@@ -111,6 +111,7 @@ int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, double* d_f,
 #define MBX_ALGO_MADDE  15  /* src/optimizer/madde.py              one step = one update (NP FEs), np = 2 dim^2, dim <= 40 -- classic baseline, no agent (12 and 14 are not assigned and stay rejected) */
 #define MBX_ALGO_SDMSPSO 18 /* src/optimizer/sdms_pso.py           one step = one update (NP FEs), np = 99, dim <= 40, max_fes in (99, 103272] -- classic baseline, no agent (12, 14 and 17 are not assigned and stay rejected) */
 #define MBX_ALGO_DEDQN  16  /* src/optimizer/dedqn_optimizer.py     one step = one trial vector + the landscape analysis (2 NP FEs), np in [4, 128], dim <= 40 */
+#define MBX_ALGO_NRLPSO 19  /* src/optimizer/nrlpso_optimizer.py    one step = one particle (1 FE, 3 when the neighbourhood mutation fires), np in [8, 128], dim <= 40 */
 
 typedef struct mbx_algo_cfg {
     int32_t algo;          /* MBX_ALGO_*                                                          */
@@ -132,11 +133,14 @@ typedef struct mbx_algo_cfg {
  *                                first-index rule -- the exemplar index is the reference's on any input (tests/test_fdr_ties.py) at +3..5 % of a generation.
  *   MBX_F_GENERIC_GEOMETRY       keep the run-time-geometry kernels where a compile-time-geometry instantiation exists (the tests compare the two bit for bit)
  *   MBX_F_ROLLOUT_PER_GENERATION the mbx_*_rollout entry points step one launch per generation instead of the resident kernel (same outputs)
+ *   MBX_F_NRLPSO_RECOMPUTE       NRLPSO: every cal_ef (nrlpso_optimizer.py:110-122) computes the NP x NP distances from scratch instead of refreshing one row and
+ *                                one column of a matrix kept in LDS (bit-identical; also what runs where the matrix does not fit the LDS)
  * Test override: the environment variables MBX_FDR_FAST=1, MBX_GENERIC_GEOMETRY=1, MBX_ROLLOUT_PER_GENERATION=1 are OR-ed into the flags of every batch
  * created while they are set (read once, inside mbx_batch_create; never at call time). */
 #define MBX_F_FDR_FAST               1u
 #define MBX_F_GENERIC_GEOMETRY       2u
 #define MBX_F_ROLLOUT_PER_GENERATION 4u
+#define MBX_F_NRLPSO_RECOMPUTE       8u
 /* the flags a batch was created with, environment overrides included (negative = MBX_E_*) */
 int mbx_batch_flags(const mbx_batch* b);
 
@@ -151,7 +155,8 @@ int mbx_batch_flags(const mbx_batch* b);
  *   DE, PSO, CMAES: state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
  *   GLPSO, JDE21  : state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
  *   MADDE, SDMSPSO: state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
- *   DEDQN         : state [4]      (dedqn_optimizer.py:130-142: fdc, rie, acf, nop), action [1] int32 (0 rand_1, 1 cur_to_rand_1, anything else best_2) */
+ *   DEDQN         : state [4]      (dedqn_optimizer.py:130-142: fdc, rie, acf, nop), action [1] int32 (0 rand_1, 1 cur_to_rand_1, anything else best_2)
+ *   NRLPSO        : state [1]      (nrlpso_optimizer.py:58-59, 278-296),    action [1] int32 in {0..3} */
 int mbx_state_dim(const mbx_algo_cfg* cfg);
 int mbx_action_dim(const mbx_algo_cfg* cfg);
 /* number of doubles of external random numbers one instance consumes per step (see mbx_set_tape) */
@@ -376,6 +381,18 @@ typedef struct mbx_dedqn_net {
 } mbx_dedqn_net;
 int mbx_dedqn_rollout(mbx_batch* b, const mbx_dedqn_net* net, int n_steps, int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward,
                       int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream);
+
+/* NRLPSO with its tabular policy inside the step kernel, `n_steps` env steps per launch: the loop of NRLPSO_Agent.rollout_episode
+ * (src/agent/nrlpso_agent.py:63-72) with __get_action (:28-31: softmax over the Q-row of the state, np.random.choice) evaluated on the device, while
+ * the population, the pbest positions and (unless MBX_F_NRLPSO_RECOMPUTE is set or it does not fit) the NP x NP distance matrix stay in LDS from
+ * step to step.  n_steps one-step calls, one n_steps call, and mbx_step fed the recorded actions leave bit-identical state blocks.  d_q_table is
+ * [4, 4] float64 (states x actions).  With a replay tape n_steps must be 1; the choice uniform then comes from the tape.
+ * Per-step records, each may be NULL (rows of steps after an instance's termination are not written):
+ *   d_traj_actions [n_steps, n_instances] int32, d_traj_state [n_steps, n_instances] float64 (the state AFTER the step), d_traj_reward likewise.
+ * d_actions_out [n_instances] int32: the last action taken; d_state_out [n_instances] / d_done_out: state / is_done after the last executed step;
+ * d_reward_out: SUM of the rewards of the executed steps. */
+int mbx_nrlpso_rollout(mbx_batch* b, const double* d_q_table, int n_steps, int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward,
+                       int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream);
 
 /* Test / diagnostics: apply one of the device math routines the objectives are built from to n device values.
  * op: 0 log, 1 exp, 2 sin, 3 cos, 4 pow(x, y), 5 T_osz(x) (bbob.py:51-67), 6 T_asy(x; beta_lin = y) (bbob.py:70-82). */

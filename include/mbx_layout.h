@@ -642,6 +642,89 @@
 #define MBX_SITE_SD_NOISE_A  46u
 #define MBX_SITE_SD_NOISE_B  47u
 
+/* ---------------------------------------------------------------- 16. NRLPSO (nrlpso_optimizer.py) layouts
+ * One env step = ONE particle of the round-robin `pointer` (reset to 0 by init_population, :31).  k = 5 neighbours, v_max = 0.1 (ub - lb),
+ * w from the logistic map r_w once per sweep (:88-93, at pointer == 0, with the fes of that moment).  state [1] = the action the next particle took on
+ * its previous turn (:278-296; the reset draws randint(0, 4, NP), :58); action [1] int32 in 0..3 (any other value leaves the velocity as it is, :145-191);
+ * reward in {2, 1, 0, -2} from (f_new < f_old, ef_new > ef_old) (:95-108).  A step bills 1 FE, or 3 when pbest_stag_count[pointer] >= 2 fires
+ * neb_mutation (:271-272), so fes may pass maxFEs by up to 2 and the curve still appends at most once per step (:282-284).
+ * The reference's own behaviour, kept:
+ *   gbest_pos is a numpy VIEW of population row MBX_SC_NRLPSO_G0 while MBX_SC_NRLPSO_ALIAS is 1: after init_population (:47) and after :276, and it
+ *     follows that row when the row moves or a mutation overwrites it (:220, :238); it becomes an array of its own (gbest_pos[D], alias 0) only when
+ *     neb_mutation improves gbest (:233).
+ *   pbest_cost is not written when a particle improves on it (:265-267 write the position only); only neb_mutation writes it (:216).
+ *   pbest_stag_count is not reset by a mutation (:271): once it reaches 2 every later turn of that particle mutates until the particle improves.
+ *   pbest_neb / gbest_neb are COPIES taken at pointer == 0 (:75, :84) and go stale within the sweep, while their index lists overwrite LIVE rows
+ *     (:219-221, :237-239): the block keeps the sweep-start population `snap` and the index lists, not the NP x k x D rows.
+ *   action 3 draws its two random indices and then two rand(D) vectors; the scalars r1, r2 are drawn first all the same and ignored (:138-139, :184-191).
+ *   neighbours are chosen by (distance, index); the diagonal of the pbest-to-particle matrix is +inf (:68); a NaN cs or ef compares false.
+ * state block: pop[NP*D] vel[NP*D] pbest_pos[NP*D] snap[NP*D] cost[NP] pbest_cost[NP] stag[NP] sstate[NP] pbest_neb_index[NP*5] gbest_neb_index[8]
+ *   gbest_pos[D] diag[8] scalars[16] cost_curve[nlog+1].
+ *   diag (of the last step): cs | ef_old | ef_new | mutated (0 / 1) | f_new | cost of the pbest mutation | cost of the gbest mutation | action
+ * tape per reset: pos_u[NP*D] | noise_init[3*NP] | sstate[NP] | r_w
+ * tape per step:  r1 | r2 | idx_b | idx_a | noise[9] | choice_u | r1v[D] | r2v[D] | mut_u1[D] | mut_u2[D]
+ *   idx_b / idx_a: the randint(0, k) of get_p_b / get_p_a as doubles (read only where the action and the sign of cs call them); noise: [3][3] rows
+ *   (a | b | c) x (the move's evaluation, the pbest mutation's, the gbest mutation's); choice_u: the uniform of the agent's np.random.choice (fused
+ *   policy only); r1v / r2v: action 3; mut_u1 / mut_u2: neb_mutation's rand(D) (:212, :230).
+ * Philox, counter (index, site, gen, episode); reset gen = 0, step gen = number of the step:
+ *   reset: MBX_SITE_LDE_ELEM(e): u53(w0,w1) = pos_u; noise MBX_SITE_NOISE1_A/B(i); MBX_SITE_NR_INIT(i): mulhi(w0, 4) = sstate[i]; index NP: u53(w0,w1) = r_w
+ *   MBX_SITE_NR_PART(0)    u53(w0,w1) = r1, u53(w2,w3) = r2;  index 1: mulhi(w0, 5) = idx_b, mulhi(w1, 5) = idx_a
+ *   MBX_SITE_NR_ELEM(d)    u53(w0,w1) = r1v[d], u53(w2,w3) = r2v[d]
+ *   MBX_SITE_NR_MUT(d)     u53(w0,w1) = mut_u1[d], u53(w2,w3) = mut_u2[d]
+ *   MBX_SITE_NR_NOISE_A/B(j)  evaluation j of the step: 0 the move, 1 the pbest mutation, 2 the gbest mutation
+ *   MBX_SITE_POLICY(0)     u53(w0,w1) = choice_u                                                                                              */
+#define MBX_NRLPSO_NP_MIN  8
+#define MBX_NRLPSO_NP_MAX  128
+#define MBX_NRLPSO_DIM_MAX 40
+#define MBX_NRLPSO_K       5
+#define MBX_NRLPSO_TAPE_POS(NP, D)        ((int64_t)0)
+#define MBX_NRLPSO_TAPE_NOISE_INIT(NP, D) ((int64_t)(NP) * (D))
+#define MBX_NRLPSO_TAPE_SSTATE(NP, D)     ((int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_NRLPSO_TAPE_RW(NP, D)         ((int64_t)(NP) * (D) + 4 * (int64_t)(NP))
+#define MBX_NRLPSO_TAPE_RAND(NP, D)       ((int64_t)0)
+#define MBX_NRLPSO_TAPE_IDX(NP, D)        ((int64_t)2)
+#define MBX_NRLPSO_TAPE_NOISE(NP, D)      ((int64_t)4)
+#define MBX_NRLPSO_TAPE_CHOICE(NP, D)     ((int64_t)13)
+#define MBX_NRLPSO_TAPE_R1V(NP, D)        ((int64_t)14)
+#define MBX_NRLPSO_TAPE_R2V(NP, D)        ((int64_t)14 + (D))
+#define MBX_NRLPSO_TAPE_MUT1(NP, D)       ((int64_t)14 + 2 * (D))
+#define MBX_NRLPSO_TAPE_MUT2(NP, D)       ((int64_t)14 + 3 * (D))
+#define MBX_NRLPSO_TAPE_STRIDE(NP, D)     ((int64_t)(NP) * (D) + 4 * (int64_t)(NP) + 16)     /* >= 14 + 4 D for np >= 8 */
+#define MBX_NRLPSO_ST_POP(NP, D)          ((int64_t)0)
+#define MBX_NRLPSO_ST_VEL(NP, D)          ((int64_t)(NP) * (D))
+#define MBX_NRLPSO_ST_PBPOS(NP, D)        (2 * (int64_t)(NP) * (D))
+#define MBX_NRLPSO_ST_SNAP(NP, D)         (3 * (int64_t)(NP) * (D))
+#define MBX_NRLPSO_ST_COST(NP, D)         (4 * (int64_t)(NP) * (D))
+#define MBX_NRLPSO_ST_PBCOST(NP, D)       (4 * (int64_t)(NP) * (D) + (NP))
+#define MBX_NRLPSO_ST_STAG(NP, D)         (4 * (int64_t)(NP) * (D) + 2 * (int64_t)(NP))
+#define MBX_NRLPSO_ST_SSTATE(NP, D)       (4 * (int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_NRLPSO_ST_PNIDX(NP, D)        (4 * (int64_t)(NP) * (D) + 4 * (int64_t)(NP))
+#define MBX_NRLPSO_ST_GNIDX(NP, D)        (MBX_NRLPSO_ST_PNIDX(NP, D) + (int64_t)MBX_NRLPSO_K * (NP))
+#define MBX_NRLPSO_ST_GBPOS(NP, D)        (MBX_NRLPSO_ST_GNIDX(NP, D) + 8)
+#define MBX_NRLPSO_ST_DIAG(NP, D)         (MBX_NRLPSO_ST_GBPOS(NP, D) + (D))
+#define MBX_NRLPSO_DIAG_SLOTS 8
+#define MBX_NRLPSO_ST_SCALARS(NP, D)      (MBX_NRLPSO_ST_DIAG(NP, D) + MBX_NRLPSO_DIAG_SLOTS)
+#define MBX_NRLPSO_STATE_DOUBLES(NP, D, NLOG) (MBX_NRLPSO_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)
+#define MBX_NRLPSO_DIAG_CS      0
+#define MBX_NRLPSO_DIAG_EF_OLD  1
+#define MBX_NRLPSO_DIAG_EF_NEW  2
+#define MBX_NRLPSO_DIAG_MUTATED 3
+#define MBX_NRLPSO_DIAG_FNEW    4
+#define MBX_NRLPSO_DIAG_PMCOST  5
+#define MBX_NRLPSO_DIAG_GMCOST  6
+#define MBX_NRLPSO_DIAG_ACTION  7
+#define MBX_SC_NRLPSO_POINTER 10
+#define MBX_SC_NRLPSO_G0      11
+#define MBX_SC_NRLPSO_ALIAS   12
+#define MBX_SC_NRLPSO_RW      13
+#define MBX_SC_NRLPSO_W       14
+#define MBX_SITE_NR_PART     48u
+#define MBX_SITE_NR_ELEM     49u
+#define MBX_SITE_NR_MUT      50u
+#define MBX_SITE_NR_NOISE_A  51u
+#define MBX_SITE_NR_NOISE_B  52u
+#define MBX_SITE_NR_INIT     53u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

@@ -34,7 +34,7 @@ class AlgoCfg(C.Structure):
 
 
 # mbx_algo_cfg.flags (include/mbx.h)
-F_FDR_FAST, F_GENERIC_GEOMETRY, F_ROLLOUT_PER_GENERATION = 1, 2, 4
+F_FDR_FAST, F_GENERIC_GEOMETRY, F_ROLLOUT_PER_GENERATION, F_NRLPSO_RECOMPUTE = 1, 2, 4, 8
 
 
 class GaussMlp(C.Structure):
@@ -68,6 +68,7 @@ ALGO_JDE21 = 13      # (12 is not assigned)
 ALGO_MADDE = 15      # (14 is not assigned)
 ALGO_SDMSPSO = 18    # (17 is not assigned)
 ALGO_DEDQN = 16
+ALGO_NRLPSO = 19
 POLICY_RLEPSO, POLICY_RLPSO = 0, 1
 _ARRAY_FIELDS = ('dshift', 'm1', 'm2', 'v0', 'v1', 'v2', 'py', 'pc', 'pw')
 
@@ -157,6 +158,7 @@ def load_lib():
         'mbx_rlpso_rollout': (C.c_int, [vp, C.POINTER(GaussMlp), C.c_int, vp, vp, vp, vp, vp]),
         'mbx_qlpso_rollout': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
         'mbx_dedqn_rollout': (C.c_int, [vp, C.POINTER(DedqnNet), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+        'mbx_nrlpso_rollout': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
         'mbx_gleet_policy': (C.c_int, [vp, C.POINTER(GleetActor), vp, vp, vp, vp]),
         'mbx_debug_math': (C.c_int, [C.c_int, vp, vp, vp, C.c_int, vp]),
         'mbx_debug_rlepso_draws': (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
@@ -184,7 +186,7 @@ EXPORTED_SYMBOLS = ('mbx_suite_create', 'mbx_suite_destroy', 'mbx_suite_size', '
                     'mbx_tape_stride', 'mbx_batch_create', 'mbx_batch_destroy', 'mbx_batch_flags', 'mbx_set_tape', 'mbx_reset', 'mbx_step', 'mbx_results',
                     'mbx_gauss_policy', 'mbx_lde_policy', 'mbx_ddqn_qnet', 'mbx_rlepso_policy_table_rows', 'mbx_rlepso_policy_table', 'mbx_rlepso_act_step',
                     'mbx_rlepso_rollout_resident', 'mbx_rlepso_rollout', 'mbx_lde_rollout_resident', 'mbx_lde_rollout', 'mbx_rlpso_rollout',
-                    'mbx_qlpso_rollout', 'mbx_dedqn_rollout', 'mbx_gleet_policy', 'mbx_debug_math', 'mbx_debug_rlepso_draws', 'mbx_batch_launch_info', 'mbx_instance_state_doubles',
+                    'mbx_qlpso_rollout', 'mbx_dedqn_rollout', 'mbx_nrlpso_rollout', 'mbx_gleet_policy', 'mbx_debug_math', 'mbx_debug_rlepso_draws', 'mbx_batch_launch_info', 'mbx_instance_state_doubles',
                     'mbx_debug_read_state', 'mbx_debug_write_state', 'mbx_debug_clock_probe', 'mbx_debug_clock_mark', 'mbx_debug_clock_slots',
                     'mbx_batch_rebind', 'mbx_read_public', 'mbx_last_error', 'mbx_version')
 

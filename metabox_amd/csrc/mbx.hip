@@ -1,5 +1,5 @@
 // mbx.hip — libmbx.so: kernels' launch code and the C-ABI of include/mbx.h.
-// Build: make -C metabox_amd/csrc  (seven translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
+// Build: make -C metabox_amd/csrc  (eight translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -44,6 +44,7 @@
 #include "mbx_run_kernels.hpp"
 #ifdef MBX_SINGLE_TU
 #include "mbx_run_dedqn.hip"           // the DEDQN kernels and their launch code, in this file as well
+#include "mbx_run_nrlpso.hip"          // ... and the NRLPSO ones
 #endif
 
 using namespace mbx;
@@ -95,6 +96,7 @@ struct mbx_batch {
     bool rl_run_kinds_ok = false;          // RLEPSO: every problem of the batch is one of the 24 BBOB kinds the per-kind k_rlepso_run geometries have a body for (rl_run_kind_ok)
     bool lde_run_kinds_ok = false;         // LDE: every problem of the batch has an objective kind the LEAN instantiations of k_lde_run build (one tile array: lde_run_kind_ok(.., two = false))
     bool lde_run_kinds_two = false;        // ... a kind the instantiations with the second tile array build (F1-F24)
+    bool nrlpso_cached = false;            // NRLPSO: the step kernels keep the NP x NP distance matrix in LDS (MBX_F_NRLPSO_RECOMPUTE clear and the matrix fits)
     bool rollout_per_generation = false;   // MBX_F_ROLLOUT_PER_GENERATION: the mbx_*_rollout entry points take the host-loop route
     int64_t state_stride = 0;
     const double* d_tape = nullptr;
@@ -112,6 +114,8 @@ struct mbx_batch {
 
 // per-algorithm geometry
 struct AlgoGeom { int64_t state_doubles, sc_off, tape_stride, lds_doubles; int state_dim, action_dim; };
+
+static int max_lds_bytes();
 
 static AlgoGeom geom_of(const mbx_algo_cfg& c)
 {
@@ -196,6 +200,14 @@ static AlgoGeom geom_of(const mbx_algo_cfg& c)
         g.tape_stride = MBX_DEDQN_TAPE_STRIDE(c.np, c.dim);
         g.lds_doubles = dedqn_lds_doubles(c.np, c.dim);
         g.state_dim = MBX_DEDQN_NFEAT; g.action_dim = 1;
+    } else if (c.algo == MBX_ALGO_NRLPSO) {
+        g.state_doubles = MBX_NRLPSO_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
+        g.sc_off = MBX_NRLPSO_ST_SCALARS(c.np, c.dim);
+        g.tape_stride = MBX_NRLPSO_TAPE_STRIDE(c.np, c.dim);
+        // the larger of the reset's carve-up (NP evaluation rows) and the step's (one row, the resident arrays, the distance matrix where it is kept)
+        g.lds_doubles = std::max(nrlpso_lds_doubles(c.np, c.dim, false, false),
+                                 nrlpso_lds_doubles(c.np, c.dim, true, nrlpso_cached(c.np, c.dim, c.flags, (size_t)max_lds_bytes())));
+        g.state_dim = 1; g.action_dim = 1;
     }
     return g;
 }
@@ -488,7 +500,7 @@ static int check_cfg(const mbx_algo_cfg* c)
     if (!c) return fail(MBX_E_ARG, "null cfg");
     // the ids this build has kernels for (12, 14 and 17 are not assigned)
     if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21 || c->algo == MBX_ALGO_MADDE || c->algo == MBX_ALGO_DEDQN ||
-          c->algo == MBX_ALGO_SDMSPSO))
+          c->algo == MBX_ALGO_SDMSPSO || c->algo == MBX_ALGO_NRLPSO))
         return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
     if (c->algo == MBX_ALGO_JDE21 && c->np != MBX_JDE21_NP) return fail(MBX_E_ARG, "JDE21 runs np = %d (160 + 10 rows), not %d", MBX_JDE21_NP, c->np);
     if (c->algo == MBX_ALGO_MADDE) {
@@ -508,12 +520,16 @@ static int check_cfg(const mbx_algo_cfg* c)
         // the landscape analysis deals one row per lane of two waves, and LDS holds the population three times over
         if (c->np < 4 || c->np > MBX_DEDQN_NP_MAX) return fail(MBX_E_ARG, "DEDQN runs np in [4, %d], not %d", MBX_DEDQN_NP_MAX, c->np);
         if (c->dim < 2 || c->dim > MBX_DEDQN_DIM_MAX) return fail(MBX_E_ARG, "DEDQN runs dim in [2, %d], not %d", MBX_DEDQN_DIM_MAX, c->dim);
+    } else if (c->algo == MBX_ALGO_NRLPSO) {
+        // one lane per row of the distance matrix (two waves), k = 5 neighbours out of np - 1, and LDS holds population and pbest positions
+        if (c->np < MBX_NRLPSO_NP_MIN || c->np > MBX_NRLPSO_NP_MAX) return fail(MBX_E_ARG, "NRLPSO runs np in [%d, %d], not %d", MBX_NRLPSO_NP_MIN, MBX_NRLPSO_NP_MAX, c->np);
+        if (c->dim < 2 || c->dim > MBX_NRLPSO_DIM_MAX) return fail(MBX_E_ARG, "NRLPSO runs dim in [2, %d], not %d", MBX_NRLPSO_DIM_MAX, c->dim);
     } else if (c->np < 4 || c->np > kThreads) return fail(MBX_E_ARG, "np %d outside [4, %d]", c->np, kThreads);
     if (c->dim < 2 || c->dim > 64) return fail(MBX_E_ARG, "dim %d outside [2, 64]", c->dim);
     if (c->algo == MBX_ALGO_RLEPSO && (c->n_group < 1 || c->n_group > 16 || c->np / c->n_group < 1))
         return fail(MBX_E_ARG, "bad n_group %d", c->n_group);
     if (c->max_fes <= 0 || c->log_interval <= 0 || c->n_logpoint <= 0) return fail(MBX_E_ARG, "bad budget/log settings");
-    if (c->flags & ~(MBX_F_FDR_FAST | MBX_F_GENERIC_GEOMETRY | MBX_F_ROLLOUT_PER_GENERATION)) return fail(MBX_E_ARG, "unknown bits in cfg.flags 0x%x", c->flags);
+    if (c->flags & ~(MBX_F_FDR_FAST | MBX_F_GENERIC_GEOMETRY | MBX_F_ROLLOUT_PER_GENERATION | MBX_F_NRLPSO_RECOMPUTE)) return fail(MBX_E_ARG, "unknown bits in cfg.flags 0x%x", c->flags);
     return MBX_OK;
 }
 
@@ -644,6 +660,7 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
         if (cfg->algo == MBX_ALGO_DEDDQN && cfg->np == 100 && cfg->dim == 12 && !generic) b->fixed_geometry = 4;
         if (cfg->algo == MBX_ALGO_GLEET && cfg->np == 100 && cfg->dim == 10 && !generic) b->fixed_geometry = 5;
         b->rollout_per_generation = (cfg->flags & MBX_F_ROLLOUT_PER_GENERATION) != 0;
+        b->nrlpso_cached = cfg->algo == MBX_ALGO_NRLPSO && nrlpso_cached(cfg->np, cfg->dim, cfg->flags, (size_t)max_lds_bytes());
     }
 #ifdef MBX_LDS_PAD_EXPERIMENT
     if (const char* e = getenv("MBX_LDS_PAD")) b->lds_bytes += (size_t)atoi(e);      // occupancy experiments only
@@ -730,6 +747,8 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
             HIP_TRY(hipMalloc(&b->d_pci, lt.size() * sizeof(double)));
             HIP_TRY(hipMemcpy(b->d_pci, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
         }
+    } else if (cfg->algo == MBX_ALGO_NRLPSO) {
+        HIP_TRY(nrlpso_prepare(lds));
     } else if (cfg->algo == MBX_ALGO_QLPSO) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -848,6 +867,8 @@ extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
         hipLaunchKernelGGL(k_sdmspso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_DEDQN)
         dedqn_launch_reset(make_params(b), b->lds_bytes, (hipStream_t)stream, d_state_out);
+    else if (b->cfg.algo == MBX_ALGO_NRLPSO)
+        nrlpso_launch_reset(make_params(b), (hipStream_t)stream, d_state_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_GLEET)
@@ -907,6 +928,9 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
                            d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_DEDQN)
         dedqn_launch_step(make_params(b), b->lds_bytes, (hipStream_t)stream, (const int32_t*)d_actions, d_state_out, d_reward_out, d_done_out);
+    else if (b->cfg.algo == MBX_ALGO_NRLPSO)
+        nrlpso_launch_steps(make_params(b), b->nrlpso_cached, (hipStream_t)stream, (const int32_t*)d_actions, nullptr, 1, nullptr, nullptr, nullptr, nullptr,
+                            d_state_out, d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_step<false>, dim3(b->B), dim3(kThreads), (size_t)ql_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double),
                            (hipStream_t)stream, make_params(b), (const int32_t*)d_actions, (const double*)nullptr, 1, d_state_out,
@@ -1247,6 +1271,19 @@ extern "C" int mbx_dedqn_rollout(mbx_batch* b, const mbx_dedqn_net* net, int n_s
     return MBX_OK;
 }
 
+extern "C" int mbx_nrlpso_rollout(mbx_batch* b, const double* d_q_table, int n_steps, int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward,
+                                  int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
+{
+    if (!b || !d_q_table) return fail(MBX_E_ARG, "mbx_nrlpso_rollout: bad arguments");
+    if (b->cfg.algo != MBX_ALGO_NRLPSO) return fail(MBX_E_UNSUPPORTED, "mbx_nrlpso_rollout: the batch is not an NRLPSO batch");
+    if (n_steps < 1) return fail(MBX_E_ARG, "mbx_nrlpso_rollout: n_steps must be >= 1");
+    if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_nrlpso_rollout: a replay tape holds one step");
+    nrlpso_launch_steps(make_params(b), b->nrlpso_cached, (hipStream_t)stream, nullptr, d_q_table, n_steps, d_traj_actions, d_traj_state, d_traj_reward,
+                        d_actions_out, d_state_out, d_reward_out, d_done_out);
+    HIP_TRY(hipGetLastError());
+    return MBX_OK;
+}
+
 extern "C" int mbx_qlpso_rollout(mbx_batch* b, const double* d_q_table, int n_steps, int32_t* d_actions_out, double* d_state_out,
                                  double* d_reward_out, uint8_t* d_done_out, void* stream)
 {
@@ -1359,6 +1396,7 @@ extern "C" int mbx_batch_launch_info(const mbx_batch* b, int32_t out[4])
 {
     if (!b || !out) return fail(MBX_E_ARG, "mbx_batch_launch_info: bad arguments");
     out[0] = b->threads; out[1] = (int32_t)b->lds_bytes; out[2] = b->fixed_geometry; out[3] = (int32_t)b->state_stride;
+    if (b->cfg.algo == MBX_ALGO_NRLPSO) out[1] = (int32_t)(nrlpso_lds_doubles(b->cfg.np, b->cfg.dim, true, b->nrlpso_cached) * sizeof(double));   // the step kernels' (the reset's carve-up is smaller at np = 100)
     if (b->cfg.algo == MBX_ALGO_LDE && b->fixed_geometry == 3) out[0] = MBX_LDE50_STEP_THREADS;       // k_lde_step's own workgroup size (k_lde_reset keeps b->threads)
     if (b->cfg.algo == MBX_ALGO_DEDDQN) {                      // the step kernel (small workgroups, one-row evaluator scratch), not k_dq_reset
         out[0] = kDqStepThreads; out[1] = (int32_t)(dq_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double));

@@ -11,6 +11,7 @@
 #include "mbx_device.hpp"
 #include "mbx_rlepso.hpp"   // BatchParams, align2
 #include "mbx_npsum.hpp"    // np_sum: numpy's pairwise summation order
+#include "mbx_qchoose.hpp"  // ql_choose: the tabular agents' choice rule
 
 namespace mbx {
 // four waves per SIMD: left alone the compiler takes 126-160 VGPRs for the multi-step / sweep kernels (three resident workgroups per CU
@@ -116,21 +117,6 @@ __global__ __launch_bounds__(kThreads) void k_qlpso_reset(BatchParams bp, double
         sc[MBX_SC_QLPSO_DIVERSITY] = diversity;
         sc[MBX_NSCALAR] = gb;
     }
-}
-
-// QLPSO_Agent.__get_action (qlpso_agent.py:35-38): p = softmax(Q[state]); np.random.choice(4, p = p) with one uniform u:
-// index = searchsorted(cumsum(p) / cumsum(p)[-1], u, side = 'right').
-__device__ __forceinline__ int ql_choose(const double* __restrict__ q_row, double u)
-{
-    double e[4], s = 0., cdf[4], c = 0.;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { e[k] = m_exp(q_row[k]); s += e[k]; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { c += e[k] / s; cdf[k] = c; }
-    int idx = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) idx += (cdf[k] / cdf[3]) <= u;
-    return idx;
 }
 
 // ------------------------------------------------------------------------------------------------ step (update :92-125)

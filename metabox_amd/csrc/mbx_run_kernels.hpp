@@ -36,3 +36,14 @@ void dedqn_launch_step(const BatchParams& bp, size_t lds_bytes, hipStream_t stre
 void dedqn_launch_run(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, const float* d_net, int n_steps, int32_t* d_traj_actions,
                       double* d_traj_state, double* d_traj_reward, int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
 }  // namespace mbx
+// NRLPSO (mbx_nrlpso.hpp): likewise in mbx_run_nrlpso.hip
+namespace mbx {
+bool nrlpso_cached(int np, int dim, uint32_t flags, size_t max_lds_bytes);     // the distance matrix stays in LDS (flag clear and it fits)
+int64_t nrlpso_lds_doubles(int np, int dim, bool step, bool cached);
+hipError_t nrlpso_prepare(size_t lds_bytes);
+void nrlpso_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state_out);
+// d_actions: the caller's actions (mbx_step), or nullptr with the Q-table: the policy decides in the kernel
+void nrlpso_launch_steps(const BatchParams& bp, bool cached, hipStream_t stream, const int32_t* d_actions, const double* d_q_table, int n_steps,
+                         int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward, int32_t* d_actions_out, double* d_state_out,
+                         double* d_reward_out, uint8_t* d_done_out);
+}  // namespace mbx

@@ -8,6 +8,7 @@ from .rl_pso_optimizer import RL_PSO_Optimizer
 from .gleet_optimizer import GLEET_Optimizer
 from .qlpso_optimizer import QLPSO_Optimizer
 from .dedqn_optimizer import DEDQN_Optimizer
+from .nrlpso_optimizer import NRLPSO_Optimizer
 from .classic import DEAP_CMAES, DEAP_DE, DEAP_PSO
 from .gl_pso import GL_PSO
 from .jde21 import JDE21

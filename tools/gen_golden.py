@@ -2067,7 +2067,270 @@ def gen_sdmspso():
         assert os.path.getsize(path) < 1000 * 1000
 
 
-SECTIONS = {'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+class _NrMargin(Exception):
+    pass
+
+
+NR_TIE_RTOL, NR_ATOL = 1e-9, 8 * 4.6e-13          # tests/helpers.py: TIE_RTOL, ATOL
+
+
+def run_nrlpso_episode(problem, seed, q_table, config, opt=None, snaps=6, noisy=False):
+    """One reference NRLPSO rollout.  q_table given: the agent's rule (softmax over the Q-row + np.random.choice from the global stream);
+    None: uniform actions from a private RandomState.  Raises _NrMargin when a cost comparison (:214, :232, :256-274) between different
+    positions is closer than the parity tolerance, when an unmoved particle's re-evaluation differs from its stored cost, or when a
+    neighbour list hangs on tied distances."""
+    import copy
+    from optimizer.nrlpso_optimizer import NRLPSO_Optimizer
+    from environment import PBO_Env
+    opt = opt if opt is not None else NRLPSO_Optimizer(copy.deepcopy(config))
+    get = lambda name: getattr(opt, '_NRLPSO_Optimizer__' + name)          # noqa: E731
+    cur, track = {}, {}
+
+    def margin(a, b, same, what):
+        if same and not noisy:
+            if a != b:
+                raise _NrMargin(f'{what}: the re-evaluation of an unmoved position differs')
+        elif abs(a - b) <= NR_TIE_RTOL * max(abs(a), abs(b)) + NR_ATOL:
+            raise _NrMargin(what)
+
+    real = {k: getattr(opt, k) for k in ('cal_cs', 'cal_ef', 'neb_mutation', 'cal_cost', 'update_construct_neighborhood')}
+
+    def cal_cs(p1, p2):
+        cur['cs'] = real['cal_cs'](p1, p2)
+        return cur['cs']
+
+    def cal_ef(ith):
+        v = real['cal_ef'](ith)
+        cur.setdefault('ef', []).append(v)
+        return v
+
+    def neb_mutation(ith, prob):
+        cur['mutated'] = True
+        nb = opt.pbest_neb[ith]
+        cur['stale'] = not np.array_equal(nb, get('population')[opt.pbest_neb_index[ith]])
+        for ref_pos, rows in ((get('pbest_pos')[ith], nb), (get('gbest_pos'), opt.gbest_neb)):
+            d = np.sqrt(np.sum((ref_pos[None, :] - rows) ** 2, axis=-1))
+            if len(np.unique(d)) != len(d):
+                raise _NrMargin('tied mutation distances')
+        return real['neb_mutation'](ith, prob)
+
+    def cal_cost(x, prob):
+        k = len(cur['costs'])
+        c = float(real['cal_cost'](x, prob))
+        p = opt.pointer
+        if k == 0:
+            margin(c, float(get('cost')[p]), np.array_equal(x, cur['x_before']), 'f_new < f_old')
+            margin(c, float(get('pbest_cost')[p]), np.array_equal(x, track['pbpos'][p]), 'f_new < pbest_cost')
+            cur['x'] = np.array(x)
+        elif k == 1:
+            margin(c, float(get('pbest_cost')[p]), False, 'mutation < pbest_cost')
+            cur['pm_take'] = c < get('pbest_cost')[p]
+            if cur['pm_take']:
+                track['pbpos'][p] = np.array(x)
+        else:
+            margin(c, float(get('gbest_cost')), False, 'mutation < gbest_cost')
+            cur['gm_take'] = c < get('gbest_cost')
+            if cur['gm_take']:
+                track['gbpos'] = np.array(x)
+        cur['costs'].append(c)
+        return c
+
+    def construct():
+        real['update_construct_neighborhood']()
+        pop, pb = get('population'), get('pbest_pos')
+        m = np.sqrt(np.sum((pb[None, :] - pop[:, None]) ** 2, axis=-1))
+        m[np.arange(len(m)), np.arange(len(m))] = np.inf
+        g = np.sqrt(np.sum((get('gbest_pos')[None, :] - pop) ** 2, axis=-1))
+        for row in list(m) + [g]:
+            six = np.sort(row)[:6]
+            if len(np.unique(six)) != 6:
+                raise _NrMargin('tied neighbour distances')
+    opt.cal_cs, opt.cal_ef, opt.neb_mutation, opt.cal_cost, opt.update_construct_neighborhood = cal_cs, cal_ef, neb_mutation, cal_cost, construct
+
+    def alias_row():
+        g, pop = get('gbest_pos'), get('population')
+        if not np.shares_memory(g, pop):
+            return -1
+        return (g.__array_interface__['data'][0] - pop.__array_interface__['data'][0]) // pop.strides[0]
+
+    def snapshot():
+        return {'pop': np.array(get('population')), 'vel': np.array(get('velocity')), 'pbpos': np.array(get('pbest_pos')),
+                'pbcost': np.array(get('pbest_cost')), 'cost': np.array(get('cost')), 'stag': np.array(opt.pbest_stag_count),
+                'pnidx': np.array(opt.pbest_neb_index, dtype=np.int16), 'gnidx': np.array(opt.gbest_neb_index, dtype=np.int16),
+                'gbpos': np.array(get('gbest_pos')), 'alias': np.int64(alias_row()), 'w': np.float64(opt.w), 'r_w': np.float64(opt.r_w)}
+    try:
+        env = PBO_Env(problem, opt)
+        np.random.seed(seed)
+        ars = np.random.RandomState(90_000 + seed)
+        state = env.reset()
+        track['pbpos'] = [np.array(r) for r in get('population')]
+        track['gbpos'] = np.array(get('gbest_pos'))
+        rec = {k: [] for k in ('actions', 'reward', 'done', 'gbest', 'fes', 'csneg', 'mutated', 'ef_old', 'ef_new', 'alias', 'moved_alias', 'pm_take', 'gm_take',
+                               'stale', 'fnew')}
+        rec['states'] = [int(state)]
+        rec['sstate0'] = np.array(get('state'), dtype=np.uint8)
+        rec['cost0'], rec['pmcost'], rec['gmcost'] = np.array(get('cost')), [], []
+        snap, done, g, first_mut = {}, False, 0, None
+        while not done:
+            if q_table is not None:
+                e = np.exp(q_table[state])
+                a = np.random.choice(4, size=1, p=e / e.sum())
+            else:
+                a = np.array([ars.randint(0, 4)])
+            p, al = opt.pointer, alias_row()
+            cur.clear()
+            cur.update(costs=[], mutated=False, x_before=np.array(get('population')[p]), pm_take=-1, gm_take=-1, stale=False)
+            gb0 = float(get('gbest_cost'))
+            state, r, done = env.step(a)
+            g += 1
+            fnew = cur['costs'][0]
+            gb274 = cur['costs'][2] if cur['mutated'] and cur['gm_take'] else gb0
+            margin(fnew, gb274, np.array_equal(cur['x'], track['gbpos']), 'f_new < gbest_cost')
+            if fnew < gb274:
+                track['gbpos'] = np.array(cur['x'])
+            rec['actions'].append(int(a[0])); rec['states'].append(int(state)); rec['reward'].append(int(r)); rec['done'].append(bool(done))
+            rec['gbest'].append(float(get('gbest_cost'))); rec['fes'].append(opt.fes); rec['csneg'].append(bool(cur['cs'] < 0))
+            rec['mutated'].append(cur['mutated']); rec['ef_old'].append(cur['ef'][0]); rec['ef_new'].append(cur['ef'][1]); rec['alias'].append(alias_row())
+            rec['moved_alias'].append(al == p and not np.array_equal(cur['x_before'], cur['x']))
+            rec['pm_take'].append(int(cur['pm_take'])); rec['gm_take'].append(int(cur['gm_take'])); rec['stale'].append(cur['stale']); rec['fnew'].append(fnew)
+            rec['pmcost'].append(cur['costs'][1] if cur['mutated'] else np.nan); rec['gmcost'].append(cur['costs'][2] if cur['mutated'] else np.nan)
+            snap[g] = snapshot() if (g % 100 == 0 or done or (cur['mutated'] and first_mut is None)) else None
+            if cur['mutated'] and first_mut is None:
+                first_mut = g
+    finally:
+        for k in real:
+            delattr(opt, k)
+    G = len(rec['actions'])
+    keep = sorted(set([min((s for s in snap if snap[s] is not None), key=lambda s: abs(s - t)) for t in np.linspace(1, G, snaps - 1)] +
+                      ([first_mut] if first_mut else []) + [G]))
+    out = {'actions': np.array(rec['actions'], dtype=np.uint8), 'states': np.array(rec['states'], dtype=np.uint8), 'reward': np.array(rec['reward'], dtype=np.int8),
+           'done': np.array(rec['done']), 'gbest': np.array(rec['gbest']), 'fes': np.array(rec['fes'], dtype=np.int64), 'csneg': np.array(rec['csneg']),
+           'mutated': np.array(rec['mutated']), 'ef_old': np.array(rec['ef_old']), 'ef_new': np.array(rec['ef_new']), 'alias': np.array(rec['alias'], dtype=np.int16),
+           'moved_alias': np.array(rec['moved_alias']), 'pm_take': np.array(rec['pm_take'], dtype=np.int8), 'gm_take': np.array(rec['gm_take'], dtype=np.int8),
+           'stale': np.array(rec['stale']), 'fnew': np.array(rec['fnew']), 'sstate0': rec['sstate0'], 'cost0': rec['cost0'],
+           'pmcost': np.array(rec['pmcost']), 'gmcost': np.array(rec['gmcost']), 'cost': np.array(opt.cost, dtype=np.float64),
+           'snap_steps': np.array(keep), 'first_mutation': np.int64(first_mut or 0), 'next_rand': np.float64(np.random.rand())}
+    for s_ in keep:
+        for k, v in snap[s_].items():
+            out[f'snap{s_}/{k}'] = v
+    return opt, out
+
+
+def gen_nrlpso():
+    """NRLPSO (src/optimizer/nrlpso_optimizer.py, src/agent/nrlpso_agent.py).  The reference ships no NRLPSO model: its agent is trained here for
+    three seeded episodes, the table stored, and the last training episode's transitions with the table before and after.  Episodes at maxFEs
+    1500 driven by that table or by uniform actions, recorded per step with about six full snapshots each; the numpy draws are NOT stored (the
+    tests regenerate them from the seed and the recorded `cs < 0` / mutated flags).  An episode is kept only if it passes the margins of
+    run_nrlpso_episode; otherwise the next seed is tried."""
+    import copy as _copy
+    from agent.nrlpso_agent import NRLPSO_Agent
+    from optimizer.nrlpso_optimizer import NRLPSO_Optimizer
+    from environment import PBO_Env
+    scratch = tempfile.mkdtemp()
+
+    def config_for(suite, dim, max_fes=1500, extra=()):
+        c = ref_import.ref_config(['--problem', suite, '--dim', str(dim)] + list(extra), scratch)
+        c.maxFEs = max_fes
+        c.log_interval = c.maxFEs // c.n_logpoint
+        return c
+    probs = {}
+
+    def pick(suite, dim, fid):
+        if (suite, dim) not in probs:
+            tr, te, _ = all_problems(suite, dim)
+            probs[(suite, dim)] = {fid_of(p): p for p in tr + te}
+        return probs[(suite, dim)][fid]
+    # ---- the table: three training episodes of the reference agent
+    config = config_for('bbob', 10, extra=['--max_learning_step', '6000'])
+    config.save_interval = 10 ** 9
+    agent = NRLPSO_Agent(_copy.deepcopy(config))
+    np.random.seed(7)
+    pol = {}
+    for n, fid in enumerate((1, 15, 21)):
+        env = PBO_Env(pick('bbob', 10, fid), NRLPSO_Optimizer(_copy.deepcopy(config)))
+        trans, real_step, real_reset, last = [], env.step, env.reset, {}
+
+        def reset():
+            last['s'] = real_reset()
+            return last['s']
+
+        def step(a):
+            s2, r, d = real_step(a)
+            trans.append((int(last['s']), int(a[0]), int(r), int(s2)))
+            last['s'] = s2
+            return s2, r, d
+        env.reset, env.step = reset, step
+        q0, ls0 = np.array(agent._NRLPSO_Agent__q_table), int(agent._NRLPSO_Agent__global_ls)
+        agent.train_episode(env)
+        if n == 2:
+            t = np.array(trans)
+            pol.update({'train/q_before': q0, 'train/q_after': np.array(agent._NRLPSO_Agent__q_table), 'train/ls0': np.int64(ls0),
+                        'train/max_ls': np.int64(config.max_learning_step), 'train/state': t[:, 0].astype(np.uint8), 'train/action': t[:, 1].astype(np.uint8),
+                        'train/reward': t[:, 2].astype(np.int8), 'train/next_state': t[:, 3].astype(np.uint8)})
+    q = np.array(agent._NRLPSO_Agent__q_table, dtype=np.float64)
+    pol['q_table'] = q
+    np.savez_compressed(os.path.join(OUT, 'nrlpso_policy.npz'), **pol)
+    print('q_table', q, 'training transitions', len(pol['train/state']))
+    # ---- episodes: (suite, dim, function, first seed, policy-driven, a second episode on the same object, file)
+    jobs = [('bbob', 10, 3, 41, False, False, 0), ('bbob', 10, 21, 42, True, True, 0), ('bbob-noisy', 10, 118, 43, True, False, 1),
+            ('bbob-noisy', 10, 129, 44, False, False, 1), ('bbob', 10, 1, 45, True, False, 1), ('bbob', 30, 15, 46, False, False, 2),
+            ('bbob-noisy', 30, 118, 47, True, False, 3)]
+    files, cases = [{}, {}, {}, {}], []
+    for suite, dim, fid, seed0, policy, second, fno in jobs:
+        config = config_for(suite, dim)
+        noisy = suite == 'bbob-noisy'
+        for seed in range(seed0, seed0 + 100000, 100):
+            p = pick(suite, dim, fid)
+            p.reset()
+            try:
+                opt, rec = run_nrlpso_episode(p, seed, q if policy else None, config, noisy=noisy, snaps=6 if dim == 10 else 4)
+                if dim == 30 and not rec['mutated'].any():
+                    raise _NrMargin('no mutation')
+                if fid == 129 and rec['fes'][-1] <= config.maxFEs:         # the stress case also ends on a mutating step: fes passes maxFEs
+                    raise _NrMargin('fes does not pass maxFEs')
+                rec2 = run_nrlpso_episode(p, seed + 1, q if policy else None, config, opt=opt, noisy=noisy, snaps=3)[1] if second else None
+                break
+            except _NrMargin as e:
+                print(f'  {suite}/{dim}/{fid} seed {seed}: {e}; next seed')
+        key = f'{suite}/{dim}/{fid}/{seed}/' + ('policy' if policy else 'uniform')
+        cases.append(key)
+        out = files[fno]
+        out[f'{key}/max_fes'] = np.int64(config.maxFEs)
+        for k, v in rec.items():
+            out[f'{key}/{k}'] = v
+        if rec2 is not None:
+            for k, v in rec2.items():
+                out[f'{key}/second/{k}'] = v
+        m = rec['mutated']
+        print(key, 'steps', len(m), 'fes', rec['fes'][-1], 'mutations', int(m.sum()), 'pbest taken / not', int((rec['pm_take'] == 1).sum()), int((rec['pm_take'] == 0).sum()),
+              'gbest taken / not', int((rec['gm_take'] == 1).sum()), int((rec['gm_take'] == 0).sum()), 'moved alias', int(rec['moved_alias'].sum()),
+              'ef equal', int((rec['ef_old'] == rec['ef_new']).sum()), 'actions', np.bincount(rec['actions'], minlength=4), 'snaps', rec['snap_steps'])
+    # ---- the set as a whole covers the reference's quirks (the early stop at gbest <= 1e-8 is not reached at these budgets)
+    allrec = [(c, files[j[6]]) for c, j in zip(cases, jobs)]
+    cat = lambda k: np.concatenate([f[f'{c}/{k}'] for c, f in allrec])          # noqa: E731
+    assert (cat('pm_take') == 1).any() and (cat('pm_take') == 0).any() and (cat('gm_take') == 1).any() and (cat('gm_take') == 0).any()
+    assert cat('moved_alias').any() and (cat('alias') == -1).any() and cat('stale').any() and (cat('ef_old') == cat('ef_new')).any()
+    for a in range(4):
+        sel = cat('actions') == a
+        assert cat('csneg')[sel].any() and (~cat('csneg')[sel]).any(), a
+    assert any(f[f'{c}/fes'][-1] > 1500 for c, f in allrec)                    # fes passes maxFEs
+    assert any((np.diff(f[f'{c}/fes']) == 3).any() and len(f[f'{c}/cost']) == 51 for c, f in allrec)
+    for c, f in allrec:                                                        # a particle whose count stays >= 2 mutates again on its next turn
+        m = np.nonzero(f[f'{c}/mutated'])[0]
+        if len(m) and np.any(np.isin(m + 100, m)):
+            break
+    else:
+        raise AssertionError('no particle mutates on consecutive turns')
+    assert not any(f[f'{c}/done'][-1] and f[f'{c}/fes'][-1] < 1500 for c, f in allrec), 'an episode stopped early: describe it in the tests'
+    files[0]['cases'] = np.array(cases)
+    for n, out in enumerate(files):
+        path = os.path.join(OUT, 'nrlpso_traces.npz' if n == 0 else f'nrlpso_traces_{n}.npz')
+        np.savez_compressed(path, **out)
+        print(os.path.basename(path), os.path.getsize(path))
+        assert os.path.getsize(path) < 1000 * 1000, (path, os.path.getsize(path))
+
+
+SECTIONS = {'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -248,6 +248,38 @@ if 'dedqn' in which:
         print(json.dumps({'path': f'k_dedqn_run bbob d={dim} NP=100, {B} instances, 32 env steps per launch, Q-network in the kernel', 'us_per_step': dt / 96 * 1e6,
                           'ns_per_row': dt / 96 / (101 * B) * 1e9}))
         b.close()
+if 'nrlpso' in which:
+    # NRLPSO (one env step = one particle: the move, two normalised mean distances over the NP x NP distance matrix, one evaluation, now and then the
+    # neighbourhood mutation) in its cached form (matrix in LDS, row / column refresh) and its recompute form (MBX_F_NRLPSO_RECOMPUTE), one launch per
+    # step (mbx_step, action from the host side) and resident (64 steps per launch, table in the kernel), beside QLPSO's resident step in the same
+    # process: bbob round-robin, 4096 instances at D = 10 and 1024 at D = 30, NP = 100, a budget so large that every instance stays live.  Median of
+    # 5 windows per path, the paths alternating window by window, each window ended by a device synchronise (wall times, launch gaps included).
+    from metabox_amd._abi import ALGO_NRLPSO, ALGO_QLPSO, F_NRLPSO_RECOMPUTE
+    from metabox_amd.suite import Batch, Suite
+    q = torch.from_numpy(np.load(os.path.join(os.path.dirname(__file__), '..', 'tests', 'golden', 'nrlpso_policy.npz'))['q_table']).cuda()
+    for dim, B in ((10, 4096), (30, 1024)):
+        cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+        tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+        s = Suite(ps)
+        mk = lambda algo, np_, flags=0: Batch(s, algo, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, np_, 10 ** 9, 10 ** 7, 50, early_stop=False, flags=flags)
+        bq, bc, br = mk(ALGO_QLPSO, 30), mk(ALGO_NRLPSO, 100), mk(ALGO_NRLPSO, 100, F_NRLPSO_RECOMPUTE)
+        acts = torch.full((B,), 2, dtype=torch.int32, device='cuda')
+        paths = {'QLPSO resident (NP = 30)': (lambda n: [bq.qlpso_rollout(q, 64) for _ in range(n)], 64),
+                 'NRLPSO cached, resident': (lambda n: [bc.nrlpso_rollout(q, 64) for _ in range(n)], 64),
+                 'NRLPSO recompute, resident': (lambda n: [br.nrlpso_rollout(q, 64) for _ in range(n)], 64),
+                 'NRLPSO cached, one launch per step': (lambda n: [bc.step(acts) for _ in range(n)], 1),
+                 'NRLPSO recompute, one launch per step': (lambda n: [br.step(acts) for _ in range(n)], 1)}
+        for b in (bq, bc, br): b.reset()
+        times = {k: [] for k in paths}
+        for w in range(6):
+            for k, (fn, per) in paths.items():
+                n = 2 if per == 64 else 32
+                dt = timed(fn, n)
+                if w: times[k].append(dt / (n * per) * 1e6)             # window 0 warms up
+        for k, v in times.items():
+            print(json.dumps({'path': f'{k}, bbob d={dim}, {B} instances', 'us_per_step_median': float(np.median(v)), 'windows': [round(x, 1) for x in v],
+                              'launch_info': (bc if 'cached' in k else br if 'recompute' in k else bq).launch_info()}))
+        for b in (bq, bc, br): b.close()
 if 'sdmspso' in which:
     # sDMS_PSO (one mbx_step = one update: 99 evaluated rows) next to GL-PSO (one generation: 200 evaluated rows and the exemplar breeding) in the
     # same process, alternating: bbob round-robin, 4096 instances, every instance live for the whole window (sDMS_PSO has no early stop; its
