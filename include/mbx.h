@@ -112,6 +112,7 @@ int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, double* d_f,
 #define MBX_ALGO_SDMSPSO 18 /* src/optimizer/sdms_pso.py           one step = one update (NP FEs), np = 99, dim <= 40, max_fes in (99, 103272] -- classic baseline, no agent (12, 14 and 17 are not assigned and stay rejected) */
 #define MBX_ALGO_DEDQN  16  /* src/optimizer/dedqn_optimizer.py     one step = one trial vector + the landscape analysis (2 NP FEs), np in [4, 128], dim <= 40 */
 #define MBX_ALGO_NRLPSO 19  /* src/optimizer/nrlpso_optimizer.py    one step = one particle (1 FE, 3 when the neighbourhood mutation fires), np in [8, 128], dim <= 40 */
+#define MBX_ALGO_SAHLPSO 20 /* src/optimizer/sahlpso.py            one step = one pass over the live particles (NP FEs, NP shrinking 40 -> 4; fewer when the episode ends inside the pass), np = 40, dim <= 40, max_fes > 40 -- classic baseline, no agent */
 
 typedef struct mbx_algo_cfg {
     int32_t algo;          /* MBX_ALGO_*                                                          */
@@ -155,6 +156,7 @@ int mbx_batch_flags(const mbx_batch* b);
  *   DE, PSO, CMAES: state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
  *   GLPSO, JDE21  : state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
  *   MADDE, SDMSPSO: state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
+ *   SAHLPSO       : state [1]      (fes/maxFEs),                             no action (pass NULL to mbx_step)
  *   DEDQN         : state [4]      (dedqn_optimizer.py:130-142: fdc, rie, acf, nop), action [1] int32 (0 rand_1, 1 cur_to_rand_1, anything else best_2)
  *   NRLPSO        : state [1]      (nrlpso_optimizer.py:58-59, 278-296),    action [1] int32 in {0..3} */
 int mbx_state_dim(const mbx_algo_cfg* cfg);

@@ -725,6 +725,95 @@
 #define MBX_SITE_NR_NOISE_B  52u
 #define MBX_SITE_NR_INIT     53u
 
+/* ---------------------------------------------------------------- 17. SAHLPSO (sahlpso.py) layouts
+ * No agent: mbx_reset is run_episode :22-47 (V and X draws, 40 evaluations, the static ranking, the 8 exploration particles -- 40 FEs), every
+ * mbx_step (actions = NULL) one pass of `for i in remain_index` (:50-124: one move and one FE per live particle, strictly in order, each move
+ * seeing the one before it) plus the end-of-generation block (:126-155: every fifth generation the selection probabilities, then the linear
+ * population reduction 40 -> 4).  An episode may end in the middle of a pass (:114-124): the later particles stay untouched and fes is exact.
+ * cfg.np must be 40, 2 <= dim <= 40, max_fes > 40.  state [1] = fes / maxFEs.  Bounds are the literals -5 / 5, v_max 1 (:10).  Kept behaviour:
+ * the header of mbx_sahlpso.hpp.
+ * state block: X[40*D] V[40*D] pbest_pos[40*D] f_X[40] pbest_cost0[40] w[40] rank[40] selected[8] P_cr[8] nf_cr[8] ns_cr[8] P_ls[16] nf_ls[16]
+ *   ns_ls[16] move_i[40] move_cr[40] move_ls[40] move_succ[40] move_cauchy[40] scalars[16] cost_curve[nlog+1].
+ *   pbest_cost0: pBest_cost, which the reference never writes after :31.   rank: np.argsort(pBest_cost) -- rank[k] = the particle with the
+ *   k-th smallest initial cost (equal costs: the lower index first); remain_index is 0..39 while NP = 40 and rank[:NP] afterwards, best_p_index
+ *   is rank[:max(1, int(0.2 NP))].   selected: selected_indiv_index.   P_cr / nf_cr / ns_cr: 5 entries in use (H_cr stays 5), P_ls / nf_ls / ns_ls: 15.
+ *   move_*: one entry per slot of remain_index in the last pass, the first scalars[MBX_SC_SAHL_MOVES] of them valid: the particle, cr_index,
+ *   ls_index, the success flag and the standard-cauchy value of a failed move (the Philox route makes it with the device's tan, which the host
+ *   does not reproduce to the bit: a tape rebuilt from a Philox step takes it from here).
+ *   scalars beyond the common ones (MBX_SC_GEN counts the passes and is the Philox generation word; G = MBX_SC_GEN + 1): the live NP, the row g
+ *   of X that gBest views (MBX_SC_GBEST is gBest_cost, which goes stale when row g moves without improving), the moves of the last pass.
+ * tape per reset: vel_u[40*D] | pos_u[40*D] | noise[3*40] | selected[8]           (draw order :23, :24, the evaluation, :47)
+ * tape per step:  40 records of 10 + 3 D doubles, record k for slot k of remain_index:
+ *   u_cr | u_ls | m | n | pick | rnd2 | cauchy | noise a, b, c | cross_u[D] | rnd1[D] | vel_u[D]
+ *   u_cr / u_ls: the uniforms of the two np.random.choice(range(H), p=P) (:54, :56; read unless G % 5 == 0 and G != 1); m, n: the two PARTICLES of
+ *   np.random.choice(remain_index, 2) (:60, exploration particles), pick: the particle of np.random.choice(best_p_index) (:69, the others), as
+ *   doubles, clamped to [0, 40); rnd2 and cauchy (:102-106, the standard_cauchy value itself) are read after a failed move; rnd1 (:76) by the
+ *   particles that are not exploration particles.
+ * Philox, counter (index, site, gen, episode); reset gen = 0, step gen = number of the pass; k = slot of remain_index:
+ *   reset: MBX_SITE_ELEM_R(e): u53(w0,w1) = pos_u, u53(w2,w3) = vel_u;  MBX_SITE_SH_PERM(i): w0 = the key of particle i, selected[r] = the particle
+ *          whose key has rank r < 8 among the 40 (equal keys: the lower index first);  noise MBX_SITE_SH_NOISE_A/B(i)
+ *   MBX_SITE_SH_CHOICE(k)    u53(w0,w1) = u_cr, u53(w2,w3) = u_ls
+ *   MBX_SITE_SH_PICK(k)      remain_index[mulhi(w0, NP)] = m, remain_index[mulhi(w1, NP)] = n, rank[mulhi(w2, len(best_p_index))] = pick
+ *   MBX_SITE_SH_ELEM(64 k + d)  u53(w0,w1) = cross_u[d], u53(w2,w3) = rnd1[d]        MBX_SITE_SH_VEL(64 k + d)  u53(w0,w1) = vel_u[d]
+ *   MBX_SITE_SH_FAIL(k)      u53(w0,w1) = rnd2, tan(pi (u53(w2,w3) - 0.5)) = cauchy (as MBX_SITE_MD_CAUCHY)
+ *   MBX_SITE_SH_NOISE_A/B(k) the evaluation of slot k                                                                                           */
+#define MBX_SAHL_NP      40
+#define MBX_SAHL_NP_MIN  4
+#define MBX_SAHL_DIM_MAX 40
+#define MBX_SAHL_NSEL    8
+#define MBX_SAHL_HCR     5
+#define MBX_SAHL_HLS     15
+#define MBX_SAHL_LP      5
+#define MBX_SAHL_REC(D)                  (10 + 3 * (int64_t)(D))
+#define MBX_SAHL_REC_UCR     0
+#define MBX_SAHL_REC_ULS     1
+#define MBX_SAHL_REC_M       2
+#define MBX_SAHL_REC_N       3
+#define MBX_SAHL_REC_PICK    4
+#define MBX_SAHL_REC_RND2    5
+#define MBX_SAHL_REC_CAUCHY  6
+#define MBX_SAHL_REC_NOISE   7
+#define MBX_SAHL_REC_CROSS(D)            ((int64_t)10)
+#define MBX_SAHL_REC_RND1(D)             (10 + (int64_t)(D))
+#define MBX_SAHL_REC_VEL(D)              (10 + 2 * (int64_t)(D))
+#define MBX_SAHL_TAPE_VEL(NP, D)         ((int64_t)0)
+#define MBX_SAHL_TAPE_POS(NP, D)         ((int64_t)(NP) * (D))
+#define MBX_SAHL_TAPE_NOISE_INIT(NP, D)  (2 * (int64_t)(NP) * (D))
+#define MBX_SAHL_TAPE_SEL(NP, D)         (2 * (int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_SAHL_TAPE_STRIDE(NP, D)      ((int64_t)(NP) * MBX_SAHL_REC(D))        /* >= 2 NP D + 3 NP + 8 for NP = 40 */
+#define MBX_SAHL_ST_X(NP, D)             ((int64_t)0)
+#define MBX_SAHL_ST_V(NP, D)             ((int64_t)(NP) * (D))
+#define MBX_SAHL_ST_PBPOS(NP, D)         (2 * (int64_t)(NP) * (D))
+#define MBX_SAHL_ST_FX(NP, D)            (3 * (int64_t)(NP) * (D))
+#define MBX_SAHL_ST_PBCOST0(NP, D)       (3 * (int64_t)(NP) * (D) + (NP))
+#define MBX_SAHL_ST_W(NP, D)             (3 * (int64_t)(NP) * (D) + 2 * (int64_t)(NP))
+#define MBX_SAHL_ST_RANK(NP, D)          (3 * (int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_SAHL_ST_SEL(NP, D)           (3 * (int64_t)(NP) * (D) + 4 * (int64_t)(NP))
+#define MBX_SAHL_ST_PCR(NP, D)           (MBX_SAHL_ST_SEL(NP, D) + 8)
+#define MBX_SAHL_ST_NFCR(NP, D)          (MBX_SAHL_ST_SEL(NP, D) + 16)
+#define MBX_SAHL_ST_NSCR(NP, D)          (MBX_SAHL_ST_SEL(NP, D) + 24)
+#define MBX_SAHL_ST_PLS(NP, D)           (MBX_SAHL_ST_SEL(NP, D) + 32)
+#define MBX_SAHL_ST_NFLS(NP, D)          (MBX_SAHL_ST_SEL(NP, D) + 48)
+#define MBX_SAHL_ST_NSLS(NP, D)          (MBX_SAHL_ST_SEL(NP, D) + 64)
+#define MBX_SAHL_ST_MOVE_I(NP, D)        (MBX_SAHL_ST_SEL(NP, D) + 80)
+#define MBX_SAHL_ST_MOVE_CR(NP, D)       (MBX_SAHL_ST_MOVE_I(NP, D) + (NP))
+#define MBX_SAHL_ST_MOVE_LS(NP, D)       (MBX_SAHL_ST_MOVE_I(NP, D) + 2 * (int64_t)(NP))
+#define MBX_SAHL_ST_MOVE_SUCC(NP, D)     (MBX_SAHL_ST_MOVE_I(NP, D) + 3 * (int64_t)(NP))
+#define MBX_SAHL_ST_MOVE_CAUCHY(NP, D)   (MBX_SAHL_ST_MOVE_I(NP, D) + 4 * (int64_t)(NP))
+#define MBX_SAHL_ST_SCALARS(NP, D)       (MBX_SAHL_ST_MOVE_I(NP, D) + 5 * (int64_t)(NP))
+#define MBX_SAHL_STATE_DOUBLES(NP, D, NLOG) (MBX_SAHL_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)
+#define MBX_SC_SAHL_NP       10
+#define MBX_SC_SAHL_GROW     11
+#define MBX_SC_SAHL_MOVES    12
+#define MBX_SITE_SH_CHOICE   54u
+#define MBX_SITE_SH_PICK     55u
+#define MBX_SITE_SH_ELEM     56u
+#define MBX_SITE_SH_VEL      57u
+#define MBX_SITE_SH_FAIL     58u
+#define MBX_SITE_SH_NOISE_A  59u
+#define MBX_SITE_SH_NOISE_B  60u
+#define MBX_SITE_SH_PERM     61u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

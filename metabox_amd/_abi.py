@@ -69,6 +69,7 @@ ALGO_MADDE = 15      # (14 is not assigned)
 ALGO_SDMSPSO = 18    # (17 is not assigned)
 ALGO_DEDQN = 16
 ALGO_NRLPSO = 19
+ALGO_SAHLPSO = 20
 POLICY_RLEPSO, POLICY_RLPSO = 0, 1
 _ARRAY_FIELDS = ('dshift', 'm1', 'm2', 'v0', 'v1', 'v2', 'py', 'pc', 'pw')
 

@@ -194,6 +194,12 @@ static AlgoGeom geom_of(const mbx_algo_cfg& c)
         g.tape_stride = MBX_SDMS_TAPE_STRIDE(c.np, c.dim);
         g.lds_doubles = sd_lds_doubles(c.np, c.dim);
         g.state_dim = 1; g.action_dim = 0;
+    } else if (c.algo == MBX_ALGO_SAHLPSO) {
+        g.state_doubles = MBX_SAHL_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
+        g.sc_off = MBX_SAHL_ST_SCALARS(c.np, c.dim);
+        g.tape_stride = MBX_SAHL_TAPE_STRIDE(c.np, c.dim);
+        g.lds_doubles = sahlpso_lds_doubles(c.dim);
+        g.state_dim = 1; g.action_dim = 0;
     } else if (c.algo == MBX_ALGO_DEDQN) {
         g.state_doubles = MBX_DEDQN_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
         g.sc_off = MBX_DEDQN_ST_SCALARS(c.np, c.dim);
@@ -500,7 +506,7 @@ static int check_cfg(const mbx_algo_cfg* c)
     if (!c) return fail(MBX_E_ARG, "null cfg");
     // the ids this build has kernels for (12, 14 and 17 are not assigned)
     if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21 || c->algo == MBX_ALGO_MADDE || c->algo == MBX_ALGO_DEDQN ||
-          c->algo == MBX_ALGO_SDMSPSO || c->algo == MBX_ALGO_NRLPSO))
+          c->algo == MBX_ALGO_SDMSPSO || c->algo == MBX_ALGO_NRLPSO || c->algo == MBX_ALGO_SAHLPSO))
         return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
     if (c->algo == MBX_ALGO_JDE21 && c->np != MBX_JDE21_NP) return fail(MBX_E_ARG, "JDE21 runs np = %d (160 + 10 rows), not %d", MBX_JDE21_NP, c->np);
     if (c->algo == MBX_ALGO_MADDE) {
@@ -516,6 +522,11 @@ static int check_cfg(const mbx_algo_cfg* c)
         if (sd_local_generations(c->max_fes) >= MBX_SDMS_L)
             return fail(MBX_E_ARG, "sDMS_PSO: with max_fes %d the local phase reaches generation %d, where the reference calls its quasi-Newton refinement "
                                    "(and fails in it); not built", c->max_fes, MBX_SDMS_L);
+    } else if (c->algo == MBX_ALGO_SAHLPSO) {
+        // 40 particles shrinking to 4 (8 of them exploration particles), one lane per dimension in the move; the 40 initial evaluations are spent by mbx_reset
+        if (c->np != MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO runs np = %d (shrinking to 4), not %d", MBX_SAHL_NP, c->np);
+        if (c->dim < 2 || c->dim > MBX_SAHL_DIM_MAX) return fail(MBX_E_ARG, "SAHLPSO runs dim in [2, %d], not %d", MBX_SAHL_DIM_MAX, c->dim);
+        if (c->max_fes <= MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO needs max_fes > %d (the initial evaluation), not %d", MBX_SAHL_NP, c->max_fes);
     } else if (c->algo == MBX_ALGO_DEDQN) {
         // the landscape analysis deals one row per lane of two waves, and LDS holds the population three times over
         if (c->np < 4 || c->np > MBX_DEDQN_NP_MAX) return fail(MBX_E_ARG, "DEDQN runs np in [4, %d], not %d", MBX_DEDQN_NP_MAX, c->np);
@@ -749,6 +760,8 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
         }
     } else if (cfg->algo == MBX_ALGO_NRLPSO) {
         HIP_TRY(nrlpso_prepare(lds));
+    } else if (cfg->algo == MBX_ALGO_SAHLPSO) {
+        HIP_TRY(sahlpso_prepare(lds));
     } else if (cfg->algo == MBX_ALGO_QLPSO) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -869,6 +882,8 @@ extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
         dedqn_launch_reset(make_params(b), b->lds_bytes, (hipStream_t)stream, d_state_out);
     else if (b->cfg.algo == MBX_ALGO_NRLPSO)
         nrlpso_launch_reset(make_params(b), (hipStream_t)stream, d_state_out);
+    else if (b->cfg.algo == MBX_ALGO_SAHLPSO)
+        sahlpso_launch_reset(make_params(b), (hipStream_t)stream, d_state_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_GLEET)
@@ -895,7 +910,7 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
 {
     const bool no_agent = b && (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH || b->cfg.algo == MBX_ALGO_DE || b->cfg.algo == MBX_ALGO_PSO ||
                                 b->cfg.algo == MBX_ALGO_CMAES || b->cfg.algo == MBX_ALGO_GLPSO || b->cfg.algo == MBX_ALGO_JDE21 ||
-                                b->cfg.algo == MBX_ALGO_MADDE || b->cfg.algo == MBX_ALGO_SDMSPSO);
+                                b->cfg.algo == MBX_ALGO_MADDE || b->cfg.algo == MBX_ALGO_SDMSPSO || b->cfg.algo == MBX_ALGO_SAHLPSO);
     if (!b || (!d_actions && !no_agent)) return fail(MBX_E_ARG, "mbx_step: bad arguments");
     if (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH)
         hipLaunchKernelGGL(k_rs_population, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), 0, d_state_out,
@@ -926,6 +941,8 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
     else if (b->cfg.algo == MBX_ALGO_SDMSPSO)
         hipLaunchKernelGGL(k_sdmspso_update, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
                            d_reward_out, d_done_out);
+    else if (b->cfg.algo == MBX_ALGO_SAHLPSO)
+        sahlpso_launch_generation(make_params(b), (hipStream_t)stream, d_state_out, d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_DEDQN)
         dedqn_launch_step(make_params(b), b->lds_bytes, (hipStream_t)stream, (const int32_t*)d_actions, d_state_out, d_reward_out, d_done_out);
     else if (b->cfg.algo == MBX_ALGO_NRLPSO)

@@ -47,3 +47,10 @@ void nrlpso_launch_steps(const BatchParams& bp, bool cached, hipStream_t stream,
                          int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward, int32_t* d_actions_out, double* d_state_out,
                          double* d_reward_out, uint8_t* d_done_out);
 }  // namespace mbx
+// SAHLPSO (mbx_sahlpso.hpp): likewise in mbx_run_sahlpso.hip
+namespace mbx {
+int64_t sahlpso_lds_doubles(int dim);
+hipError_t sahlpso_prepare(size_t lds_bytes);
+void sahlpso_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state_out);
+void sahlpso_launch_generation(const BatchParams& bp, hipStream_t stream, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
+}  // namespace mbx

@@ -14,3 +14,4 @@ from .gl_pso import GL_PSO
 from .jde21 import JDE21
 from .madde import MadDE
 from .sdms_pso import sDMS_PSO
+from .sahlpso import SAHLPSO

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -308,3 +308,39 @@ if 'sdmspso' in which:
             print(json.dumps({'path': f'{name} bbob d={dim}, {B} instances, one launch per step', 'ms_per_step_median': t * 1e3, 'ms_per_step_min_max': [min(times[name]) * 1e3, max(times[name]) * 1e3],
                               'rows_per_step': rows, 'row_evaluations_per_s': rows * B / t, 'launch_info': b.launch_info()}))
             b.close()
+if 'sahlpso' in which:
+    # SAHLPSO (one mbx_step = one pass over the live particles, each move seeing the one before it: 40 sequential single-row evaluations in ONE launch)
+    # beside sDMS_PSO (one update: 99 rows evaluated side by side) and QLPSO (one particle per env step: one launch per step, and resident with 64 steps
+    # per launch) in the same process, the paths alternating window by window: bbob round-robin, 4096 instances at D = 10 and 1024 at D = 30.  The
+    # budget is so large that SAHLPSO's population stays at 40 and every instance stays live.  Median of 5 windows per path after a warm-up window,
+    # each window ended by a device synchronise (wall times, launch gaps included).
+    from metabox_amd._abi import ALGO_QLPSO, ALGO_SAHLPSO, ALGO_SDMSPSO
+    from metabox_amd.suite import Batch, Suite
+    q = torch.from_numpy(np.load(os.path.join(os.path.dirname(__file__), '..', 'metabox_amd', 'agent_model', 'qlpso_bbob_easy.npz'))['q_table']).cuda()
+    for dim, B in ((10, 4096), (30, 1024)):
+        cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+        tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+        s = Suite(ps)
+        pidx, seeds = np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1
+        bs = Batch(s, ALGO_SAHLPSO, pidx, seeds, 40, 10 ** 9, 10 ** 7, 50, early_stop=False)
+        bd = Batch(s, ALGO_SDMSPSO, pidx, seeds, 99, 100000, 2000, 50)
+        bq = Batch(s, ALGO_QLPSO, pidx, seeds, 30, 10 ** 9, 10 ** 7, 50, early_stop=False)
+        acts = torch.full((B,), 2, dtype=torch.int32, device='cuda')
+        # name: (run n launches, FEs per launch, launches per window)
+        paths = {'k_sahlpso_generation (NP = 40)': (lambda n: [bs.step(None) for _ in range(n)], 40, 16),
+                 'k_sdmspso_update (NP = 99)': (lambda n: [bd.step(None) for _ in range(n)], 99, 16),
+                 'QLPSO one launch per step (NP = 30)': (lambda n: [bq.step(acts) for _ in range(n)], 1, 32),
+                 'QLPSO resident, 64 steps per launch': (lambda n: [bq.qlpso_rollout(q, 64) for _ in range(n)], 64, 2)}
+        for b in (bs, bd, bq): b.reset()
+        times = {k: [] for k in paths}
+        for w in range(6):
+            for k, (fn, fes, n) in paths.items():
+                dt = timed(fn, n)
+                if w: times[k].append(dt / n * 1e6)                  # window 0 warms up
+        assert not bool(bs.done.any()) and int((bs.results()['steps'] > 0).sum()) == B
+        for k, v in times.items():
+            fes = paths[k][1]
+            print(json.dumps({'path': f'{k}, bbob d={dim}, {B} instances', 'us_per_launch_median': float(np.median(v)), 'us_per_fe_median': float(np.median(v)) / fes,
+                              'fes_per_launch': fes, 'windows_us_per_launch': [round(x, 1) for x in v],
+                              'launch_info': (bs if 'sahlpso' in k else bd if 'sdmspso' in k else bq).launch_info()}))
+        for b in (bs, bd, bq): b.close()
