@@ -112,6 +112,7 @@ int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, double* d_f,
 #define MBX_ALGO_SDMSPSO 18 /* src/optimizer/sdms_pso.py           one step = one update (NP FEs), np = 99, dim <= 40, max_fes in (99, 103272] -- classic baseline, no agent (12, 14 and 17 are not assigned and stay rejected) */
 #define MBX_ALGO_DEDQN  16  /* src/optimizer/dedqn_optimizer.py     one step = one trial vector + the landscape analysis (2 NP FEs), np in [4, 128], dim <= 40 */
 #define MBX_ALGO_NRLPSO 19  /* src/optimizer/nrlpso_optimizer.py    one step = one particle (1 FE, 3 when the neighbourhood mutation fires), np in [8, 128], dim <= 40 */
+#define MBX_ALGO_LES    21  /* src/optimizer/les_optimizer.py      one step = one generation (16 FEs) of a learned diagonal ES; np = 16, dim <= 40, max_fes > 16; parameters per instance (mbx_les_set_params) */
 #define MBX_ALGO_SAHLPSO 20 /* src/optimizer/sahlpso.py            one step = one pass over the live particles (NP FEs, NP shrinking 40 -> 4; fewer when the episode ends inside the pass), np = 40, dim <= 40, max_fes > 40 -- classic baseline, no agent */
 
 typedef struct mbx_algo_cfg {
@@ -395,6 +396,8 @@ int mbx_dedqn_rollout(mbx_batch* b, const mbx_dedqn_net* net, int n_steps, int32
  * d_reward_out: SUM of the rewards of the executed steps. */
 int mbx_nrlpso_rollout(mbx_batch* b, const double* d_q_table, int n_steps, int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward,
                        int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream);
+
+/* LES (MBX_ALGO_LES): its two entry points, the per-instance network parameters and the resident rollout, are declared in include/mbx_les.h. */
 
 /* Test / diagnostics: apply one of the device math routines the objectives are built from to n device values.
  * op: 0 log, 1 exp, 2 sin, 3 cos, 4 pow(x, y), 5 T_osz(x) (bbob.py:51-67), 6 T_asy(x; beta_lin = y) (bbob.py:70-82). */

@@ -814,6 +814,63 @@
 #define MBX_SITE_SH_NOISE_B  60u
 #define MBX_SITE_SH_PERM     61u
 
+/* ---------------------------------------------------------------- 18. LES (les_optimizer.py) layouts
+ * A learned evolution strategy: a 68-parameter attention module turns the 16 costs of a generation into recombination weights W, a
+ * 178-parameter MLP turns the evolution paths and a timestamp embedding into per-coordinate learning rates, and a diagonal Gaussian (mu, sigma)
+ * is sampled 16 times per generation.  mbx_reset is init_population (:63-84: D uniforms, 16 D normals, 16 FEs); one generation is one turn of
+ * update()'s loop (:128-178, 16 FEs).  mbx_les_rollout runs n_gens of them in one launch with everything below in LDS; mbx_step (actions = NULL)
+ * is one generation.  The 246 float32 parameters are PER INSTANCE: mbx_les_set_params stores n_sets vectors and one set index per instance.
+ * cfg.np must be 16, 2 <= dim <= 40, max_fes > 16.  state [1] = gbest.  Costs are problem.eval(x) as the reference takes them: noise included,
+ * the optimum NOT subtracted (:71, :147).  Kept behaviour and the float32 summation orders: the header of mbx_les.hpp.
+ * state block: parents[16*D] parents_cost[16] mu[D] sigma[D] Pc[3*D] Ps[3*D] normals[16*D] W[16] alpha[2*D] scalars[16] cost_curve[MBX_LES_CURVE_CAP].
+ *   normals: the standard normals z of the LAST sampling (parents = clip(mu + sigma z)), so that a Philox run can be fed back as a tape;
+ *   W: the attention weights of the last generation, alpha[2 d + k]: its learning rates (k = 0 mu, 1 sigma) -- float32 values held in doubles.
+ *   scalars beyond the common ones (MBX_SC_GEN is evolution_info['generation_counter'] and, plus one, the Philox generation word): init_y of the
+ *   budget route (gbest after the first generation after the reset) and init_y of the running skip_step call (gbest after its first generation).
+ * tape per reset:      mu_u[D] | z[16*D] | noise[3*16]            (draw order :68, :70, the evaluation)
+ * tape per generation: z[16*D] | noise[3*16]                      (:145, the evaluation); np.random.normal(mu, sigma, (16, D)) is mu + sigma * gauss
+ *   element by element in C order.  A tape holds one generation: with a tape n_gens must be 1.
+ * Philox, counter (index, site, gen, episode); reset gen = 0, a generation gen = generation_counter + 1 (the counter BEFORE the generation):
+ *   MBX_SITE_LES_MU(d)       u53(w0,w1) = mu_u[d]                                  (reset only)
+ *   MBX_SITE_LES_NORMAL(p)   box_muller(u53(w0,w1), u53(w2,w3)) = z[2 p], z[2 p + 1]   (16 D is even)
+ *   MBX_SITE_LES_NOISE_A/B(i) the evaluation of row i                                                                                         */
+#define MBX_LES_NP       16
+#define MBX_LES_DIM_MAX  40
+#define MBX_LES_NPARAM   246     /* attn[0:68] = Wq.weight (8x3), Wq.bias, Wk.weight, Wk.bias, Wv.weight (1x3), Wv.bias; mlp[68:246] = ln1.weight (8x19), ln1.bias, ln2.weight (2x8), ln2.bias */
+#define MBX_LES_NATTN    68
+#define MBX_LES_NTS      13      /* timestamps 1, 3, 10, 30, 50, 100, 250, 500, 750, 1000, 1250, 1500, 2000 (:51) */
+#define MBX_LES_TS_MARGIN 64     /* the timestamp table holds generation counters 0 .. max_fes / 16 + MBX_LES_TS_MARGIN; past it (skip_step calls far beyond the budget) the kernel takes the device's tanh */
+#define MBX_LES_TAPE_MU(NP, D)           ((int64_t)0)
+#define MBX_LES_TAPE_Z0(NP, D)           ((int64_t)(D))
+#define MBX_LES_TAPE_NOISE_INIT(NP, D)   ((int64_t)(D) + (int64_t)(NP) * (D))
+#define MBX_LES_TAPE_Z(NP, D)            ((int64_t)0)
+#define MBX_LES_TAPE_NOISE(NP, D)        ((int64_t)(NP) * (D))
+#define MBX_LES_TAPE_STRIDE(NP, D)       ((int64_t)(D) + (int64_t)(NP) * (D) + 3 * (int64_t)(NP))
+#define MBX_LES_ST_PARENTS(NP, D)        ((int64_t)0)
+#define MBX_LES_ST_COST(NP, D)           ((int64_t)(NP) * (D))
+#define MBX_LES_ST_MU(NP, D)             ((int64_t)(NP) * (D) + (NP))
+#define MBX_LES_ST_SIGMA(NP, D)          (MBX_LES_ST_MU(NP, D) + (D))
+#define MBX_LES_ST_PC(NP, D)             (MBX_LES_ST_MU(NP, D) + 2 * (int64_t)(D))
+#define MBX_LES_ST_PS(NP, D)             (MBX_LES_ST_MU(NP, D) + 5 * (int64_t)(D))
+#define MBX_LES_ST_Z(NP, D)              (MBX_LES_ST_MU(NP, D) + 8 * (int64_t)(D))
+#define MBX_LES_ST_W(NP, D)              (MBX_LES_ST_Z(NP, D) + (int64_t)(NP) * (D))
+#define MBX_LES_ST_ALPHA(NP, D)          (MBX_LES_ST_W(NP, D) + (NP))
+#define MBX_LES_ST_SCALARS(NP, D)        (MBX_LES_ST_ALPHA(NP, D) + 2 * (int64_t)(D))
+/* The reference's cost list can grow past n_logpoint + 1: the log point (:170-172) appends once per generation whenever FEs has reached it, unguarded, and
+ * only the closing entry (:174-178) looks at the length (maxFEs = 976, log_interval = 976 // 50 = 19: 52 entries).  The curve of an LES instance therefore has
+ * MBX_LES_CURVE_CAP slots: what an episode that runs to its budget can append (one entry per generation or per log interval, whichever is fewer, plus the first and
+ * the closing one), never fewer than n_logpoint + 1.  mbx_results / mbx_read_public report the first n_logpoint + 1 entries and the true length. */
+#define MBX_LES_GENS(MAXFES)             (((int64_t)(MAXFES) - 1) / MBX_LES_NP)                    /* generations until FEs >= maxFEs */
+#define MBX_LES_FIRES(MAXFES, LOGINT)    (((MBX_LES_GENS(MAXFES) + 1) * MBX_LES_NP / (LOGINT)) < MBX_LES_GENS(MAXFES) ? ((MBX_LES_GENS(MAXFES) + 1) * MBX_LES_NP / (LOGINT)) : MBX_LES_GENS(MAXFES))
+#define MBX_LES_CURVE_CAP(MAXFES, LOGINT, NLOG) (MBX_LES_FIRES(MAXFES, LOGINT) + 2 > (int64_t)(NLOG) + 1 ? MBX_LES_FIRES(MAXFES, LOGINT) + 2 : (int64_t)(NLOG) + 1)
+#define MBX_LES_STATE_DOUBLES(NP, D, CAP) (MBX_LES_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(CAP))
+#define MBX_SC_LES_INIT_Y      10
+#define MBX_SC_LES_CALL_INIT_Y 11
+#define MBX_SITE_LES_MU      62u
+#define MBX_SITE_LES_NORMAL  63u
+#define MBX_SITE_LES_NOISE_A 64u
+#define MBX_SITE_LES_NOISE_B 65u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/mbx.h (libmbx.so).
+"""ctypes binding of the C-ABI in include/mbx.h and include/mbx_les.h (libmbx.so).
 
 This is the stub a maintainer of the reference would add to reach the HIP path (INTEGRATION.md shows it
 in isolation).  The library is built in-tree by ``__graft_entry__.build()`` / ``make -C metabox_amd/csrc``;
@@ -70,6 +70,7 @@ ALGO_SDMSPSO = 18    # (17 is not assigned)
 ALGO_DEDQN = 16
 ALGO_NRLPSO = 19
 ALGO_SAHLPSO = 20
+ALGO_LES = 21
 POLICY_RLEPSO, POLICY_RLPSO = 0, 1
 _ARRAY_FIELDS = ('dshift', 'm1', 'm2', 'v0', 'v1', 'v2', 'py', 'pc', 'pw')
 
@@ -113,7 +114,7 @@ class MbxError(RuntimeError):
 
 
 def load_lib():
-    """Load libmbx.so and declare the prototypes of every symbol in include/mbx.h."""
+    """Load libmbx.so and declare the prototypes of every symbol in include/mbx.h and include/mbx_les.h."""
     global _lib
     if _lib is not None:
         return _lib
@@ -160,6 +161,8 @@ def load_lib():
         'mbx_qlpso_rollout': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
         'mbx_dedqn_rollout': (C.c_int, [vp, C.POINTER(DedqnNet), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
         'mbx_nrlpso_rollout': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+        'mbx_les_set_params': (C.c_int, [vp, vp, C.c_int, vp]),
+        'mbx_les_rollout': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         'mbx_gleet_policy': (C.c_int, [vp, C.POINTER(GleetActor), vp, vp, vp, vp]),
         'mbx_debug_math': (C.c_int, [C.c_int, vp, vp, vp, C.c_int, vp]),
         'mbx_debug_rlepso_draws': (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
@@ -190,6 +193,9 @@ EXPORTED_SYMBOLS = ('mbx_suite_create', 'mbx_suite_destroy', 'mbx_suite_size', '
                     'mbx_qlpso_rollout', 'mbx_dedqn_rollout', 'mbx_nrlpso_rollout', 'mbx_gleet_policy', 'mbx_debug_math', 'mbx_debug_rlepso_draws', 'mbx_batch_launch_info', 'mbx_instance_state_doubles',
                     'mbx_debug_read_state', 'mbx_debug_write_state', 'mbx_debug_clock_probe', 'mbx_debug_clock_mark', 'mbx_debug_clock_slots',
                     'mbx_batch_rebind', 'mbx_read_public', 'mbx_last_error', 'mbx_version')
+
+# the entry points of include/mbx_les.h (LES), beside the 44 of include/mbx.h
+LES_SYMBOLS = ('mbx_les_set_params', 'mbx_les_rollout')
 
 
 def check(rc):

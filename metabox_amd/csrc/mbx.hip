@@ -1,5 +1,5 @@
 // mbx.hip — libmbx.so: kernels' launch code and the C-ABI of include/mbx.h.
-// Build: make -C metabox_amd/csrc  (eight translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
+// Build: make -C metabox_amd/csrc  (ten translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -45,6 +45,7 @@
 #ifdef MBX_SINGLE_TU
 #include "mbx_run_dedqn.hip"           // the DEDQN kernels and their launch code, in this file as well
 #include "mbx_run_nrlpso.hip"          // ... and the NRLPSO ones
+#include "mbx_run_les.hip"
 #endif
 
 using namespace mbx;
@@ -97,6 +98,11 @@ struct mbx_batch {
     bool lde_run_kinds_ok = false;         // LDE: every problem of the batch has an objective kind the LEAN instantiations of k_lde_run build (one tile array: lde_run_kind_ok(.., two = false))
     bool lde_run_kinds_two = false;        // ... a kind the instantiations with the second tile array build (F1-F24)
     bool nrlpso_cached = false;            // NRLPSO: the step kernels keep the NP x NP distance matrix in LDS (MBX_F_NRLPSO_RECOMPUTE clear and the matrix fits)
+    float* d_les_params = nullptr;         // LES: [les_n_sets][246] parameter sets and the set of every instance (mbx_les_set_params; copies)
+    int32_t* d_les_set = nullptr;
+    int les_n_sets = 0;
+    float* d_les_ts = nullptr;             // LES: [les_horizon + 1][13] float32 timestamp embedding tanh(t / timestamp - 1), one row per generation counter
+    int les_horizon = 0;
     bool rollout_per_generation = false;   // MBX_F_ROLLOUT_PER_GENERATION: the mbx_*_rollout entry points take the host-loop route
     int64_t state_stride = 0;
     const double* d_tape = nullptr;
@@ -199,6 +205,12 @@ static AlgoGeom geom_of(const mbx_algo_cfg& c)
         g.sc_off = MBX_SAHL_ST_SCALARS(c.np, c.dim);
         g.tape_stride = MBX_SAHL_TAPE_STRIDE(c.np, c.dim);
         g.lds_doubles = sahlpso_lds_doubles(c.dim);
+        g.state_dim = 1; g.action_dim = 0;
+    } else if (c.algo == MBX_ALGO_LES) {
+        g.state_doubles = MBX_LES_STATE_DOUBLES(c.np, c.dim, MBX_LES_CURVE_CAP(c.max_fes, c.log_interval, c.n_logpoint));
+        g.sc_off = MBX_LES_ST_SCALARS(c.np, c.dim);
+        g.tape_stride = MBX_LES_TAPE_STRIDE(c.np, c.dim);
+        g.lds_doubles = les_lds_doubles_of(c.dim);
         g.state_dim = 1; g.action_dim = 0;
     } else if (c.algo == MBX_ALGO_DEDQN) {
         g.state_doubles = MBX_DEDQN_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
@@ -506,7 +518,7 @@ static int check_cfg(const mbx_algo_cfg* c)
     if (!c) return fail(MBX_E_ARG, "null cfg");
     // the ids this build has kernels for (12, 14 and 17 are not assigned)
     if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21 || c->algo == MBX_ALGO_MADDE || c->algo == MBX_ALGO_DEDQN ||
-          c->algo == MBX_ALGO_SDMSPSO || c->algo == MBX_ALGO_NRLPSO || c->algo == MBX_ALGO_SAHLPSO))
+          c->algo == MBX_ALGO_SDMSPSO || c->algo == MBX_ALGO_NRLPSO || c->algo == MBX_ALGO_SAHLPSO || c->algo == MBX_ALGO_LES))
         return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
     if (c->algo == MBX_ALGO_JDE21 && c->np != MBX_JDE21_NP) return fail(MBX_E_ARG, "JDE21 runs np = %d (160 + 10 rows), not %d", MBX_JDE21_NP, c->np);
     if (c->algo == MBX_ALGO_MADDE) {
@@ -527,6 +539,11 @@ static int check_cfg(const mbx_algo_cfg* c)
         if (c->np != MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO runs np = %d (shrinking to 4), not %d", MBX_SAHL_NP, c->np);
         if (c->dim < 2 || c->dim > MBX_SAHL_DIM_MAX) return fail(MBX_E_ARG, "SAHLPSO runs dim in [2, %d], not %d", MBX_SAHL_DIM_MAX, c->dim);
         if (c->max_fes <= MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO needs max_fes > %d (the initial evaluation), not %d", MBX_SAHL_NP, c->max_fes);
+    } else if (c->algo == MBX_ALGO_LES) {
+        // 16 samples per generation, one lane of wave 0 per row and per dimension; the 16 initial evaluations are spent by mbx_reset
+        if (c->np != MBX_LES_NP) return fail(MBX_E_ARG, "LES runs np = %d, not %d", MBX_LES_NP, c->np);
+        if (c->dim < 2 || c->dim > MBX_LES_DIM_MAX) return fail(MBX_E_ARG, "LES runs dim in [2, %d], not %d", MBX_LES_DIM_MAX, c->dim);
+        if (c->max_fes <= MBX_LES_NP) return fail(MBX_E_ARG, "LES needs max_fes > %d (the initial evaluation), not %d", MBX_LES_NP, c->max_fes);
     } else if (c->algo == MBX_ALGO_DEDQN) {
         // the landscape analysis deals one row per lane of two waves, and LDS holds the population three times over
         if (c->np < 4 || c->np > MBX_DEDQN_NP_MAX) return fail(MBX_E_ARG, "DEDQN runs np in [4, %d], not %d", MBX_DEDQN_NP_MAX, c->np);
@@ -762,6 +779,18 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
         HIP_TRY(nrlpso_prepare(lds));
     } else if (cfg->algo == MBX_ALGO_SAHLPSO) {
         HIP_TRY(sahlpso_prepare(lds));
+    } else if (cfg->algo == MBX_ALGO_LES) {
+        HIP_TRY(les_prepare(lds));
+        {   // the timestamp embedding (les_optimizer.py:110): tanh(t / timestamp - 1) rounded to float32, as the reference's float64 numpy row is when it
+            // enters the MLP; made in extended precision and rounded once to double, then to float, so that it does not depend on the device's tanh
+            static const int stamps[MBX_LES_NTS] = {1, 3, 10, 30, 50, 100, 250, 500, 750, 1000, 1250, 1500, 2000};
+            b->les_horizon = cfg->max_fes / MBX_LES_NP + MBX_LES_TS_MARGIN;
+            std::vector<float> ts((size_t)(b->les_horizon + 1) * MBX_LES_NTS);
+            for (int t = 0; t <= b->les_horizon; ++t)
+                for (int k = 0; k < MBX_LES_NTS; ++k) ts[(size_t)t * MBX_LES_NTS + k] = (float)(double)std::tanh((long double)((double)t / (double)stamps[k] - 1.));
+            HIP_TRY(hipMalloc(&b->d_les_ts, ts.size() * sizeof(float)));
+            HIP_TRY(hipMemcpy(b->d_les_ts, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
     } else if (cfg->algo == MBX_ALGO_QLPSO) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -784,7 +813,7 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
 extern "C" int mbx_batch_destroy(mbx_batch* b)
 {
     if (!b) return MBX_OK;
-    (void)hipFree(b->d_problem_idx); (void)hipFree(b->d_seeds); (void)hipFree(b->d_state); (void)hipFree(b->d_order); (void)hipFree(b->d_pci); (void)hipFree(b->d_scratch); (void)hipFree(b->d_lstm_pack);
+    (void)hipFree(b->d_problem_idx); (void)hipFree(b->d_seeds); (void)hipFree(b->d_state); (void)hipFree(b->d_order); (void)hipFree(b->d_pci); (void)hipFree(b->d_scratch); (void)hipFree(b->d_lstm_pack); (void)hipFree(b->d_les_params); (void)hipFree(b->d_les_set); (void)hipFree(b->d_les_ts);
     delete b;
     return MBX_OK;
 }
@@ -884,6 +913,8 @@ extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
         nrlpso_launch_reset(make_params(b), (hipStream_t)stream, d_state_out);
     else if (b->cfg.algo == MBX_ALGO_SAHLPSO)
         sahlpso_launch_reset(make_params(b), (hipStream_t)stream, d_state_out);
+    else if (b->cfg.algo == MBX_ALGO_LES)
+        les_launch_reset(make_params(b), (hipStream_t)stream, d_state_out);
     else if (b->cfg.algo == MBX_ALGO_QLPSO)
         hipLaunchKernelGGL(k_qlpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
     else if (b->cfg.algo == MBX_ALGO_GLEET)
@@ -910,8 +941,10 @@ extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out
 {
     const bool no_agent = b && (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH || b->cfg.algo == MBX_ALGO_DE || b->cfg.algo == MBX_ALGO_PSO ||
                                 b->cfg.algo == MBX_ALGO_CMAES || b->cfg.algo == MBX_ALGO_GLPSO || b->cfg.algo == MBX_ALGO_JDE21 ||
-                                b->cfg.algo == MBX_ALGO_MADDE || b->cfg.algo == MBX_ALGO_SDMSPSO || b->cfg.algo == MBX_ALGO_SAHLPSO);
+                                b->cfg.algo == MBX_ALGO_MADDE || b->cfg.algo == MBX_ALGO_SDMSPSO || b->cfg.algo == MBX_ALGO_SAHLPSO ||
+                                b->cfg.algo == MBX_ALGO_LES);
     if (!b || (!d_actions && !no_agent)) return fail(MBX_E_ARG, "mbx_step: bad arguments");
+    if (b->cfg.algo == MBX_ALGO_LES) return mbx_les_rollout(b, 1, 0, d_state_out, d_reward_out, d_done_out, stream);   // one generation of the budget route
     if (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH)
         hipLaunchKernelGGL(k_rs_population, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), 0, d_state_out,
                            d_reward_out, d_done_out);
@@ -1297,6 +1330,48 @@ extern "C" int mbx_nrlpso_rollout(mbx_batch* b, const double* d_q_table, int n_s
     if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_nrlpso_rollout: a replay tape holds one step");
     nrlpso_launch_steps(make_params(b), b->nrlpso_cached, (hipStream_t)stream, nullptr, d_q_table, n_steps, d_traj_actions, d_traj_state, d_traj_reward,
                         d_actions_out, d_state_out, d_reward_out, d_done_out);
+    HIP_TRY(hipGetLastError());
+    return MBX_OK;
+}
+
+extern "C" int mbx_les_set_params(mbx_batch* b, const float* d_params, int n_sets, const int32_t* d_set_of_instance)
+{
+    if (!b || !d_params || n_sets < 1) return fail(MBX_E_ARG, "mbx_les_set_params: bad arguments");
+    if (b->cfg.algo != MBX_ALGO_LES) return fail(MBX_E_UNSUPPORTED, "mbx_les_set_params: the batch is not an LES batch");
+    HIP_TRY(hipDeviceSynchronize());
+    if (d_set_of_instance) {                                        // an index outside the table would be read out of bounds on the device
+        std::vector<int32_t> h(b->B);
+        HIP_TRY(hipMemcpy(h.data(), d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < b->B; ++i)
+            if (h[i] < 0 || h[i] >= n_sets) return fail(MBX_E_ARG, "mbx_les_set_params: set_of_instance[%d] = %d outside [0, %d)", i, h[i], n_sets);
+    }
+    (void)hipFree(b->d_les_params); (void)hipFree(b->d_les_set);
+    b->d_les_params = nullptr; b->d_les_set = nullptr; b->les_n_sets = 0;
+    HIP_TRY(hipMalloc(&b->d_les_params, (size_t)n_sets * MBX_LES_NPARAM * sizeof(float)));
+    HIP_TRY(hipMemcpy(b->d_les_params, d_params, (size_t)n_sets * MBX_LES_NPARAM * sizeof(float), hipMemcpyDeviceToDevice));
+    if (d_set_of_instance) {
+        HIP_TRY(hipMalloc(&b->d_les_set, (size_t)b->B * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(b->d_les_set, d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToDevice));
+    }
+    b->les_n_sets = n_sets;
+    return MBX_OK;
+}
+
+extern "C" int mbx_les_rollout(mbx_batch* b, int n_gens, int skip, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
+{
+    if (!b) return fail(MBX_E_ARG, "mbx_les_rollout: null batch");
+    if (b->cfg.algo != MBX_ALGO_LES) return fail(MBX_E_UNSUPPORTED, "mbx_les_rollout: the batch is not an LES batch");
+    if (!b->d_les_params) return fail(MBX_E_ARG, "LES: no parameters yet, call mbx_les_set_params first");
+    if (n_gens < 1 || (skip != 0 && skip != 1)) return fail(MBX_E_ARG, "mbx_les_rollout: n_gens must be >= 1 and skip 0 or 1");
+    if (b->d_tape && n_gens != 1) return fail(MBX_E_ARG, "mbx_les_rollout: a replay tape holds one generation");
+    const BatchParams bp = make_params(b);
+    if (b->rollout_per_generation)
+        for (int g = 0; g < n_gens; ++g)
+            les_launch_run(bp, (hipStream_t)stream, b->d_les_params, b->d_les_set, b->les_n_sets, b->d_les_ts, b->les_horizon, 1, skip, g, n_gens, d_state_out,
+                           d_reward_out, d_done_out);
+    else
+        les_launch_run(bp, (hipStream_t)stream, b->d_les_params, b->d_les_set, b->les_n_sets, b->d_les_ts, b->les_horizon, n_gens, skip, 0, n_gens, d_state_out,
+                       d_reward_out, d_done_out);
     HIP_TRY(hipGetLastError());
     return MBX_OK;
 }

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/mbx.h"
+#include "../../include/mbx_les.h"
 #include "../../include/mbx_layout.h"
 #include "mbx_math.hpp"
 

@@ -54,3 +54,12 @@ hipError_t sahlpso_prepare(size_t lds_bytes);
 void sahlpso_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state_out);
 void sahlpso_launch_generation(const BatchParams& bp, hipStream_t stream, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
 }  // namespace mbx
+// LES (mbx_les.hpp): likewise in mbx_run_les.hip
+namespace mbx {
+int64_t les_lds_doubles_of(int dim);
+hipError_t les_prepare(size_t lds_bytes);
+void les_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state_out);
+// skip = 0: up to n_gens generations under the budget / early-stop end rule; skip = 1: steps step0 .. step0 + n_gens - 1 of a skip_step call of skip_total steps
+void les_launch_run(const BatchParams& bp, hipStream_t stream, const float* d_params, const int32_t* d_set_of, int n_sets, const float* d_ts, int horizon,
+                    int n_gens, int skip, int step0, int skip_total, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
+}  // namespace mbx

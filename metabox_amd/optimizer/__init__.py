@@ -9,6 +9,7 @@ from .gleet_optimizer import GLEET_Optimizer
 from .qlpso_optimizer import QLPSO_Optimizer
 from .dedqn_optimizer import DEDQN_Optimizer
 from .nrlpso_optimizer import NRLPSO_Optimizer
+from .les_optimizer import LES_Optimizer
 from .classic import DEAP_CMAES, DEAP_DE, DEAP_PSO
 from .gl_pso import GL_PSO
 from .jde21 import JDE21

@@ -213,6 +213,27 @@ class Batch:
                                                _ptr(self._iactions), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
         return (self.state, self.reward, self.done, self._iactions, traj) if trajectory else (self.state, self.reward, self.done, self._iactions)
 
+    def les_set_params(self, params, set_of_instance=None):
+        """LES: the parameter sets of the batch and the set of every instance (``mbx_les_set_params``).  params: [n_sets, 246] (or [246]) in the
+        reference's ``vector2nn`` order, attention first; float64 input is cast to float32 here, as the reference's ``torch.FloatTensor`` does.
+        set_of_instance: [B] integers, or None = set 0 for every instance.  The library keeps copies."""
+        p = np.asarray(params.detach().cpu().numpy() if torch.is_tensor(params) else params)
+        p = np.ascontiguousarray(p.reshape(-1, 246).astype(np.float32))
+        pd = torch.from_numpy(p).to(self.device)
+        sd = None
+        if set_of_instance is not None:
+            si = np.ascontiguousarray(set_of_instance, dtype=np.int32)
+            assert si.shape == (self.B,)
+            sd = torch.from_numpy(si).to(self.device)
+        _abi.check(self.lib.mbx_les_set_params(self._h, _ptr(pd), int(p.shape[0]), _ptr(sd)))
+
+    def les_rollout(self, n_gens, skip=False):
+        """LES generations in ONE launch with the population, the evolution paths and every instance's own parameters on chip in between
+        (``mbx_les_rollout``).  skip=False: up to `n_gens` generations under the budget / early-stop end rule, finished instances frozen; skip=True:
+        the reference's ``skip_step = n_gens`` call.  Returns (state = gbest [B, 1], reward = (init_y - gbest) / init_y, done)."""
+        _abi.check(self.lib.mbx_les_rollout(self._h, int(n_gens), int(bool(skip)), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
+        return self.state, self.reward, self.done
+
     def dedqn_rollout(self, weights, n_steps, trajectory=False):
         """`n_steps` DEDQN env steps of every instance in ONE launch, the 4 -> 10 -> 10 -> 3 Q-network evaluated in the kernel and the population
         on chip in between (``mbx_dedqn_rollout``); bit-identical to `n_steps` one-step calls and to step() fed the same actions.  weights: packed

@@ -2475,7 +2475,190 @@ def gen_sahlpso():
         assert os.path.getsize(path) <= 620 * 1024, (path, os.path.getsize(path))
 
 
-SECTIONS = {'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+class _LesTie(Exception):
+    pass
+
+
+def load_les_checkpoint(path):
+    """A shipped LES_Agent checkpoint without the `cmaes` package: classes of the cmaes / agent / config modules are fabricated empty, the
+    pickled attribute dictionaries are all that is read."""
+    class U(pickle.Unpickler):
+        def find_class(self, module, name):
+            if module.split('.')[0] in ('cmaes', 'agent', 'config'):
+                return type(name, (), {})
+            return super().find_class(module, name)
+    with open(path, 'rb') as f:
+        return U(f).load()
+
+
+def run_les_episode(problem, seed, best_x, config, calls, keep_every=1):
+    """Reference LES: init_population, then one update() per entry of `calls` (None = the budget route, n = skip_step n) with the parameter vector
+    best_x, seeded with np.random.seed / torch.manual_seed.  The reference's methods are wrapped from here (its text is untouched): the state
+    BEFORE every generation (mu, sigma, Pc, Ps, parents, costs, gbest, FEs, generation counter) with the W and alpha that generation computes, and
+    the state after the last one.  keep_every > 1 thins the record to every keep_every-th generation, the last one and the final state (the costs are kept
+    for every generation).  Raises
+    _LesTie if two costs of one generation are closer than 1e-9 relative."""
+    from optimizer.les_optimizer import LES_Optimizer
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    opt = LES_Optimizer(config)
+    problem.reset()
+    opt.init_population(problem)
+    gens, io = [], {}
+
+    def snap():
+        e = opt.evolution_info
+        c = np.sort(np.asarray(e['parents_cost'], dtype=np.float64))
+        if np.any(np.diff(c) <= 1e-9 * np.abs(c[1:])):
+            raise _LesTie(f'generation {len(gens)}: costs closer than 1e-9 relative')
+        return dict(mu=np.array(e['mu']), sigma=np.array(e['sigma']), Pc=np.array(e['Pc']), Ps=np.array(e['Ps']), parents=np.array(e['parents']),
+                    costs=np.array(e['parents_cost']), gbest=float(e['gbest']), fes=int(opt.FEs), t=int(e['generation_counter']), cost_len=len(opt.cost))
+    real_feat, real_attn, real_mlp = opt.cal_attn_feature, opt.attn.forward, opt.mlp.forward
+
+    def feat():
+        gens.append(snap())
+        x = real_feat()
+        gens[-1]['improved'] = bool(x[:, 2].any())
+        io.setdefault('attn_in', []).append(x.numpy().copy())
+        return x
+
+    def attn(x):
+        w = real_attn(x)
+        gens[-1]['W'] = w.detach().numpy().copy()
+        return w
+
+    def mlp(x):
+        a = real_mlp(x)
+        gens[-1]['alpha'] = a.detach().numpy().copy()
+        io.setdefault('mlp_in', []).append(x.numpy().copy())
+        return a
+    opt.cal_attn_feature, opt.attn.forward, opt.mlp.forward = feat, attn, mlp
+    rets, lens, ngen = [], [], []
+    for skip in calls:
+        action = {'attn': best_x[:68], 'mlp': best_x[68:]}
+        if skip is not None:
+            action['skip_step'] = skip
+        n0 = len(gens)
+        gb, rw, end, _ = opt.update(action, problem)
+        rets.append((float(gb), float(rw), float(end)))
+        lens.append(len(opt.cost))
+        ngen.append(len(gens) - n0)
+    final = snap()
+    G = len(gens)
+    keep = [g for g in range(G) if g % keep_every == 0 or g == G - 1]
+    states = [gens[g] for g in keep] + [final]
+    lo, hi = problem.lb, problem.ub
+    rec = {'gens': np.array(keep + [G], dtype=np.int64), 'calls': np.array([-1 if c is None else c for c in calls], dtype=np.int64),
+           'call_ret': np.array(rets), 'call_len': np.array(lens, dtype=np.int64), 'call_gens': np.array(ngen, dtype=np.int64),
+           'cost': np.array(opt.cost, dtype=np.float64), 'fes_end': np.int64(opt.FEs), 'next_rand': np.float64(np.random.rand()),
+           'improved_any': np.bool_(any(g['improved'] for g in gens)),
+           'nclip': np.int64(sum(int(np.sum((g['parents'] == lo) | (g['parents'] == hi))) for g in gens + [final])),
+           'W': np.stack([gens[g]['W'] for g in keep]), 'alpha': np.stack([gens[g]['alpha'] for g in keep])}
+    for k in ('mu', 'sigma', 'Pc', 'Ps', 'parents', 'costs', 'gbest', 'fes', 't', 'cost_len'):
+        rec[k] = np.array([s[k] for s in states])
+    if keep_every > 1:                                               # a thinned record still holds the costs of EVERY generation: the restatement is fed them
+        rec['costs_all'] = np.array([g['costs'] for g in gens + [final]])
+    return rec, io
+
+
+def gen_les():
+    """LES (src/optimizer/les_optimizer.py, src/agent/les_agent.py).  les_policy.npz: best_x of the three shipped checkpoint20s, best_x / x_population
+    and the recorded state of the cmaes.CMA meta-optimizer of the three checkpoint0s (read without the cmaes package: load_les_checkpoint), and a few
+    input / output pairs of the reference's two modules.  les_traces*.npz: whole reference episodes with the shipped best_x (run_les_episode); the
+    numpy draws are NOT stored, the tests regenerate them from the seed.  An episode is kept only if no two costs of a generation are closer than
+    1e-9 relative; otherwise the next seed is tried."""
+    scratch = tempfile.mkdtemp()
+    root = os.path.join(ref_import.REF_SRC, 'agent_model', 'rollout')
+    sets = {'bbob': 'bbob_easy', 'bbob-noisy': 'bbob-noisy_easy', 'protein': 'protein_easy'}
+    pol, best = {}, {}
+    cma_keys = ('_weights', '_mu_eff', '_c1', '_cmu', '_cc', '_c_sigma', '_d_sigma', '_chi_n', '_cm', '_mean', '_sigma', '_n_dim', '_popsize', '_mu')
+    for suite, d in sets.items():
+        a20 = load_les_checkpoint(os.path.join(root, d, 'LES_Agent', 'checkpoint20.pkl')).__dict__
+        a0 = load_les_checkpoint(os.path.join(root, d, 'LES_Agent', 'checkpoint0.pkl')).__dict__
+        best[suite] = np.array(a20['best_x'], dtype=np.float64)
+        pol[f'{suite}/best_x'] = best[suite]
+        pol[f'{suite}/ckpt0/best_x'] = np.array(a0['best_x'], dtype=np.float64)
+        pol[f'{suite}/ckpt0/x_population'] = np.array(a0['x_population'], dtype=np.float64)
+        for k in cma_keys:
+            pol[f'{suite}/ckpt0/cma{k}'] = np.array(a0['optimizer'].__dict__[k], dtype=np.float64)
+        assert best[suite].shape == (246,) and pol[f'{suite}/ckpt0/x_population'].shape == (16, 246)
+    probs = {}
+
+    def pick(suite, dim, fid):
+        if suite == 'protein':
+            if 'protein' not in probs:
+                probs['protein'] = protein_problems()[0]
+            return probs['protein'][fid]
+        if (suite, dim) not in probs:
+            tr, te, _ = all_problems(suite, dim)
+            probs[(suite, dim)] = {fid_of(p): p for p in tr + te}
+        return probs[(suite, dim)][int(fid)]
+
+    def config_for(suite, dim, max_fes):
+        c = ref_import.ref_config(['--problem', suite] + ([] if suite == 'protein' else ['--dim', str(dim)]), scratch)
+        if max_fes is not None:
+            c.maxFEs = max_fes
+            c.log_interval = c.maxFEs // c.n_logpoint
+        return c
+    # (suite, dim, function, first seed, maxFEs or None = the suite's own, calls, keep_every, tag)
+    jobs = [('bbob', 10, 1, 71, 16 * 61, [None], 1, 'budget'), ('bbob', 10, 8, 72, 16 * 51, [None], 1, 'budget'), ('bbob', 10, 15, 73, 16 * 45, [None], 1, 'budget'),
+            ('bbob', 10, 21, 74, 16 * 56, [None], 1, 'budget'), ('bbob-noisy', 10, 101, 75, 16 * 47, [None], 1, 'budget'),
+            ('bbob-noisy', 10, 102, 76, 16 * 53, [None], 1, 'budget'), ('bbob-noisy', 10, 103, 77, 16 * 58, [None], 1, 'budget'),
+            ('protein', 12, '1AVX_1', 78, None, [None], 1, 'budget'), ('bbob', 30, 15, 79, 16 * 41, [None], 1, 'budget'),
+            ('bbob', 40, 8, 80, 16 * 43, [None], 1, 'budget'), ('bbob', 10, 1, 81, None, [None], 25, 'full'), ('bbob', 10, 21, 82, None, [None], 25, 'full'),
+            ('bbob', 10, 15, 83, None, [50], 1, 'skip50'), ('bbob', 10, 8, 84, None, [1] * 60, 1, 'skip1x60')]
+    data, cases, ios = {}, [], None
+    for suite, dim, fid, seed0, max_fes, calls, keep_every, tag in jobs:
+        config = config_for(suite, dim, max_fes)
+        for seed in range(seed0, seed0 + 100000, 100):
+            try:
+                rec, io = run_les_episode(pick(suite, dim, fid), seed, best[suite], config, calls, keep_every)
+                break
+            except _LesTie as e:
+                print(f'  {suite}/{dim}/{fid} seed {seed}: {e}; next seed')
+        key = f'{suite}/{dim}/{fid}/{seed}/{tag}'
+        cases.append(key)
+        for k, v in rec.items():
+            data[f'{key}/{k}'] = v
+        data[f'{key}/max_fes'] = np.int64(config.maxFEs)
+        data[f'{key}/log_interval'] = np.int64(config.log_interval)
+        data[f'{key}/n_logpoint'] = np.int64(config.n_logpoint)
+        if ios is None:
+            ios = io
+        print(key, 'generations', int(rec['gens'][-1]), 'recorded', len(rec['gens']), 'fes', int(rec['fes_end']), 'of', config.maxFEs, 'curve', len(rec['cost']),
+              'clipped', int(rec['nclip']), 'gbest', rec['gbest'][-1], 'ret', rec['call_ret'][-1])
+    # ---- the set as a whole covers the quirks
+    assert not any(bool(data[f'{c}/improved_any']) for c in cases)                       # improved is all-false in every generation
+    assert any(int(data[f'{c}/nclip']) > 0 for c in cases)                               # a coordinate clipped
+    assert len(data[[c for c in cases if c.endswith('skip1x60')][0] + '/cost']) == 51    # the closing log fills, then overwrites the end of cost
+    assert all(int(data[f'{c}/fes_end']) >= int(data[f'{c}/max_fes']) for c in cases if c.endswith(('budget', 'full')))
+    for g in (0, 7, 20):
+        pol[f'io/attn_in/{g}'], pol[f'io/mlp_in/{g}'] = ios['attn_in'][g], ios['mlp_in'][g]
+        pol[f'io/W/{g}'], pol[f'io/alpha/{g}'] = data[f'{cases[0]}/W'][g], data[f'{cases[0]}/alpha'][g]
+    np.savez_compressed(os.path.join(OUT, 'les_policy.npz'), **pol)
+    print('les_policy.npz', os.path.getsize(os.path.join(OUT, 'les_policy.npz')))
+    data['cases'] = np.array(cases)
+    parts, sizes, owner = [], [], {}
+    for key in data:
+        prefix = '/'.join(key.split('/')[:5])
+        if prefix not in owner:
+            need = sum(data[k].nbytes for k in data if '/'.join(k.split('/')[:5]) == prefix)
+            for n in range(len(parts) + 1):
+                if n == len(parts):
+                    parts.append({}); sizes.append(0)
+                if sizes[n] + need <= 900 * 1024 or sizes[n] == 0:
+                    break
+            owner[prefix] = n
+            sizes[n] += need
+        parts[owner[prefix]][key] = data[key]
+    for n, d in enumerate(parts):
+        path = os.path.join(OUT, 'les_traces%s.npz' % ('' if n == 0 else '_' + 'abcdefgh'[n]))
+        np.savez_compressed(path, **d)
+        print(os.path.basename(path), os.path.getsize(path))
+        assert os.path.getsize(path) <= 1000 * 1024, (path, os.path.getsize(path))
+
+
+SECTIONS = {'les': gen_les, 'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

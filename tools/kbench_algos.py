@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso|les] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -344,3 +344,43 @@ if 'sahlpso' in which:
                               'fes_per_launch': fes, 'windows_us_per_launch': [round(x, 1) for x in v],
                               'launch_info': (bs if 'sahlpso' in k else bd if 'sdmspso' in k else bq).launch_info()}))
         for b in (bs, bd, bq): b.close()
+if 'les' in which:
+    # LES (one generation = 16 FEs): the resident kernel with 50 generations per launch -- a skip_step = 50 call, what one meta-generation of LES_Agent.train_batch
+    # runs -- beside one launch per generation (MBX_F_ROLLOUT_PER_GENERATION: same call, same outputs) and beside SAHLPSO's pass (40 single-row evaluations per launch)
+    # in the same process, the paths alternating window by window: bbob round-robin, 4096 instances at D = 10 and 1024 at D = 30, every instance with one of 16
+    # parameter sets drawn as CMA-ES draws its first population (N(0, 0.1^2)).  Median of 5 windows per path after a warm-up window, each window ended by a device
+    # synchronise (wall times, launch gaps included).
+    from metabox_amd._abi import ALGO_LES, ALGO_SAHLPSO, F_ROLLOUT_PER_GENERATION
+    from metabox_amd.suite import Batch, Suite
+    sets = np.random.RandomState(0).randn(16, 246) * 0.1
+    for dim, B in ((10, 4096), (30, 1024)):
+        cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+        tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+        s = Suite(ps)
+        pidx, seeds = np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1
+        br = Batch(s, ALGO_LES, pidx, seeds, 16, 20000, 400, 50)
+        bg = Batch(s, ALGO_LES, pidx, seeds, 16, 20000, 400, 50, flags=F_ROLLOUT_PER_GENERATION)
+        bs = Batch(s, ALGO_SAHLPSO, pidx, seeds, 40, 10 ** 9, 10 ** 7, 50, early_stop=False)
+        for b in (br, bg): b.les_set_params(sets, (np.arange(B) // len(ps)) % 16)
+        def les(b):
+            def run(n):
+                for _ in range(n):
+                    b.reset(); b.les_rollout(50, skip=True)
+            return run
+        # name: (run n launches, generations per launch, FEs per generation, launches per window)
+        paths = {'k_les_run resident, 50 generations per launch': (les(br), 50, 16, 4),
+                 'k_les_run one launch per generation': (les(bg), 50, 16, 4),
+                 'k_sahlpso_generation (NP = 40)': (lambda n: [bs.step(None) for _ in range(n)], 1, 40, 16)}
+        bs.reset()
+        times = {k: [] for k in paths}
+        for w in range(6):
+            for k, (fn, gens, fes, n) in paths.items():
+                dt = timed(fn, n)
+                if w: times[k].append(dt / n / gens * 1e6)           # window 0 warms up
+        assert torch.equal(br.state, bg.state) and torch.equal(br.results()['cost'], bg.results()['cost'])
+        for k, v in times.items():
+            gens, fes = paths[k][1], paths[k][2]
+            print(json.dumps({'path': f'{k}, bbob d={dim}, {B} instances', 'us_per_generation_median': float(np.median(v)), 'us_per_fe_median': float(np.median(v)) / fes,
+                              'generations_per_call': gens, 'windows_us_per_generation': [round(x, 1) for x in v],
+                              'launch_info': (bs if 'sahlpso' in k else br).launch_info()}))
+        for b in (br, bg, bs): b.close()
