@@ -1030,7 +1030,14 @@ static int check_gauss_mlp(const mbx_batch* b, const mbx_gauss_mlp* net, const c
     if (net->in_dim != b->state_dim || net->out_dim != b->action_dim || net->h1 < 1 || net->h2 < 1)
         return fail(MBX_E_ARG, "%s: network dimensions do not match the batch (state_dim -> h1 -> h2 -> action_dim)", who);
     *lds = gauss_mlp_lds_bytes(net->in_dim, net->h1, net->h2, net->out_dim);
-    if (*lds > 64 * 1024) return fail(MBX_E_UNSUPPORTED, "%s: the weights do not fit the 64 KB LDS budget of this kernel", who);
+    if (*lds > (size_t)max_lds_bytes()) return fail(MBX_E_UNSUPPORTED, "%s: the weights need %zu B of LDS (> %d)", who, *lds, max_lds_bytes());
+    return MBX_OK;
+}
+
+// k_gauss_mlp_policy with more than the default 64 KB of dynamic LDS (hidden layers wider than the shipped actors') has to ask for it
+static int gauss_mlp_lds_attr(size_t lds)
+{
+    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_gauss_mlp_policy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return MBX_OK;
 }
 
@@ -1047,6 +1054,7 @@ extern "C" int mbx_gauss_policy(mbx_batch* b, const mbx_gauss_mlp* net, const do
     size_t lds = 0;
     if (const int rc = check_gauss_mlp(b, net, "mbx_gauss_policy", &lds)) return rc;
     if (!d_state || !d_actions) return fail(MBX_E_ARG, "mbx_gauss_policy: bad arguments");
+    if (const int rc = gauss_mlp_lds_attr(lds)) return rc;
     const GaussMlp g{net->d_weights, net->in_dim, net->h1, net->h2, net->out_dim, net->min_sigma, net->max_sigma, net->variant};
     hipLaunchKernelGGL(k_gauss_mlp_policy, dim3(policy_blocks(b->B)), dim3(kThreads), lds, (hipStream_t)stream, make_params(b), g,
                        d_state, d_actions, d_mu_sigma, 0);
@@ -1115,6 +1123,7 @@ extern "C" int mbx_rlepso_policy_table(mbx_batch* b, const mbx_gauss_mlp* net, f
     if (const int rc = check_gauss_mlp(b, net, "mbx_rlepso_policy_table", &lds)) return rc;
     if (!d_table || net->in_dim != 1 || b->cfg.algo != MBX_ALGO_RLEPSO) return fail(MBX_E_ARG, "mbx_rlepso_policy_table: bad arguments");
     const int rows = mbx_rlepso_policy_table_rows(b);
+    if (const int rc = gauss_mlp_lds_attr(lds)) return rc;
     const GaussMlp g{net->d_weights, net->in_dim, net->h1, net->h2, net->out_dim, net->min_sigma, net->max_sigma, net->variant};
     hipLaunchKernelGGL(k_gauss_mlp_policy, dim3(policy_blocks(rows)), dim3(kThreads), lds, (hipStream_t)stream, make_params(b), g,
                        (const double*)nullptr, (float*)nullptr, d_table, rows);
