@@ -311,6 +311,7 @@ def _dq_lib():
         L.orc_dq_reset.argtypes = [C.c_void_p, _dp, _dp]
         L.orc_dq_step.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
         L.orc_dq_state.argtypes = [C.c_void_p, _dp]
+        L.orc_dq_set_state.argtypes = [C.c_void_p, _dp]
         L._dq_ready = True
     return L
 
@@ -355,6 +356,12 @@ class DqOracle:
         out = np.empty(dq_state_doubles(self.cfg.np, self.cfg.dim, self.cfg.n_logpoint))
         _dq_lib().orc_dq_state(self._h, _p(out))
         return out
+
+    def set_state(self, block):
+        """Adopt a state block (the layout state() returns); the gbest / prebest words are read only where their view flag is 0."""
+        block = np.ascontiguousarray(block, dtype=np.float64)
+        assert block.shape == (dq_state_doubles(self.cfg.np, self.cfg.dim, self.cfg.n_logpoint),)
+        _dq_lib().orc_dq_set_state(self._h, _p(block))
 
 
 class DqTapeFeeder:
