@@ -225,6 +225,9 @@ __device__ unsigned long long g_phase_cycles[8192 * 16];         // [block][phas
 #ifndef MBX_FDR_UNROLL
 #define MBX_FDR_UNROLL 4
 #endif
+#ifndef MBX_FDR_UNROLL_D40
+#define MBX_FDR_UNROLL_D40 2        // the D = 40 resident kernels (1024 threads; config 5)
+#endif
 #ifndef MBX_FDR_OWN_AT
 #define MBX_FDR_OWN_AT 64           // flagged items per swarm and generation above which every lane settles its own items instead of one wave per coordinate (fdr_pass)
 #endif
@@ -395,7 +398,7 @@ __device__ __forceinline__ int fdr_settle(const RlLds& L, const int* __restrict_
 //  * j == i contributes the ratio 0, every particle with a larger pbest a positive one: the minimum is attained
 //    among the strictly better particles (negative ratios) if there are any, otherwise it is 0 and np.argmin
 //    returns the lowest index with pbest_j == pbest_i.  Only the `nless` better particles are scanned, in
-//    ascending-cost order (ORDER / NC), halving the O(NP^2 D) work on average.
+//    ascending-cost order (ORDER / NC), halving the O(NP^2 D) work on average (a wave runs on to the highest rank among its items, see `bound` below).
 //  * ratios are compared by cross-multiplication (denominators >= 1e-5 > 0): a_j/b_j < a*/b* <=> a_j b* < a* b_j.
 //    The reference compares ROUNDED quotients; the two orders can differ only where two candidates' quotients are within an ulp or two of each other
 //    (tests/test_fdr_ties.py: 49 % / 9 % of crafted pairs 0 / 1 ulp apart resolve differently by cross-multiplication alone).
@@ -407,17 +410,27 @@ __device__ __forceinline__ int fdr_settle(const RlLds& L, const int* __restrict_
 //    are adjacent in the (cost, index) order, so the strict `<` keeps the lower index like np.argmin.
 // Exact float64 scan for W adjacent coordinates d0 .. d0+W-1 of the particle of pbest-rank rk; the exemplar's rank per coordinate goes to kb; returns the near-tie flag.
 // The candidates' costs are read from NCS (= NC but for the rows rl_mark_copies took out of the scan).
+//  * The loops run to ONE trip count per wave, `bound` (wave-uniform, >= the nless of every lane of the wave, <= NP: fdr_pass passes the highest rank among the
+//    wave's items, and nless(rank) <= rank), not to the lane's own nless: counter, loop test and the rank k handed to the takes live on the scalar unit, and the
+//    remainder is (bound - 1) mod UN scalar-controlled steps.  (Per-lane trip counts made the loop a divergent one -- a vector compare, a vector counter and EXEC
+//    bookkeeping per group, 22 instead of 18 instructions per remainder candidate -- and bought nothing: a lane that is done is masked off while the wave finishes.)
+//    A lane that scans past its nless gets the same (ab, bb, kb) and the same flag:
+//    - never taken: positions are in (cost, index) order and rows taken out read 1e300, so a candidate at k >= nless has au = NCS[k] - f_i >= 0.  A lane with
+//      nless > 0 holds a running best with ab < 0 and bb, b >= 1e-5: dif = fma(au, bb, -fl(ab b)) >= 0, and the strict test 0 > dif fails.  A lane with nless == 0
+//      holds ab = a_0 = 0: dif = au bb >= 0 again; its kb stays 0 = nless, the rank of the exemplar when nobody is strictly better.
+//    - flag unchanged: a running best has won against candidate 0, so |ab| >= |a_0| bb / b_0 >= |a_0| 1e-5 / range (up to an ulp per comparison), and an extra
+//      candidate contributes |dif| >= |ab| b >= |a_0| 1e-10 / range ~ |a_0| 2^-36.5 (range ~ 10) against the threshold |a_0| range 2^-49 ~ |a_0| 2^-45.7: a factor
+//      of 2^9 above it (tests/test_fdr_bound.py asserts the margin on real and crafted swarms).  Only a lane with nless == 0 (a_0 = 0: threshold 0, dif = 0 at
+//      its cost-ties) has its flag forced to false, which is what its early return used to say.
+//    With equal costs the bound overshoots nless by the tied particles only.  No position at or beyond NP is read: the bound is at most a rank.
 // UN: candidates per unrolled group (MBX_FDR_UNROLL = 4 everywhere but config 5's resident kernel: 1024 threads, D = 40: 2 / 4 / 8 -> 1.619 / 1.641 / 1.703 ms per
-// generation; the headline kernel: 2 / 3 / 4 / 6 / 8 -> 119.9 / 117.1 / 116.5 / 117.5 / 121.6 us)
+// generation; the headline kernel: 2 / 3 / 4 / 6 / 8 -> 119.9 / 117.1 / 116.5 / 117.5 / 121.6 us; both with per-lane trip counts)
 // range: an upper bound of |p_jd - p_id| + 1e-5 (ub - lb + 1e-5), used by the near-tie flag only
 template <int W, int UN = MBX_FDR_UNROLL, bool TIE = true>
-__device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0, int nless, int kb[W], double range = 0.)
+__device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0, int nless, int bound, int kb[W], double range = 0.)
 {
-#pragma unroll
-    for (int q = 0; q < W; ++q) kb[q] = nless;                   // rank of the exemplar when nobody is strictly better
-    if (nless <= 0) return false;
 #ifdef MBX_ABLATE_FDR_SCAN
-    nless = 1;                                                    // instruction-budget builds: the head and the tail of the scan without its loops
+    bound = 1;                                                    // instruction-budget builds: the head and the tail of the scan without its loops
 #endif
     const double fi = L.NC[rk];
     double pp[W], ab[W], bb[W];
@@ -444,7 +457,7 @@ __device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0,
         tiem = fdr_min3_abs(tiem, f64_hi_as_f32(difv[0]), f64_hi_as_f32(difv[W - 1]));
     };
     int k = 1;
-    for (; k + UN <= nless; k += UN) {
+    for (; k + UN <= bound; k += UN) {
         double a[UN], x[UN][W];
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
@@ -455,19 +468,19 @@ __device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0,
 #pragma unroll
         for (int u = 0; u < UN; ++u) step(a[u] - fi, x[u], k + u);
     }
-    for (; k < nless; ++k) {
+    for (; k < bound; ++k) {
         double x[W];
 #pragma unroll
         for (int q = 0; q < W; ++q) x[q] = col[k * D + q];
         step(L.NCS[k] - fi, x, k);
     }
     const double thr = fabs(a0) * range * 0x1p-49;               // |a* b_j| <= |a_0| x range for every pair of the item
-    return !(tiem > f64_hi_as_f32(thr) * 1.0000005f);
+    return nless > 0 && !(tiem > f64_hi_as_f32(thr) * 1.0000005f);
     } else {
     // unrolled by hand (the compiler does not unroll around the inline assembly of fdr_take); the LDS reads of a group are
     // issued before its first comparison
     int k = 1;
-    for (; k + UN <= nless; k += UN) {
+    for (; k + UN <= bound; k += UN) {
         double a[UN], x[UN][W];
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
@@ -485,7 +498,7 @@ __device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0,
             }
         }
     }
-    for (; k < nless; ++k) {
+    for (; k < bound; ++k) {
         const double a = L.NCS[k] - fi;
 #pragma unroll
         for (int q = 0; q < W; ++q) {
@@ -544,7 +557,8 @@ __device__ __noinline__ void fdr_settle_own(const double* __restrict__ NC, const
 }
 
 // The FDR pass of a generation: every (rank, coordinate pair) item of the population -> KB[rank * D + d] = rank of its exemplar.  Items are visited in
-// pbest-rank order so that the lanes of a wave own particles of similar rank, i.e. similar trip counts; the trip count grows with the rank and wave w of
+// pbest-rank order so that the lanes of a wave own particles of similar rank: the wave scans to ONE trip count, its highest rank (fdr_exact: `bound`), and ~13 ranks
+// of NP 100 / D 10 share a wave; the trip count grows with the rank and wave w of
 // every resident workgroup shares one SIMD, so odd passes run backwards (boustrophedon): each wave pairs a cheap slice of ranks with an expensive one.
 // Items whose scan met a near-tie are appended to the workgroup's list FL (FLN was zeroed before the ranking barrier) and settled after a barrier: up to 64 of them one wave
 // per coordinate (fdr_settle), more than that -- a swarm collapsed onto the rounding floor of its costs -- every lane its own (fdr_settle_own: a second pass of everybody is
@@ -558,13 +572,18 @@ __device__ __forceinline__ void fdr_pass(const RlLds& L, const int* ORDER, const
     const int DW = D / W, NI = NP * DW;
     const FastDiv fw(DW);
     uint32_t mine = 0;                                            // bit p: this thread's item of pass p was flagged
+    const int w0 = __builtin_amdgcn_readfirstlane(tid & ~63);     // the wave's first thread, on the scalar unit
     for (int base = 0, pass = 0; base < NI; base += THREADS, ++pass) {
         const int lim = base + THREADS < NI ? base + THREADS : NI;
         const int ps = (pass & 1) ? lim - 1 - tid : base + tid;
         if (ps >= base && ps < lim) {
             const int rk = fw.div(ps), d0 = W * (ps - rk * DW);
+            // the scan's trip count, one per wave: the highest rank among the wave's items (consecutive in ps; nless(rank) <= rank), scalar arithmetic from the pass
+            // and the wave's place in it (fdr_exact: scanning past a lane's own nless changes nothing)
+            const int top = (pass & 1) ? lim - 1 - w0 : (base + w0 + 63 < lim ? base + w0 + 63 : lim - 1);
+            const int bound = __builtin_amdgcn_readfirstlane(fw.div(top));
             int kb[W];
-            const bool tie = fdr_exact<W, UN, TIE>(L, D, rk, d0, NLESS[ORDER[rk]], kb, range);
+            const bool tie = fdr_exact<W, UN, TIE>(L, D, rk, d0, NLESS[ORDER[rk]], bound, kb, range);
 #pragma unroll
             for (int q = 0; q < W; ++q) L.KB[rk * D + d0 + q] = (uint8_t)kb[q];
 #ifdef MBX_FDR_COUNT
@@ -1216,7 +1235,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         for (int e = tid; e < NP * D; e += THREADS) L.KB[e] = 0;
         __syncthreads();
 #else
-        fdr_pass<2, (DC == 40 ? 2 : MBX_FDR_UNROLL), TIE, THREADS>(L, ORDER, NLESS, NP, D, tid, ub - lb + 1e-5, ar().bp.clk);      // (ends with the barrier that publishes KB)
+        fdr_pass<2, (DC == 40 ? MBX_FDR_UNROLL_D40 : MBX_FDR_UNROLL), TIE, THREADS>(L, ORDER, NLESS, NP, D, tid, ub - lb + 1e-5, ar().bp.clk);      // (ends with the barrier that publishes KB)
 #endif
         // (Measured and dropped, round 3: dealing config 5's half-empty last pass -- 512 items of the highest ranks on 1024 threads -- as single
         // coordinates, one per thread, so that every wave scans: 1.80 -> 1.94 ms per generation; the one-coordinate scan repeats the cost difference
