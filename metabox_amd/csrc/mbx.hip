@@ -79,9 +79,12 @@ struct mbx_suite {
     std::vector<double> optimum;
 };
 
+struct AlgoOps;
+
 struct mbx_batch {
     mbx_suite* suite = nullptr;
     mbx_algo_cfg cfg{};
+    const AlgoOps* ops = nullptr;          // the row of kAlgoOps for cfg.algo
     int B = 0;
     int32_t* d_problem_idx = nullptr;
     std::vector<int32_t> h_problem_idx;    // host copy (mbx_debug_write_state validates an injected block against its problem's box)
@@ -121,114 +124,22 @@ struct mbx_batch {
 // per-algorithm geometry
 struct AlgoGeom { int64_t state_doubles, sc_off, tape_stride, lds_doubles; int state_dim, action_dim; };
 
-static int max_lds_bytes();
+// Everything the host code knows about one algorithm id: the blocks and the table kAlgoOps further down
+struct AlgoOps {
+    int id; const char* name;
+    bool takes_actions;      // mbx_step refuses a null d_actions
+    bool needs_state_out;    // mbx_reset / mbx_step refuse a null d_state_out: the kernels write the features without asking
+    int (*check)(const mbx_algo_cfg&);                  // the algorithm's own limits; null = the common np in [4, kThreads]
+    AlgoGeom (*geom)(const mbx_algo_cfg&);
+    int (*prepare)(mbx_batch*, const AlgoGeom&);        // once per batch, at the end of mbx_batch_create
+    void (*reset)(mbx_batch*, hipStream_t, double* d_state_out);
+    int (*step)(mbx_batch*, hipStream_t, const void* d_actions, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
+    void (*launch_info)(const mbx_batch*, int32_t out[4]);   // where the step kernel's figures differ from the batch's; null = they do not
+};
 
-static AlgoGeom geom_of(const mbx_algo_cfg& c)
-{
-    AlgoGeom g{};
-    if (c.algo == MBX_ALGO_RLEPSO) {
-        g.state_doubles = MBX_RLEPSO_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_RLEPSO_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_RLEPSO_TAPE_STRIDE(c.np, c.dim);
-        // compile-time geometries that read their maps from global memory need no LDS for them (unless the generic kernels are asked for)
-        g.lds_doubles = rl_lds_doubles(c.np, c.dim, (c.flags & MBX_F_GENERIC_GEOMETRY) || c.n_group != 5 || rl_maps_in_lds(c.np, c.dim));
-        g.state_dim = 1; g.action_dim = 7 * c.n_group;
-    } else if (c.algo == MBX_ALGO_LDE) {
-        g.state_doubles = MBX_LDE_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_LDE_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_LDE_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = lde_lds_doubles(c.np, c.dim, lde_maps_in_lds(c.np, c.dim) || (c.flags & MBX_F_GENERIC_GEOMETRY));
-        g.state_dim = c.np + 2 * MBX_LDE_BINS; g.action_dim = 2 * c.np;
-    } else if (c.algo == MBX_ALGO_DEDDQN) {
-        g.state_doubles = MBX_DQ_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_DQ_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_DQ_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = dq_lds_doubles(c.np, c.np, c.dim);          // k_dq_reset; k_dq_step launches with the one-row layout
-        g.state_dim = MBX_DQ_NFEAT; g.action_dim = 1;
-    } else if (c.algo == MBX_ALGO_RANDOM_SEARCH) {
-        g.state_doubles = MBX_RS_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_RS_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_RS_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = rs_lds_doubles(c.np, c.dim);
-        g.state_dim = 1; g.action_dim = 0;
-    } else if (c.algo == MBX_ALGO_RLPSO) {
-        g.state_doubles = MBX_RLPSO_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_RLPSO_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_RLPSO_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = rp_lds_doubles(c.np, c.dim, 0);
-        g.state_dim = 2 * c.dim; g.action_dim = 1;
-    } else if (c.algo == MBX_ALGO_GLEET) {
-        g.state_doubles = MBX_GLEET_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_GLEET_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_GLEET_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = gl_lds_doubles(c.np, c.dim);
-        g.state_dim = 27 * c.np; g.action_dim = c.np;
-    } else if (c.algo == MBX_ALGO_QLPSO) {
-        g.state_doubles = MBX_QLPSO_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_QLPSO_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_QLPSO_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = ql_lds_doubles(c.np, c.np, c.dim);
-        g.state_dim = 1; g.action_dim = 1;
-    } else if (c.algo == MBX_ALGO_DE || c.algo == MBX_ALGO_PSO || c.algo == MBX_ALGO_CMAES) {
-        g.state_doubles = c.algo == MBX_ALGO_DE ? MBX_DE_STATE_DOUBLES(c.np, c.dim, c.n_logpoint)
-                        : c.algo == MBX_ALGO_PSO ? MBX_PSO_STATE_DOUBLES(c.np, c.dim, c.n_logpoint) : MBX_CMA_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = c.algo == MBX_ALGO_DE ? MBX_DE_ST_SCALARS(c.np, c.dim) : c.algo == MBX_ALGO_PSO ? MBX_PSO_ST_SCALARS(c.np, c.dim) : MBX_CMA_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = 0;
-        g.lds_doubles = cl_lds_doubles(c.np, c.np, c.dim, 0, c.algo == MBX_ALGO_CMAES);       // the largest carve-up of the family
-        g.state_dim = 1; g.action_dim = 0;
-    } else if (c.algo == MBX_ALGO_GLPSO) {
-        g.state_doubles = MBX_GLPSO_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_GLPSO_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_GLPSO_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = gp_lds_doubles(c.np, c.dim);
-        g.state_dim = 1; g.action_dim = 0;
-    } else if (c.algo == MBX_ALGO_JDE21) {
-        g.state_doubles = MBX_JDE21_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_JDE21_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_JDE21_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = jd_lds_doubles(c.np, c.dim);
-        g.state_dim = 1; g.action_dim = 0;
-    } else if (c.algo == MBX_ALGO_MADDE) {
-        g.state_doubles = MBX_MADDE_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_MADDE_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_MADDE_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = md_lds_doubles(c.np, c.dim);
-        g.state_dim = 1; g.action_dim = 0;
-    } else if (c.algo == MBX_ALGO_SDMSPSO) {
-        g.state_doubles = MBX_SDMS_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_SDMS_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_SDMS_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = sd_lds_doubles(c.np, c.dim);
-        g.state_dim = 1; g.action_dim = 0;
-    } else if (c.algo == MBX_ALGO_SAHLPSO) {
-        g.state_doubles = MBX_SAHL_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_SAHL_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_SAHL_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = sahlpso_lds_doubles(c.dim);
-        g.state_dim = 1; g.action_dim = 0;
-    } else if (c.algo == MBX_ALGO_LES) {
-        g.state_doubles = MBX_LES_STATE_DOUBLES(c.np, c.dim, MBX_LES_CURVE_CAP(c.max_fes, c.log_interval, c.n_logpoint));
-        g.sc_off = MBX_LES_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_LES_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = les_lds_doubles_of(c.dim);
-        g.state_dim = 1; g.action_dim = 0;
-    } else if (c.algo == MBX_ALGO_DEDQN) {
-        g.state_doubles = MBX_DEDQN_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_DEDQN_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_DEDQN_TAPE_STRIDE(c.np, c.dim);
-        g.lds_doubles = dedqn_lds_doubles(c.np, c.dim);
-        g.state_dim = MBX_DEDQN_NFEAT; g.action_dim = 1;
-    } else if (c.algo == MBX_ALGO_NRLPSO) {
-        g.state_doubles = MBX_NRLPSO_STATE_DOUBLES(c.np, c.dim, c.n_logpoint);
-        g.sc_off = MBX_NRLPSO_ST_SCALARS(c.np, c.dim);
-        g.tape_stride = MBX_NRLPSO_TAPE_STRIDE(c.np, c.dim);
-        // the larger of the reset's carve-up (NP evaluation rows) and the step's (one row, the resident arrays, the distance matrix where it is kept)
-        g.lds_doubles = std::max(nrlpso_lds_doubles(c.np, c.dim, false, false),
-                                 nrlpso_lds_doubles(c.np, c.dim, true, nrlpso_cached(c.np, c.dim, c.flags, (size_t)max_lds_bytes())));
-        g.state_dim = 1; g.action_dim = 1;
-    }
-    return g;
-}
+static const AlgoOps* ops_of(int algo);
+static int max_lds_bytes();
+static AlgoGeom geom_of(const mbx_algo_cfg& c) { return ops_of(c.algo)->geom(c); }      // c has passed check_cfg
 
 extern "C" int mbx_suite_destroy(mbx_suite* s);
 extern "C" int mbx_batch_destroy(mbx_batch* b);
@@ -513,71 +424,25 @@ extern "C" int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, dou
 }
 
 // ------------------------------------------------------------------------------------------------ batch
+static int check_np(const mbx_algo_cfg& c) { return c.np < 4 || c.np > kThreads ? fail(MBX_E_ARG, "np %d outside [4, %d]", c.np, kThreads) : MBX_OK; }
+static int check_dim(const mbx_algo_cfg& c) { return c.dim < 2 || c.dim > 64 ? fail(MBX_E_ARG, "dim %d outside [2, 64]", c.dim) : MBX_OK; }
+
+// unknown id, then the algorithm's own limits, then the common ones: the order decides which message a doubly-wrong cfg gets
 static int check_cfg(const mbx_algo_cfg* c)
 {
     if (!c) return fail(MBX_E_ARG, "null cfg");
-    // the ids this build has kernels for (12, 14 and 17 are not assigned)
-    if (!((c->algo >= MBX_ALGO_RLEPSO && c->algo <= MBX_ALGO_GLPSO) || c->algo == MBX_ALGO_JDE21 || c->algo == MBX_ALGO_MADDE || c->algo == MBX_ALGO_DEDQN ||
-          c->algo == MBX_ALGO_SDMSPSO || c->algo == MBX_ALGO_NRLPSO || c->algo == MBX_ALGO_SAHLPSO || c->algo == MBX_ALGO_LES))
-        return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
-    if (c->algo == MBX_ALGO_JDE21 && c->np != MBX_JDE21_NP) return fail(MBX_E_ARG, "JDE21 runs np = %d (160 + 10 rows), not %d", MBX_JDE21_NP, c->np);
-    if (c->algo == MBX_ALGO_MADDE) {
-        // the one algorithm whose rows are strided over the lanes: np is 2 dim^2, and LDS is sized for at most 3200 rows
-        if (c->dim < 2 || c->dim > MBX_MADDE_DIM_MAX) return fail(MBX_E_ARG, "MadDE runs dim in [2, %d], not %d", MBX_MADDE_DIM_MAX, c->dim);
-        if (c->np != MBX_MADDE_NP(c->dim)) return fail(MBX_E_ARG, "MadDE runs np = 2 dim^2 = %d, not %d", MBX_MADDE_NP(c->dim), c->np);
-    } else if (c->algo == MBX_ALGO_SDMSPSO) {
-        // 33 sub-swarms of 3; the reference's generation 100 would call __quasi_Newton, which fails in the reference itself (sdms_pso.py:198 reads
-        // self.__problem, never assigned) and is not built here; with max_fes <= np the reference returns without its final log entry
-        if (c->np != MBX_SDMS_NP) return fail(MBX_E_ARG, "sDMS_PSO runs np = %d (33 sub-swarms of 3), not %d", MBX_SDMS_NP, c->np);
-        if (c->dim < 2 || c->dim > MBX_SDMS_DIM_MAX) return fail(MBX_E_ARG, "sDMS_PSO runs dim in [2, %d], not %d", MBX_SDMS_DIM_MAX, c->dim);
-        if (c->max_fes <= MBX_SDMS_NP) return fail(MBX_E_ARG, "sDMS_PSO needs max_fes > %d (the initial evaluation), not %d", MBX_SDMS_NP, c->max_fes);
-        if (sd_local_generations(c->max_fes) >= MBX_SDMS_L)
-            return fail(MBX_E_ARG, "sDMS_PSO: with max_fes %d the local phase reaches generation %d, where the reference calls its quasi-Newton refinement "
-                                   "(and fails in it); not built", c->max_fes, MBX_SDMS_L);
-    } else if (c->algo == MBX_ALGO_SAHLPSO) {
-        // 40 particles shrinking to 4 (8 of them exploration particles), one lane per dimension in the move; the 40 initial evaluations are spent by mbx_reset
-        if (c->np != MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO runs np = %d (shrinking to 4), not %d", MBX_SAHL_NP, c->np);
-        if (c->dim < 2 || c->dim > MBX_SAHL_DIM_MAX) return fail(MBX_E_ARG, "SAHLPSO runs dim in [2, %d], not %d", MBX_SAHL_DIM_MAX, c->dim);
-        if (c->max_fes <= MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO needs max_fes > %d (the initial evaluation), not %d", MBX_SAHL_NP, c->max_fes);
-    } else if (c->algo == MBX_ALGO_LES) {
-        // 16 samples per generation, one lane of wave 0 per row and per dimension; the 16 initial evaluations are spent by mbx_reset
-        if (c->np != MBX_LES_NP) return fail(MBX_E_ARG, "LES runs np = %d, not %d", MBX_LES_NP, c->np);
-        if (c->dim < 2 || c->dim > MBX_LES_DIM_MAX) return fail(MBX_E_ARG, "LES runs dim in [2, %d], not %d", MBX_LES_DIM_MAX, c->dim);
-        if (c->max_fes <= MBX_LES_NP) return fail(MBX_E_ARG, "LES needs max_fes > %d (the initial evaluation), not %d", MBX_LES_NP, c->max_fes);
-    } else if (c->algo == MBX_ALGO_DEDQN) {
-        // the landscape analysis deals one row per lane of two waves, and LDS holds the population three times over
-        if (c->np < 4 || c->np > MBX_DEDQN_NP_MAX) return fail(MBX_E_ARG, "DEDQN runs np in [4, %d], not %d", MBX_DEDQN_NP_MAX, c->np);
-        if (c->dim < 2 || c->dim > MBX_DEDQN_DIM_MAX) return fail(MBX_E_ARG, "DEDQN runs dim in [2, %d], not %d", MBX_DEDQN_DIM_MAX, c->dim);
-    } else if (c->algo == MBX_ALGO_NRLPSO) {
-        // one lane per row of the distance matrix (two waves), k = 5 neighbours out of np - 1, and LDS holds population and pbest positions
-        if (c->np < MBX_NRLPSO_NP_MIN || c->np > MBX_NRLPSO_NP_MAX) return fail(MBX_E_ARG, "NRLPSO runs np in [%d, %d], not %d", MBX_NRLPSO_NP_MIN, MBX_NRLPSO_NP_MAX, c->np);
-        if (c->dim < 2 || c->dim > MBX_NRLPSO_DIM_MAX) return fail(MBX_E_ARG, "NRLPSO runs dim in [2, %d], not %d", MBX_NRLPSO_DIM_MAX, c->dim);
-    } else if (c->np < 4 || c->np > kThreads) return fail(MBX_E_ARG, "np %d outside [4, %d]", c->np, kThreads);
-    if (c->dim < 2 || c->dim > 64) return fail(MBX_E_ARG, "dim %d outside [2, 64]", c->dim);
-    if (c->algo == MBX_ALGO_RLEPSO && (c->n_group < 1 || c->n_group > 16 || c->np / c->n_group < 1))
-        return fail(MBX_E_ARG, "bad n_group %d", c->n_group);
+    const AlgoOps* ops = ops_of(c->algo);
+    if (!ops) return fail(MBX_E_UNSUPPORTED, "algo %d is not implemented in this build", c->algo);
+    if (int rc = ops->check ? ops->check(*c) : check_np(*c)) return rc;
+    if (int rc = check_dim(*c)) return rc;
     if (c->max_fes <= 0 || c->log_interval <= 0 || c->n_logpoint <= 0) return fail(MBX_E_ARG, "bad budget/log settings");
     if (c->flags & ~(MBX_F_FDR_FAST | MBX_F_GENERIC_GEOMETRY | MBX_F_ROLLOUT_PER_GENERATION | MBX_F_NRLPSO_RECOMPUTE)) return fail(MBX_E_ARG, "unknown bits in cfg.flags 0x%x", c->flags);
     return MBX_OK;
 }
 
-extern "C" int mbx_state_dim(const mbx_algo_cfg* c)
-{
-    if (int rc = check_cfg(c)) return rc;
-    return geom_of(*c).state_dim;
-}
-
-extern "C" int mbx_action_dim(const mbx_algo_cfg* c)
-{
-    if (int rc = check_cfg(c)) return rc;
-    return geom_of(*c).action_dim;
-}
-
-extern "C" int64_t mbx_tape_stride(const mbx_algo_cfg* c)
-{
-    if (int rc = check_cfg(c)) return rc;
-    return geom_of(*c).tape_stride;
-}
+extern "C" int mbx_state_dim(const mbx_algo_cfg* c) { const int rc = check_cfg(c); return rc ? rc : geom_of(*c).state_dim; }
+extern "C" int mbx_action_dim(const mbx_algo_cfg* c) { const int rc = check_cfg(c); return rc ? rc : geom_of(*c).action_dim; }
+extern "C" int64_t mbx_tape_stride(const mbx_algo_cfg* c) { const int rc = check_cfg(c); return rc ? rc : geom_of(*c).tape_stride; }
 
 // Longest-processing-time-first launch order: workgroups of the expensive objectives are dispatched first so that they do not form the
 // tail of the launch.
@@ -655,41 +520,15 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
     if (cfg->dim != s->dim) return fail(MBX_E_ARG, "cfg.dim %d != suite dim %d", cfg->dim, s->dim);
     for (int i = 0; i < n_instances; ++i)
         if (problem_idx[i] < 0 || problem_idx[i] >= s->n) return fail(MBX_E_ARG, "problem_idx[%d]=%d out of range", i, problem_idx[i]);
-    const AlgoGeom g = geom_of(*cfg);
+    const AlgoOps* ops = ops_of(cfg->algo);
+    const AlgoGeom g = ops->geom(*cfg);
     const size_t lds = (size_t)g.lds_doubles * sizeof(double);
     if (lds > (size_t)max_lds_bytes())
         return fail(MBX_E_UNSUPPORTED, "np=%d dim=%d needs %zu B of LDS per workgroup (> %d)", cfg->np, cfg->dim, lds, max_lds_bytes());
     std::unique_ptr<mbx_batch, int (*)(mbx_batch*)> guard(new mbx_batch(), mbx_batch_destroy);   // freed on every error return
     mbx_batch* b = guard.get();
-    b->suite = s; b->cfg = *cfg; b->B = n_instances; b->lds_bytes = lds;
-    // More than half a CU's LDS per workgroup means one resident workgroup per CU: give it 8 or 16 waves instead of 4 (D >= 16 / 32 keeps the
-    // evaluator's per-wave scratch inside its T region).
-    if (cfg->algo == MBX_ALGO_LDE && (size_t)lde_lds_doubles(cfg->np, cfg->dim, true) * sizeof(double) > 40 * 1024 && cfg->dim >= 16) b->threads = 512;   // objective-bound at D = 30: 8 waves per workgroup, -21 %
-    if (cfg->algo == MBX_ALGO_RLEPSO && (size_t)rl_lds_doubles(cfg->np, cfg->dim, true) * sizeof(double) > 80 * 1024 && cfg->dim >= 16) b->threads = cfg->dim >= 32 ? 1024 : 512;   // per-wave evaluator scratch needs D >= 2 x waves
-    // MBX_F_GENERIC_GEOMETRY keeps the run-time-geometry kernel (the tests compare the two instantiations bit for bit)
-    {
-        const bool generic = (cfg->flags & MBX_F_GENERIC_GEOMETRY) != 0;
-        if (cfg->algo == MBX_ALGO_RLEPSO && cfg->n_group == 5 && !generic) {
-            if (b->threads == kThreads && cfg->np == 100 && cfg->dim == 10) b->fixed_geometry = 1;
-            if (b->threads == 1024 && cfg->np == 128 && cfg->dim == 40) b->fixed_geometry = 2;
-            if (b->threads == 512 && cfg->np == 100 && cfg->dim == 30) b->fixed_geometry = 7;
-            if (b->threads == kThreads && cfg->np == 100 && cfg->dim == 12) b->fixed_geometry = 8;     // protein docking: resident rollout only, the one-generation kernel stays the run-time-geometry one
-            if (b->threads == 1024 && cfg->np == 100 && cfg->dim == 40) b->fixed_geometry = 10;        // the reference's own NP at bbob --dim 40 (config.py:74, rlepso_optimizer.py:11): resident rollout only, likewise
-        }
-        // the fast FDR scan exists for the run-time-geometry kernels and the geometries of BASELINE configs 2 / 5; the other compile-time geometries keep the exact scan on
-        // BOTH routes (so that the two stay bit-identical), and the batch's effective flags say so
-        if (cfg->algo != MBX_ALGO_RLEPSO || b->fixed_geometry == 7 || b->fixed_geometry == 8 || b->fixed_geometry == 10) b->cfg.flags &= ~MBX_F_FDR_FAST;
-        b->fdr_fast = (b->cfg.flags & MBX_F_FDR_FAST) != 0;
-        // config 3 (LDE, NP 50 / D 30, 512 threads) and config 4 (DE-DDQN, NP 100 / D 12)
-        if (cfg->algo == MBX_ALGO_LDE && b->threads == 512 && cfg->np == 50 && cfg->dim == 30 && !generic) b->fixed_geometry = 3;
-        if (cfg->algo == MBX_ALGO_LDE && b->threads == 512 && cfg->np == 100 && cfg->dim == 30 && !generic) b->fixed_geometry = 6;
-        // the reference's own LDE setting (lde_optimizer.py:10 NP = 50, bbob --dim 10): resident rollout only, the one-generation kernel stays the run-time-geometry one
-        if (cfg->algo == MBX_ALGO_LDE && b->threads == kThreads && cfg->np == 50 && cfg->dim == 10 && !generic) b->fixed_geometry = 9;
-        if (cfg->algo == MBX_ALGO_DEDDQN && cfg->np == 100 && cfg->dim == 12 && !generic) b->fixed_geometry = 4;
-        if (cfg->algo == MBX_ALGO_GLEET && cfg->np == 100 && cfg->dim == 10 && !generic) b->fixed_geometry = 5;
-        b->rollout_per_generation = (cfg->flags & MBX_F_ROLLOUT_PER_GENERATION) != 0;
-        b->nrlpso_cached = cfg->algo == MBX_ALGO_NRLPSO && nrlpso_cached(cfg->np, cfg->dim, cfg->flags, (size_t)max_lds_bytes());
-    }
+    b->suite = s; b->cfg = *cfg; b->ops = ops; b->B = n_instances; b->lds_bytes = lds;
+    b->rollout_per_generation = (cfg->flags & MBX_F_ROLLOUT_PER_GENERATION) != 0;
 #ifdef MBX_LDS_PAD_EXPERIMENT
     if (const char* e = getenv("MBX_LDS_PAD")) b->lds_bytes += (size_t)atoi(e);      // occupancy experiments only
 #endif
@@ -706,106 +545,8 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
     hipLaunchKernelGGL(k_init_state, dim3((n_instances + 255) / 256), dim3(256), 0, nullptr, b->d_state, b->state_stride,
                        g.sc_off, n_instances);
     HIP_TRY(hipDeviceSynchronize());
-    if (cfg->algo == MBX_ALGO_RLEPSO) {
-        {   // RLEPSO learning-probability curve (rlepso_optimizer.py:23-24): pci_i = 0.05 + 0.45 exp(10 i/(NP-1)) / (e^10 - 1)
-        std::vector<double> pci(cfg->np);
-        for (int i = 0; i < cfg->np; ++i) pci[i] = 0.05 + 0.45 * std::exp(10. * i / (cfg->np - 1)) / (std::exp(10.) - 1);
-        HIP_TRY(hipMalloc(&b->d_pci, cfg->np * sizeof(double)));
-        HIP_TRY(hipMemcpy(b->d_pci, pci.data(), cfg->np * sizeof(double), hipMemcpyHostToDevice));
-        // mbx_rlepso_rollout never allocates or reads the environment (it may run under stream capture): both happen here
-        HIP_TRY(hipMalloc(&b->d_scratch, (size_t)n_instances * sizeof(double)));
-    }
-#define MBX_RL_LDS(...) HIP_TRY(hipFuncSetAttribute((const void*)(__VA_ARGS__), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-        MBX_RL_LDS(k_rlepso_reset<kThreads>); MBX_RL_LDS(k_rlepso_reset<512>); MBX_RL_LDS(k_rlepso_reset<1024>); MBX_RL_LDS(k_rlepso_reset<512, 100, 30>);
-        // generation kernels: run-time geometry and the geometries of BASELINE configs 2 / 5 in both FDR forms, bbob --dim 30 exact only
-        MBX_RL_LDS(k_rlepso_step<kThreads, 0, 0, 0, true>); MBX_RL_LDS(k_rlepso_step<512, 0, 0, 0, true>); MBX_RL_LDS(k_rlepso_step<1024, 0, 0, 0, true>);
-        MBX_RL_LDS(k_rlepso_step<kThreads, 0, 0, 0, false>); MBX_RL_LDS(k_rlepso_step<512, 0, 0, 0, false>); MBX_RL_LDS(k_rlepso_step<1024, 0, 0, 0, false>);
-        MBX_RL_LDS(k_rlepso_step<kThreads, 100, 10, 5, true>); MBX_RL_LDS(k_rlepso_step<kThreads, 100, 10, 5, false>);
-        MBX_RL_LDS(k_rlepso_step<1024, 128, 40, 5, true>); MBX_RL_LDS(k_rlepso_step<1024, 128, 40, 5, false>);
-        MBX_RL_LDS(k_rlepso_step<512, 100, 30, 5, true>);
-        MBX_RL_LDS(k_rlepso_run<MBX_RUN10_THREADS, 100, 10, 5, true>); MBX_RL_LDS(k_rlepso_run<MBX_RUN10_THREADS, 100, 10, 5, false>);
-        MBX_RL_LDS(k_rlepso_run<1024, 128, 40, 5, true>); MBX_RL_LDS(k_rlepso_run<1024, 128, 40, 5, false>);
-        MBX_RL_LDS(k_rlepso_run<512, 100, 30, 5, true>); MBX_RL_LDS(k_rlepso_run<256, 100, 12, 5, true>); MBX_RL_LDS(k_rlepso_run<1024, 100, 40, 5, true>);
-#undef MBX_RL_LDS
-    } else if (cfg->algo == MBX_ALGO_LDE) {
-        {   // mbx_lde_rollout: per-generation rewards / actions of the host-loop route
-            HIP_TRY(hipMalloc(&b->d_scratch, (size_t)n_instances * (sizeof(double) + (size_t)g.action_dim * sizeof(float))));
-            HIP_TRY(hipMalloc(&b->d_lstm_pack, (size_t)lde_run_pack_floats(g.state_dim, 64, g.action_dim) * sizeof(float)));      // hidden <= 64
-            HIP_TRY(hipFuncSetAttribute((const void*)k_lde_run<100, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lde_run_lds_doubles(100, 30, 50, false) * sizeof(double))));
-            HIP_TRY(hipFuncSetAttribute((const void*)k_lde_run<50, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lde_run_lds_doubles(50, 30, 50, false) * sizeof(double))));
-            HIP_TRY(hipFuncSetAttribute((const void*)k_lde_run<50, 30, 50, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lde_run_lds_doubles(50, 30, 50, true) * sizeof(double))));
-            HIP_TRY(hipFuncSetAttribute((const void*)k_lde_run<50, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lde_run_lds_doubles(50, 10, 50, true) * sizeof(double))));
-        }
-        HIP_TRY(hipFuncSetAttribute((const void*)k_lde_reset<kThreads>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_lde_step<kThreads>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_lde_reset<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_lde_step<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_lde_step<MBX_LDE50_STEP_THREADS, 50, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_lde_step<MBX_LDE100_STEP_THREADS, 100, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_lde_reset<512, 100, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_lde_reset<512, 50, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else if (cfg->algo == MBX_ALGO_DEDDQN) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_dq_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_dq_step<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_dq_step<100, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else if (cfg->algo == MBX_ALGO_DE || cfg->algo == MBX_ALGO_PSO || cfg->algo == MBX_ALGO_CMAES) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_classic_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_de_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_pso_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_cmaes_generation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else if (cfg->algo == MBX_ALGO_GLPSO) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_glpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_glpso_generation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else if (cfg->algo == MBX_ALGO_JDE21) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_jde21_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_jde21_generation<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_jde21_generation<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else if (cfg->algo == MBX_ALGO_MADDE) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_madde_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_madde_generation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else if (cfg->algo == MBX_ALGO_SDMSPSO) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_sdmspso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_sdmspso_update, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else if (cfg->algo == MBX_ALGO_DEDQN) {
-        HIP_TRY(dedqn_prepare(lds));
-        {   // cal_rie's frequencies are n / NP: their logarithms, correctly rounded (extended precision, then one rounding to double), so that the kernel's
-            // entropies do not depend on the device's log (mbx_dedqn.hpp: dd_features); the batch's table pointer `pci` carries them
-            std::vector<double> lt(cfg->np + 1, 0.);
-            for (int n = 1; n < cfg->np; ++n) lt[n] = (double)std::log((long double)((double)n / (double)cfg->np));
-            HIP_TRY(hipMalloc(&b->d_pci, lt.size() * sizeof(double)));
-            HIP_TRY(hipMemcpy(b->d_pci, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-    } else if (cfg->algo == MBX_ALGO_NRLPSO) {
-        HIP_TRY(nrlpso_prepare(lds));
-    } else if (cfg->algo == MBX_ALGO_SAHLPSO) {
-        HIP_TRY(sahlpso_prepare(lds));
-    } else if (cfg->algo == MBX_ALGO_LES) {
-        HIP_TRY(les_prepare(lds));
-        {   // the timestamp embedding (les_optimizer.py:110): tanh(t / timestamp - 1) rounded to float32, as the reference's float64 numpy row is when it
-            // enters the MLP; made in extended precision and rounded once to double, then to float, so that it does not depend on the device's tanh
-            static const int stamps[MBX_LES_NTS] = {1, 3, 10, 30, 50, 100, 250, 500, 750, 1000, 1250, 1500, 2000};
-            b->les_horizon = cfg->max_fes / MBX_LES_NP + MBX_LES_TS_MARGIN;
-            std::vector<float> ts((size_t)(b->les_horizon + 1) * MBX_LES_NTS);
-            for (int t = 0; t <= b->les_horizon; ++t)
-                for (int k = 0; k < MBX_LES_NTS; ++k) ts[(size_t)t * MBX_LES_NTS + k] = (float)(double)std::tanh((long double)((double)t / (double)stamps[k] - 1.));
-            HIP_TRY(hipMalloc(&b->d_les_ts, ts.size() * sizeof(float)));
-            HIP_TRY(hipMemcpy(b->d_les_ts, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-    } else if (cfg->algo == MBX_ALGO_QLPSO) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_qlpso_step<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else if (cfg->algo == MBX_ALGO_GLEET) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_gleet_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_gleet_step<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_gleet_step<100, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else if (cfg->algo == MBX_ALGO_RLPSO) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_rlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_rlpso_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_rlpso_step<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_rs_population, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    if (int rc = ops->prepare(b, g)) return rc;             // workgroup size, compile-time geometry, tables, dynamic-LDS limits
+    if (!b->fdr_fast) b->cfg.flags &= ~MBX_F_FDR_FAST;      // the effective flags: only RLEPSO, and not every geometry of it, has the fast FDR scan
     *out = guard.release();
     return MBX_OK;
 }
@@ -862,6 +603,84 @@ static BatchParams make_params(const mbx_batch* b)
     return p;
 }
 
+// ------------------------------------------------------------------------------------------------ algorithms
+// One block per algorithm id: its limits (check), geometry (geom), per-batch setup (prepare: workgroup size / compile-time geometry, tables, and the
+// kernels' dynamic-LDS limits), the reset launch and the one-step launch; then one row of kAlgoOps at the end of the section.  The entry points
+// above and below look the row up and call through.  Templates are instantiated in the order this file first names them: keep the lists' order.
+template <class... K>
+static int allow_lds(size_t lds, K... kernels)
+{
+    for (const void* k : {(const void*)kernels...}) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return MBX_OK;
+}
+
+static size_t lds_of(const AlgoGeom& g) { return (size_t)g.lds_doubles * sizeof(double); }
+static bool generic_geometry(const mbx_batch* b) { return (b->cfg.flags & MBX_F_GENERIC_GEOMETRY) != 0; }   // keeps the run-time-geometry kernels (the tests compare the two instantiations bit for bit)
+
+#define MBX_GEOM(P, lds, sdim, adim) \
+    AlgoGeom{MBX_##P##_STATE_DOUBLES(c.np, c.dim, c.n_logpoint), MBX_##P##_ST_SCALARS(c.np, c.dim), MBX_##P##_TAPE_STRIDE(c.np, c.dim), (lds), (sdim), (adim)}
+#define MBX_RESET_FN(name) static void name(mbx_batch* b, hipStream_t stream, double* d_state_out)
+#define MBX_STEP_FN(name) static int name(mbx_batch* b, hipStream_t stream, const void* d_actions, double* d_state_out, double* d_reward_out, uint8_t* d_done_out)
+#define MBX_OUT d_state_out, d_reward_out, d_done_out
+// one workgroup per instance; a template-id with commas goes in parentheses
+#define MBX_LAUNCH(kernel, threads, lds, ...) hipLaunchKernelGGL(kernel, dim3(b->B), dim3(threads), (lds), stream, make_params(b), __VA_ARGS__)
+
+// ---- RLEPSO
+static int rlepso_check(const mbx_algo_cfg& c)
+{
+    if (int rc = check_np(c)) return rc;
+    if (int rc = check_dim(c)) return rc;
+    if (c.n_group < 1 || c.n_group > 16 || c.np / c.n_group < 1) return fail(MBX_E_ARG, "bad n_group %d", c.n_group);
+    return MBX_OK;
+}
+
+static AlgoGeom rlepso_geom(const mbx_algo_cfg& c)
+{
+    // compile-time geometries that read their maps from global memory need no LDS for them (unless the generic kernels are asked for)
+    return MBX_GEOM(RLEPSO, rl_lds_doubles(c.np, c.dim, (c.flags & MBX_F_GENERIC_GEOMETRY) || c.n_group != 5 || rl_maps_in_lds(c.np, c.dim)), 1, 7 * c.n_group);
+}
+
+static int rlepso_prepare(mbx_batch* b, const AlgoGeom& g)
+{
+    const mbx_algo_cfg* cfg = &b->cfg;
+    // More than half a CU's LDS per workgroup means one resident workgroup per CU: give it 8 or 16 waves instead of 4 (D >= 16 / 32 keeps the
+    // evaluator's per-wave scratch inside its T region).
+    if ((size_t)rl_lds_doubles(cfg->np, cfg->dim, true) * sizeof(double) > 80 * 1024 && cfg->dim >= 16) b->threads = cfg->dim >= 32 ? 1024 : 512;   // per-wave evaluator scratch needs D >= 2 x waves
+    if (cfg->n_group == 5 && !generic_geometry(b)) {
+        if (b->threads == kThreads && cfg->np == 100 && cfg->dim == 10) b->fixed_geometry = 1;
+        if (b->threads == 1024 && cfg->np == 128 && cfg->dim == 40) b->fixed_geometry = 2;
+        if (b->threads == 512 && cfg->np == 100 && cfg->dim == 30) b->fixed_geometry = 7;
+        if (b->threads == kThreads && cfg->np == 100 && cfg->dim == 12) b->fixed_geometry = 8;     // protein docking: resident rollout only, the one-generation kernel stays the run-time-geometry one
+        if (b->threads == 1024 && cfg->np == 100 && cfg->dim == 40) b->fixed_geometry = 10;        // the reference's own NP at bbob --dim 40 (config.py:74, rlepso_optimizer.py:11): resident rollout only, likewise
+    }
+    // the fast FDR scan exists for the run-time-geometry kernels and the geometries of BASELINE configs 2 / 5; the other compile-time geometries keep the exact scan on
+    // BOTH routes (so that the two stay bit-identical), and the batch's effective flags say so (mbx_batch_create clears the flag where fdr_fast stays false)
+    b->fdr_fast = (cfg->flags & MBX_F_FDR_FAST) != 0 && b->fixed_geometry != 7 && b->fixed_geometry != 8 && b->fixed_geometry != 10;
+    // RLEPSO learning-probability curve (rlepso_optimizer.py:23-24): pci_i = 0.05 + 0.45 exp(10 i/(NP-1)) / (e^10 - 1)
+    std::vector<double> pci(cfg->np);
+    for (int i = 0; i < cfg->np; ++i) pci[i] = 0.05 + 0.45 * std::exp(10. * i / (cfg->np - 1)) / (std::exp(10.) - 1);
+    HIP_TRY(hipMalloc(&b->d_pci, cfg->np * sizeof(double)));
+    HIP_TRY(hipMemcpy(b->d_pci, pci.data(), cfg->np * sizeof(double), hipMemcpyHostToDevice));
+    // mbx_rlepso_rollout never allocates or reads the environment (it may run under stream capture): both happen here
+    HIP_TRY(hipMalloc(&b->d_scratch, (size_t)b->B * sizeof(double)));
+    return allow_lds(lds_of(g), k_rlepso_reset<kThreads>, k_rlepso_reset<512>, k_rlepso_reset<1024>, k_rlepso_reset<512, 100, 30>,
+                     // generation kernels: run-time geometry and the geometries of BASELINE configs 2 / 5 in both FDR forms, bbob --dim 30 exact only
+                     k_rlepso_step<kThreads, 0, 0, 0, true>, k_rlepso_step<512, 0, 0, 0, true>, k_rlepso_step<1024, 0, 0, 0, true>,
+                     k_rlepso_step<kThreads, 0, 0, 0, false>, k_rlepso_step<512, 0, 0, 0, false>, k_rlepso_step<1024, 0, 0, 0, false>,
+                     k_rlepso_step<kThreads, 100, 10, 5, true>, k_rlepso_step<kThreads, 100, 10, 5, false>, k_rlepso_step<1024, 128, 40, 5, true>,
+                     k_rlepso_step<1024, 128, 40, 5, false>, k_rlepso_step<512, 100, 30, 5, true>,
+                     k_rlepso_run<MBX_RUN10_THREADS, 100, 10, 5, true>, k_rlepso_run<MBX_RUN10_THREADS, 100, 10, 5, false>, k_rlepso_run<1024, 128, 40, 5, true>,
+                     k_rlepso_run<1024, 128, 40, 5, false>, k_rlepso_run<512, 100, 30, 5, true>, k_rlepso_run<256, 100, 12, 5, true>, k_rlepso_run<1024, 100, 40, 5, true>);
+}
+
+MBX_RESET_FN(rlepso_reset)
+{
+    if (b->fixed_geometry == 7) MBX_LAUNCH((k_rlepso_reset<512, 100, 30>), 512, b->lds_bytes, d_state_out);
+    else if (b->threads == 1024) MBX_LAUNCH(k_rlepso_reset<1024>, 1024, b->lds_bytes, d_state_out);
+    else if (b->threads == 512) MBX_LAUNCH(k_rlepso_reset<512>, 512, b->lds_bytes, d_state_out);
+    else MBX_LAUNCH(k_rlepso_reset<kThreads>, kThreads, b->lds_bytes, d_state_out);
+}
+
 // one RLEPSO generation: the instantiation of k_rlepso_step that fits the batch (workgroup size by LDS footprint, compile-time
 // geometry for the reference's NP = 100 / D = 10 / 5 groups)
 static void launch_rlepso_step(mbx_batch* b, hipStream_t stream, const float* d_actions, double* d_state_out, double* d_reward_out,
@@ -880,58 +699,315 @@ static void launch_rlepso_step(mbx_batch* b, hipStream_t stream, const float* d_
 #undef MBX_RLEPSO_LAUNCH
 }
 
+MBX_STEP_FN(rlepso_step) { launch_rlepso_step(b, stream, (const float*)d_actions, MBX_OUT, nullptr, 0, nullptr); return MBX_OK; }
+
+// ---- LDE
+static AlgoGeom lde_geom(const mbx_algo_cfg& c)
+{
+    return MBX_GEOM(LDE, lde_lds_doubles(c.np, c.dim, lde_maps_in_lds(c.np, c.dim) || (c.flags & MBX_F_GENERIC_GEOMETRY)), c.np + 2 * MBX_LDE_BINS, 2 * c.np);
+}
+
+static int lde_prepare(mbx_batch* b, const AlgoGeom& g)
+{
+    const mbx_algo_cfg* cfg = &b->cfg;
+    // one resident workgroup per CU, as for RLEPSO; objective-bound at D = 30: 8 waves per workgroup, -21 %
+    if ((size_t)lde_lds_doubles(cfg->np, cfg->dim, true) * sizeof(double) > 40 * 1024 && cfg->dim >= 16) b->threads = 512;
+    if (!generic_geometry(b)) {
+        if (b->threads == 512 && cfg->np == 50 && cfg->dim == 30) b->fixed_geometry = 3;           // config 3 (LDE, NP 50 / D 30, 512 threads)
+        if (b->threads == 512 && cfg->np == 100 && cfg->dim == 30) b->fixed_geometry = 6;
+        // the reference's own LDE setting (lde_optimizer.py:10 NP = 50, bbob --dim 10): resident rollout only, the one-generation kernel stays the run-time-geometry one
+        if (b->threads == kThreads && cfg->np == 50 && cfg->dim == 10) b->fixed_geometry = 9;
+    }
+    // mbx_lde_rollout: per-generation rewards / actions of the host-loop route
+    HIP_TRY(hipMalloc(&b->d_scratch, (size_t)b->B * (sizeof(double) + (size_t)g.action_dim * sizeof(float))));
+    HIP_TRY(hipMalloc(&b->d_lstm_pack, (size_t)lde_run_pack_floats(g.state_dim, 64, g.action_dim) * sizeof(float)));      // hidden <= 64
+    if (int rc = allow_lds(lde_run_lds_doubles(100, 30, 50, false) * sizeof(double), k_lde_run<100, 30>)) return rc;
+    if (int rc = allow_lds(lde_run_lds_doubles(50, 30, 50, false) * sizeof(double), k_lde_run<50, 30>)) return rc;
+    if (int rc = allow_lds(lde_run_lds_doubles(50, 30, 50, true) * sizeof(double), k_lde_run<50, 30, 50, true>)) return rc;
+    if (int rc = allow_lds(lde_run_lds_doubles(50, 10, 50, true) * sizeof(double), k_lde_run<50, 10>)) return rc;
+    return allow_lds(lds_of(g), k_lde_reset<kThreads>, k_lde_step<kThreads>, k_lde_reset<512>, k_lde_step<512>, k_lde_step<MBX_LDE50_STEP_THREADS, 50, 30>,
+                     k_lde_step<MBX_LDE100_STEP_THREADS, 100, 30>, k_lde_reset<512, 100, 30>, k_lde_reset<512, 50, 30>);
+}
+
+MBX_RESET_FN(lde_reset)
+{
+    if (b->fixed_geometry == 6) MBX_LAUNCH((k_lde_reset<512, 100, 30>), 512, b->lds_bytes, d_state_out);
+    else if (b->fixed_geometry == 3) MBX_LAUNCH((k_lde_reset<512, 50, 30>), 512, b->lds_bytes, d_state_out);
+    else if (b->threads == 512) MBX_LAUNCH(k_lde_reset<512>, 512, b->lds_bytes, d_state_out);
+    else MBX_LAUNCH(k_lde_reset<kThreads>, kThreads, b->lds_bytes, d_state_out);
+}
+
+MBX_STEP_FN(lde_step)
+{
+    if (b->fixed_geometry == 3) MBX_LAUNCH((k_lde_step<MBX_LDE50_STEP_THREADS, 50, 30>), MBX_LDE50_STEP_THREADS, b->lds_bytes, (const float*)d_actions, MBX_OUT);
+    else if (b->fixed_geometry == 6) MBX_LAUNCH((k_lde_step<MBX_LDE100_STEP_THREADS, 100, 30>), MBX_LDE100_STEP_THREADS, b->lds_bytes, (const float*)d_actions, MBX_OUT);
+    else if (b->threads == 512) MBX_LAUNCH(k_lde_step<512>, 512, b->lds_bytes, (const float*)d_actions, MBX_OUT);
+    else MBX_LAUNCH(k_lde_step<kThreads>, kThreads, b->lds_bytes, (const float*)d_actions, MBX_OUT);
+    return MBX_OK;
+}
+
+static void lde_launch_info(const mbx_batch* b, int32_t out[4]) { if (b->fixed_geometry == 3) out[0] = MBX_LDE50_STEP_THREADS; }   // k_lde_step's own workgroup size (k_lde_reset keeps b->threads)
+
+// ---- DE-DDQN
+static AlgoGeom deddqn_geom(const mbx_algo_cfg& c) { return MBX_GEOM(DQ, dq_lds_doubles(c.np, c.np, c.dim), MBX_DQ_NFEAT, 1); }   // k_dq_reset's LDS; k_dq_step launches with the one-row layout
+static size_t deddqn_step_lds(const mbx_batch* b) { return (size_t)dq_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double); }
+static int deddqn_prepare(mbx_batch* b, const AlgoGeom& g)
+{
+    if (b->cfg.np == 100 && b->cfg.dim == 12 && !generic_geometry(b)) b->fixed_geometry = 4;      // config 4 (DE-DDQN, NP 100 / D 12)
+    return allow_lds(lds_of(g), k_dq_reset, k_dq_step<>, k_dq_step<100, 12>);
+}
+
+MBX_RESET_FN(deddqn_reset) { MBX_LAUNCH(k_dq_reset, kThreads, b->lds_bytes, d_state_out); }
+MBX_STEP_FN(deddqn_step)
+{
+    if (b->fixed_geometry == 4) MBX_LAUNCH((k_dq_step<100, 12>), kDqStepThreads, deddqn_step_lds(b), (const int32_t*)d_actions, MBX_OUT);
+    else MBX_LAUNCH(k_dq_step<>, kDqStepThreads, deddqn_step_lds(b), (const int32_t*)d_actions, MBX_OUT);
+    return MBX_OK;
+}
+
+static void deddqn_launch_info(const mbx_batch* b, int32_t out[4]) { out[0] = kDqStepThreads; out[1] = (int32_t)deddqn_step_lds(b); }   // the step kernel (small workgroups, one-row evaluator scratch), not k_dq_reset
+
+// ---- DE, PSO, CMA-ES: the classic family shares its reset kernel; every kernel launches with its own carve-up of the LDS, the batch holds the largest
+static size_t classic_lds(const mbx_batch* b, int rows, int de, int cma) { return (size_t)cl_lds_doubles(rows, b->cfg.np, b->cfg.dim, de, cma) * sizeof(double); }
+static AlgoGeom de_geom(const mbx_algo_cfg& c) { return AlgoGeom{MBX_DE_STATE_DOUBLES(c.np, c.dim, c.n_logpoint), MBX_DE_ST_SCALARS(c.np, c.dim), 0, cl_lds_doubles(c.np, c.np, c.dim, 0, 0), 1, 0}; }
+static AlgoGeom pso_geom(const mbx_algo_cfg& c) { return AlgoGeom{MBX_PSO_STATE_DOUBLES(c.np, c.dim, c.n_logpoint), MBX_PSO_ST_SCALARS(c.np, c.dim), 0, cl_lds_doubles(c.np, c.np, c.dim, 0, 0), 1, 0}; }
+static AlgoGeom cmaes_geom(const mbx_algo_cfg& c) { return AlgoGeom{MBX_CMA_STATE_DOUBLES(c.np, c.dim, c.n_logpoint), MBX_CMA_ST_SCALARS(c.np, c.dim), 0, cl_lds_doubles(c.np, c.np, c.dim, 0, 1), 1, 0}; }
+static int classic_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_classic_reset, k_de_sweep, k_pso_sweep, k_cmaes_generation); }
+MBX_RESET_FN(classic_reset) { MBX_LAUNCH(k_classic_reset, kThreads, classic_lds(b, b->cfg.np, 0, 0), (int)b->cfg.algo, d_state_out); }
+MBX_STEP_FN(de_step) { MBX_LAUNCH(k_de_sweep, kThreads, classic_lds(b, 1, 1, 0), MBX_OUT); return MBX_OK; }
+MBX_STEP_FN(pso_step) { MBX_LAUNCH(k_pso_sweep, kThreads, classic_lds(b, 1, 0, 0), MBX_OUT); return MBX_OK; }
+MBX_STEP_FN(cmaes_step) { MBX_LAUNCH(k_cmaes_generation, kThreads, classic_lds(b, b->cfg.np, 0, 1), MBX_OUT); return MBX_OK; }
+
+// ---- GL-PSO
+static AlgoGeom glpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(GLPSO, gp_lds_doubles(c.np, c.dim), 1, 0); }
+static int glpso_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_glpso_reset, k_glpso_generation); }
+MBX_RESET_FN(glpso_reset) { MBX_LAUNCH(k_glpso_reset, kThreads, b->lds_bytes, d_state_out); }
+MBX_STEP_FN(glpso_step) { MBX_LAUNCH(k_glpso_generation, kThreads, b->lds_bytes, MBX_OUT); return MBX_OK; }
+
+// ---- JDE21
+static int jde21_check(const mbx_algo_cfg& c) { return c.np != MBX_JDE21_NP ? fail(MBX_E_ARG, "JDE21 runs np = %d (160 + 10 rows), not %d", MBX_JDE21_NP, c.np) : MBX_OK; }
+static AlgoGeom jde21_geom(const mbx_algo_cfg& c) { return MBX_GEOM(JDE21, jd_lds_doubles(c.np, c.dim), 1, 0); }
+static int jde21_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_jde21_reset, k_jde21_generation<2>, k_jde21_generation<3>); }
+MBX_RESET_FN(jde21_reset) { MBX_LAUNCH(k_jde21_reset, kThreads, b->lds_bytes, d_state_out); }
+MBX_STEP_FN(jde21_step)
+{
+    if (jd_waves((int64_t)b->lds_bytes) == 3) MBX_LAUNCH(k_jde21_generation<3>, kThreads, b->lds_bytes, MBX_OUT);
+    else MBX_LAUNCH(k_jde21_generation<2>, kThreads, b->lds_bytes, MBX_OUT);
+    return MBX_OK;
+}
+
+// ---- MadDE
+static int madde_check(const mbx_algo_cfg& c)
+{
+    // the one algorithm whose rows are strided over the lanes: np is 2 dim^2, and LDS is sized for at most 3200 rows
+    if (c.dim < 2 || c.dim > MBX_MADDE_DIM_MAX) return fail(MBX_E_ARG, "MadDE runs dim in [2, %d], not %d", MBX_MADDE_DIM_MAX, c.dim);
+    if (c.np != MBX_MADDE_NP(c.dim)) return fail(MBX_E_ARG, "MadDE runs np = 2 dim^2 = %d, not %d", MBX_MADDE_NP(c.dim), c.np);
+    return MBX_OK;
+}
+
+static AlgoGeom madde_geom(const mbx_algo_cfg& c) { return MBX_GEOM(MADDE, md_lds_doubles(c.np, c.dim), 1, 0); }
+static int madde_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_madde_reset, k_madde_generation); }
+MBX_RESET_FN(madde_reset) { MBX_LAUNCH(k_madde_reset, kThreads, b->lds_bytes, d_state_out); }
+MBX_STEP_FN(madde_step) { MBX_LAUNCH(k_madde_generation, kThreads, b->lds_bytes, MBX_OUT); return MBX_OK; }
+
+// ---- sDMS_PSO
+static int sdmspso_check(const mbx_algo_cfg& c)
+{
+    // 33 sub-swarms of 3; the reference's generation 100 would call __quasi_Newton, which fails in the reference itself (sdms_pso.py:198 reads
+    // self.__problem, never assigned) and is not built here; with max_fes <= np the reference returns without its final log entry
+    if (c.np != MBX_SDMS_NP) return fail(MBX_E_ARG, "sDMS_PSO runs np = %d (33 sub-swarms of 3), not %d", MBX_SDMS_NP, c.np);
+    if (c.dim < 2 || c.dim > MBX_SDMS_DIM_MAX) return fail(MBX_E_ARG, "sDMS_PSO runs dim in [2, %d], not %d", MBX_SDMS_DIM_MAX, c.dim);
+    if (c.max_fes <= MBX_SDMS_NP) return fail(MBX_E_ARG, "sDMS_PSO needs max_fes > %d (the initial evaluation), not %d", MBX_SDMS_NP, c.max_fes);
+    if (sd_local_generations(c.max_fes) >= MBX_SDMS_L)
+        return fail(MBX_E_ARG, "sDMS_PSO: with max_fes %d the local phase reaches generation %d, where the reference calls its quasi-Newton refinement "
+                               "(and fails in it); not built", c.max_fes, MBX_SDMS_L);
+    return MBX_OK;
+}
+
+static AlgoGeom sdmspso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(SDMS, sd_lds_doubles(c.np, c.dim), 1, 0); }
+static int sdmspso_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_sdmspso_reset, k_sdmspso_update); }
+MBX_RESET_FN(sdmspso_reset) { MBX_LAUNCH(k_sdmspso_reset, kThreads, b->lds_bytes, d_state_out); }
+MBX_STEP_FN(sdmspso_step) { MBX_LAUNCH(k_sdmspso_update, kThreads, b->lds_bytes, MBX_OUT); return MBX_OK; }
+
+// ---- DEDQN: kernels and launch code in mbx_run_dedqn.hip
+static int dedqn_check(const mbx_algo_cfg& c)
+{
+    // the landscape analysis deals one row per lane of two waves, and LDS holds the population three times over
+    if (c.np < 4 || c.np > MBX_DEDQN_NP_MAX) return fail(MBX_E_ARG, "DEDQN runs np in [4, %d], not %d", MBX_DEDQN_NP_MAX, c.np);
+    if (c.dim < 2 || c.dim > MBX_DEDQN_DIM_MAX) return fail(MBX_E_ARG, "DEDQN runs dim in [2, %d], not %d", MBX_DEDQN_DIM_MAX, c.dim);
+    return MBX_OK;
+}
+
+static AlgoGeom dedqn_geom(const mbx_algo_cfg& c) { return MBX_GEOM(DEDQN, dedqn_lds_doubles(c.np, c.dim), MBX_DEDQN_NFEAT, 1); }
+static int dedqn_prepare_batch(mbx_batch* b, const AlgoGeom& g)
+{
+    HIP_TRY(dedqn_prepare(lds_of(g)));
+    // cal_rie's frequencies are n / NP: their logarithms, correctly rounded (extended precision, then one rounding to double), so that the kernel's
+    // entropies do not depend on the device's log (mbx_dedqn.hpp: dd_features); the batch's table pointer `pci` carries them
+    std::vector<double> lt(b->cfg.np + 1, 0.);
+    for (int n = 1; n < b->cfg.np; ++n) lt[n] = (double)std::log((long double)((double)n / (double)b->cfg.np));
+    HIP_TRY(hipMalloc(&b->d_pci, lt.size() * sizeof(double)));
+    HIP_TRY(hipMemcpy(b->d_pci, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
+    return MBX_OK;
+}
+
+MBX_RESET_FN(dedqn_reset) { dedqn_launch_reset(make_params(b), b->lds_bytes, stream, d_state_out); }
+MBX_STEP_FN(dedqn_step) { dedqn_launch_step(make_params(b), b->lds_bytes, stream, (const int32_t*)d_actions, MBX_OUT); return MBX_OK; }
+
+// ---- NRLPSO: mbx_run_nrlpso.hip
+static int nrlpso_check(const mbx_algo_cfg& c)
+{
+    // one lane per row of the distance matrix (two waves), k = 5 neighbours out of np - 1, and LDS holds population and pbest positions
+    if (c.np < MBX_NRLPSO_NP_MIN || c.np > MBX_NRLPSO_NP_MAX) return fail(MBX_E_ARG, "NRLPSO runs np in [%d, %d], not %d", MBX_NRLPSO_NP_MIN, MBX_NRLPSO_NP_MAX, c.np);
+    if (c.dim < 2 || c.dim > MBX_NRLPSO_DIM_MAX) return fail(MBX_E_ARG, "NRLPSO runs dim in [2, %d], not %d", MBX_NRLPSO_DIM_MAX, c.dim);
+    return MBX_OK;
+}
+
+static AlgoGeom nrlpso_geom(const mbx_algo_cfg& c)
+{
+    // the larger of the reset's carve-up (NP evaluation rows) and the step's (one row, the resident arrays, the distance matrix where it is kept)
+    return MBX_GEOM(NRLPSO, std::max(nrlpso_lds_doubles(c.np, c.dim, false, false),
+                                     nrlpso_lds_doubles(c.np, c.dim, true, nrlpso_cached(c.np, c.dim, c.flags, (size_t)max_lds_bytes()))), 1, 1);
+}
+
+static int nrlpso_prepare_batch(mbx_batch* b, const AlgoGeom& g)
+{
+    b->nrlpso_cached = nrlpso_cached(b->cfg.np, b->cfg.dim, b->cfg.flags, (size_t)max_lds_bytes());
+    HIP_TRY(nrlpso_prepare(lds_of(g)));
+    return MBX_OK;
+}
+
+MBX_RESET_FN(nrlpso_reset) { nrlpso_launch_reset(make_params(b), stream, d_state_out); }
+MBX_STEP_FN(nrlpso_step) { nrlpso_launch_steps(make_params(b), b->nrlpso_cached, stream, (const int32_t*)d_actions, nullptr, 1, nullptr, nullptr, nullptr, nullptr, MBX_OUT); return MBX_OK; }
+
+// the step kernels' LDS (the reset's carve-up is smaller at np = 100)
+static void nrlpso_launch_info(const mbx_batch* b, int32_t out[4]) { out[1] = (int32_t)(nrlpso_lds_doubles(b->cfg.np, b->cfg.dim, true, b->nrlpso_cached) * sizeof(double)); }
+
+// ---- SAHLPSO: mbx_run_sahlpso.hip
+static int sahlpso_check(const mbx_algo_cfg& c)
+{
+    // 40 particles shrinking to 4 (8 of them exploration particles), one lane per dimension in the move; the 40 initial evaluations are spent by mbx_reset
+    if (c.np != MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO runs np = %d (shrinking to 4), not %d", MBX_SAHL_NP, c.np);
+    if (c.dim < 2 || c.dim > MBX_SAHL_DIM_MAX) return fail(MBX_E_ARG, "SAHLPSO runs dim in [2, %d], not %d", MBX_SAHL_DIM_MAX, c.dim);
+    if (c.max_fes <= MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO needs max_fes > %d (the initial evaluation), not %d", MBX_SAHL_NP, c.max_fes);
+    return MBX_OK;
+}
+
+static AlgoGeom sahlpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(SAHL, sahlpso_lds_doubles(c.dim), 1, 0); }
+static int sahlpso_prepare_batch(mbx_batch*, const AlgoGeom& g) { HIP_TRY(sahlpso_prepare(lds_of(g))); return MBX_OK; }
+MBX_RESET_FN(sahlpso_reset) { sahlpso_launch_reset(make_params(b), stream, d_state_out); }
+MBX_STEP_FN(sahlpso_step) { sahlpso_launch_generation(make_params(b), stream, MBX_OUT); return MBX_OK; }
+
+// ---- LES: mbx_run_les.hip
+static int les_check(const mbx_algo_cfg& c)
+{
+    // 16 samples per generation, one lane of wave 0 per row and per dimension; the 16 initial evaluations are spent by mbx_reset
+    if (c.np != MBX_LES_NP) return fail(MBX_E_ARG, "LES runs np = %d, not %d", MBX_LES_NP, c.np);
+    if (c.dim < 2 || c.dim > MBX_LES_DIM_MAX) return fail(MBX_E_ARG, "LES runs dim in [2, %d], not %d", MBX_LES_DIM_MAX, c.dim);
+    if (c.max_fes <= MBX_LES_NP) return fail(MBX_E_ARG, "LES needs max_fes > %d (the initial evaluation), not %d", MBX_LES_NP, c.max_fes);
+    return MBX_OK;
+}
+
+static AlgoGeom les_geom(const mbx_algo_cfg& c)
+{
+    return AlgoGeom{MBX_LES_STATE_DOUBLES(c.np, c.dim, MBX_LES_CURVE_CAP(c.max_fes, c.log_interval, c.n_logpoint)), MBX_LES_ST_SCALARS(c.np, c.dim),
+                    MBX_LES_TAPE_STRIDE(c.np, c.dim), les_lds_doubles_of(c.dim), 1, 0};
+}
+
+static int les_prepare_batch(mbx_batch* b, const AlgoGeom& g)
+{
+    HIP_TRY(les_prepare(lds_of(g)));
+    // the timestamp embedding (les_optimizer.py:110): tanh(t / timestamp - 1) rounded to float32, as the reference's float64 numpy row is when it
+    // enters the MLP; made in extended precision and rounded once to double, then to float, so that it does not depend on the device's tanh
+    static const int stamps[MBX_LES_NTS] = {1, 3, 10, 30, 50, 100, 250, 500, 750, 1000, 1250, 1500, 2000};
+    b->les_horizon = b->cfg.max_fes / MBX_LES_NP + MBX_LES_TS_MARGIN;
+    std::vector<float> ts((size_t)(b->les_horizon + 1) * MBX_LES_NTS);
+    for (int t = 0; t <= b->les_horizon; ++t)
+        for (int k = 0; k < MBX_LES_NTS; ++k) ts[(size_t)t * MBX_LES_NTS + k] = (float)(double)std::tanh((long double)((double)t / (double)stamps[k] - 1.));
+    HIP_TRY(hipMalloc(&b->d_les_ts, ts.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(b->d_les_ts, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice));
+    return MBX_OK;
+}
+
+MBX_RESET_FN(les_reset) { les_launch_reset(make_params(b), stream, d_state_out); }
+MBX_STEP_FN(les_step) { (void)d_actions; return mbx_les_rollout(b, 1, 0, MBX_OUT, stream); }   // one generation of the budget route
+
+// ---- QLPSO
+static AlgoGeom qlpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(QLPSO, ql_lds_doubles(c.np, c.np, c.dim), 1, 1); }
+static int qlpso_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_qlpso_reset, k_qlpso_step<false>, k_qlpso_step<true>); }
+MBX_RESET_FN(qlpso_reset) { MBX_LAUNCH(k_qlpso_reset, kThreads, b->lds_bytes, d_state_out); }
+static size_t qlpso_step_lds(const mbx_batch* b) { return (size_t)ql_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double); }      // one evaluation row
+MBX_STEP_FN(qlpso_step) { MBX_LAUNCH(k_qlpso_step<false>, kThreads, qlpso_step_lds(b), (const int32_t*)d_actions, (const double*)nullptr, 1, MBX_OUT, (int32_t*)nullptr); return MBX_OK; }
+
+// ---- GLEET
+static AlgoGeom gleet_geom(const mbx_algo_cfg& c) { return MBX_GEOM(GLEET, gl_lds_doubles(c.np, c.dim), 27 * c.np, c.np); }
+static int gleet_prepare(mbx_batch* b, const AlgoGeom& g)
+{
+    if (b->cfg.np == 100 && b->cfg.dim == 10 && !generic_geometry(b)) b->fixed_geometry = 5;
+    return allow_lds(lds_of(g), k_gleet_reset, k_gleet_step<>, k_gleet_step<100, 10>);
+}
+
+MBX_RESET_FN(gleet_reset) { MBX_LAUNCH(k_gleet_reset, kThreads, b->lds_bytes, d_state_out); }
+MBX_STEP_FN(gleet_step)
+{
+    if (b->fixed_geometry == 5) MBX_LAUNCH((k_gleet_step<100, 10>), kThreads, b->lds_bytes, (const float*)d_actions, MBX_OUT);
+    else MBX_LAUNCH(k_gleet_step<>, kThreads, b->lds_bytes, (const float*)d_actions, MBX_OUT);
+    return MBX_OK;
+}
+
+// ---- RL-PSO
+static AlgoGeom rlpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(RLPSO, rp_lds_doubles(c.np, c.dim, 0), 2 * c.dim, 1); }
+static int rlpso_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_rlpso_reset, k_rlpso_step<false>, k_rlpso_step<true>); }
+MBX_RESET_FN(rlpso_reset) { MBX_LAUNCH(k_rlpso_reset, kThreads, b->lds_bytes, d_state_out); }
+static size_t rlpso_step_lds(const mbx_batch* b) { return (size_t)rp_lds_doubles(1, b->cfg.dim, 0) * sizeof(double); }      // one evaluation row, no actor
+MBX_STEP_FN(rlpso_step) { MBX_LAUNCH(k_rlpso_step<false>, kThreads, rlpso_step_lds(b), (const float*)d_actions, GaussMlp{}, 1, MBX_OUT, (float*)nullptr); return MBX_OK; }
+
+// ---- Random_search: one kernel, the population of the reset (first = 1) and of every step
+static AlgoGeom rs_geom(const mbx_algo_cfg& c) { return MBX_GEOM(RS, rs_lds_doubles(c.np, c.dim), 1, 0); }
+static int rs_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_rs_population); }
+MBX_RESET_FN(rs_reset) { MBX_LAUNCH(k_rs_population, kThreads, b->lds_bytes, 1, d_state_out, (double*)nullptr, (uint8_t*)nullptr); }
+MBX_STEP_FN(rs_step) { MBX_LAUNCH(k_rs_population, kThreads, b->lds_bytes, 0, MBX_OUT); return MBX_OK; }
+
+#undef MBX_GEOM
+#undef MBX_RESET_FN
+#undef MBX_STEP_FN
+#undef MBX_OUT
+#undef MBX_LAUNCH
+
+// id, name, takes_actions, needs_state_out, check, geom, prepare, reset, step, launch_info.  A new algorithm: its block above, its row here.
+static const AlgoOps kAlgoOps[] = {
+    {MBX_ALGO_RLEPSO, "RLEPSO", true, false, rlepso_check, rlepso_geom, rlepso_prepare, rlepso_reset, rlepso_step, nullptr},
+    {MBX_ALGO_LDE, "LDE", true, true, nullptr, lde_geom, lde_prepare, lde_reset, lde_step, lde_launch_info},
+    {MBX_ALGO_DEDDQN, "DE-DDQN", true, true, nullptr, deddqn_geom, deddqn_prepare, deddqn_reset, deddqn_step, deddqn_launch_info},
+    {MBX_ALGO_RANDOM_SEARCH, "Random_search", false, false, nullptr, rs_geom, rs_prepare, rs_reset, rs_step, nullptr},
+    {MBX_ALGO_RLPSO, "RL-PSO", true, false, nullptr, rlpso_geom, rlpso_prepare, rlpso_reset, rlpso_step, nullptr},
+    {MBX_ALGO_GLEET, "GLEET", true, false, nullptr, gleet_geom, gleet_prepare, gleet_reset, gleet_step, nullptr},
+    {MBX_ALGO_QLPSO, "QLPSO", true, false, nullptr, qlpso_geom, qlpso_prepare, qlpso_reset, qlpso_step, nullptr},
+    {MBX_ALGO_DE, "DE", false, false, nullptr, de_geom, classic_prepare, classic_reset, de_step, nullptr},
+    {MBX_ALGO_PSO, "PSO", false, false, nullptr, pso_geom, classic_prepare, classic_reset, pso_step, nullptr},
+    {MBX_ALGO_CMAES, "CMA-ES", false, false, nullptr, cmaes_geom, classic_prepare, classic_reset, cmaes_step, nullptr},
+    {MBX_ALGO_GLPSO, "GL-PSO", false, false, nullptr, glpso_geom, glpso_prepare, glpso_reset, glpso_step, nullptr},
+    {MBX_ALGO_JDE21, "JDE21", false, false, jde21_check, jde21_geom, jde21_prepare, jde21_reset, jde21_step, nullptr},
+    {MBX_ALGO_MADDE, "MadDE", false, false, madde_check, madde_geom, madde_prepare, madde_reset, madde_step, nullptr},
+    {MBX_ALGO_DEDQN, "DEDQN", true, false, dedqn_check, dedqn_geom, dedqn_prepare_batch, dedqn_reset, dedqn_step, nullptr},
+    {MBX_ALGO_SDMSPSO, "sDMS_PSO", false, false, sdmspso_check, sdmspso_geom, sdmspso_prepare, sdmspso_reset, sdmspso_step, nullptr},
+    {MBX_ALGO_NRLPSO, "NRLPSO", true, false, nrlpso_check, nrlpso_geom, nrlpso_prepare_batch, nrlpso_reset, nrlpso_step, nrlpso_launch_info},
+    {MBX_ALGO_SAHLPSO, "SAHLPSO", false, false, sahlpso_check, sahlpso_geom, sahlpso_prepare_batch, sahlpso_reset, sahlpso_step, nullptr},
+    {MBX_ALGO_LES, "LES", false, false, les_check, les_geom, les_prepare_batch, les_reset, les_step, nullptr},
+};
+
+static const AlgoOps* ops_of(int algo)      // null for the ids that are not assigned (0, 12, 14, 17) and anything out of range
+{
+    for (const AlgoOps& o : kAlgoOps)
+        if (o.id == algo) return &o;
+    return nullptr;
+}
+
 extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
 {
     if (!b) return fail(MBX_E_ARG, "null batch");
-    if (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH)
-        hipLaunchKernelGGL(k_rs_population, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), 1, d_state_out,
-                           (double*)nullptr, (uint8_t*)nullptr);
-    else if (b->cfg.algo == MBX_ALGO_RLEPSO && b->fixed_geometry == 7)
-        hipLaunchKernelGGL((k_rlepso_reset<512, 100, 30>), dim3(b->B), dim3(512), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_RLEPSO && b->threads == 1024)
-        hipLaunchKernelGGL(k_rlepso_reset<1024>, dim3(b->B), dim3(1024), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_RLEPSO && b->threads == 512)
-        hipLaunchKernelGGL(k_rlepso_reset<512>, dim3(b->B), dim3(512), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_RLEPSO)
-        hipLaunchKernelGGL(k_rlepso_reset<kThreads>, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_RLPSO)
-        hipLaunchKernelGGL(k_rlpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_DE || b->cfg.algo == MBX_ALGO_PSO || b->cfg.algo == MBX_ALGO_CMAES)
-        hipLaunchKernelGGL(k_classic_reset, dim3(b->B), dim3(kThreads), (size_t)cl_lds_doubles(b->cfg.np, b->cfg.np, b->cfg.dim, 0, 0) * sizeof(double),
-                           (hipStream_t)stream, make_params(b), (int)b->cfg.algo, d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_GLPSO)
-        hipLaunchKernelGGL(k_glpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_JDE21)
-        hipLaunchKernelGGL(k_jde21_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_MADDE)
-        hipLaunchKernelGGL(k_madde_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_SDMSPSO)
-        hipLaunchKernelGGL(k_sdmspso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_DEDQN)
-        dedqn_launch_reset(make_params(b), b->lds_bytes, (hipStream_t)stream, d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_NRLPSO)
-        nrlpso_launch_reset(make_params(b), (hipStream_t)stream, d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_SAHLPSO)
-        sahlpso_launch_reset(make_params(b), (hipStream_t)stream, d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_LES)
-        les_launch_reset(make_params(b), (hipStream_t)stream, d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_QLPSO)
-        hipLaunchKernelGGL(k_qlpso_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else if (b->cfg.algo == MBX_ALGO_GLEET)
-        hipLaunchKernelGGL(k_gleet_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    else {
-        if (!d_state_out) return fail(MBX_E_ARG, "mbx_reset: this algorithm needs d_state_out");
-        if (b->cfg.algo == MBX_ALGO_LDE && b->fixed_geometry == 6)
-            hipLaunchKernelGGL((k_lde_reset<512, 100, 30>), dim3(b->B), dim3(512), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-        else if (b->cfg.algo == MBX_ALGO_LDE && b->fixed_geometry == 3)
-            hipLaunchKernelGGL((k_lde_reset<512, 50, 30>), dim3(b->B), dim3(512), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-        else if (b->cfg.algo == MBX_ALGO_LDE && b->threads == 512)
-            hipLaunchKernelGGL(k_lde_reset<512>, dim3(b->B), dim3(512), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-        else if (b->cfg.algo == MBX_ALGO_LDE)
-            hipLaunchKernelGGL(k_lde_reset<kThreads>, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-        else
-            hipLaunchKernelGGL(k_dq_reset, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out);
-    }
+    if (b->ops->needs_state_out && !d_state_out) return fail(MBX_E_ARG, "mbx_reset: this algorithm needs d_state_out");
+    b->ops->reset(b, (hipStream_t)stream, d_state_out);
     HIP_TRY(hipGetLastError());
     return MBX_OK;
 }
@@ -939,83 +1015,9 @@ extern "C" int mbx_reset(mbx_batch* b, double* d_state_out, void* stream)
 extern "C" int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out, double* d_reward_out, uint8_t* d_done_out,
                         void* stream)
 {
-    const bool no_agent = b && (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH || b->cfg.algo == MBX_ALGO_DE || b->cfg.algo == MBX_ALGO_PSO ||
-                                b->cfg.algo == MBX_ALGO_CMAES || b->cfg.algo == MBX_ALGO_GLPSO || b->cfg.algo == MBX_ALGO_JDE21 ||
-                                b->cfg.algo == MBX_ALGO_MADDE || b->cfg.algo == MBX_ALGO_SDMSPSO || b->cfg.algo == MBX_ALGO_SAHLPSO ||
-                                b->cfg.algo == MBX_ALGO_LES);
-    if (!b || (!d_actions && !no_agent)) return fail(MBX_E_ARG, "mbx_step: bad arguments");
-    if (b->cfg.algo == MBX_ALGO_LES) return mbx_les_rollout(b, 1, 0, d_state_out, d_reward_out, d_done_out, stream);   // one generation of the budget route
-    if (b->cfg.algo == MBX_ALGO_RANDOM_SEARCH)
-        hipLaunchKernelGGL(k_rs_population, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), 0, d_state_out,
-                           d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_RLEPSO)
-        launch_rlepso_step(b, (hipStream_t)stream, (const float*)d_actions, d_state_out, d_reward_out, d_done_out, nullptr, 0, nullptr);
-    else if (b->cfg.algo == MBX_ALGO_DE)
-        hipLaunchKernelGGL(k_de_sweep, dim3(b->B), dim3(kThreads), (size_t)cl_lds_doubles(1, b->cfg.np, b->cfg.dim, 1, 0) * sizeof(double),
-                           (hipStream_t)stream, make_params(b), d_state_out, d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_PSO)
-        hipLaunchKernelGGL(k_pso_sweep, dim3(b->B), dim3(kThreads), (size_t)cl_lds_doubles(1, b->cfg.np, b->cfg.dim, 0, 0) * sizeof(double),
-                           (hipStream_t)stream, make_params(b), d_state_out, d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_CMAES)
-        hipLaunchKernelGGL(k_cmaes_generation, dim3(b->B), dim3(kThreads), (size_t)cl_lds_doubles(b->cfg.np, b->cfg.np, b->cfg.dim, 0, 1) * sizeof(double),
-                           (hipStream_t)stream, make_params(b), d_state_out, d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_GLPSO)
-        hipLaunchKernelGGL(k_glpso_generation, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
-                           d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_JDE21 && jd_waves((int64_t)b->lds_bytes) == 3)
-        hipLaunchKernelGGL(k_jde21_generation<3>, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
-                           d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_JDE21)
-        hipLaunchKernelGGL(k_jde21_generation<2>, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
-                           d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_MADDE)
-        hipLaunchKernelGGL(k_madde_generation, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
-                           d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_SDMSPSO)
-        hipLaunchKernelGGL(k_sdmspso_update, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b), d_state_out,
-                           d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_SAHLPSO)
-        sahlpso_launch_generation(make_params(b), (hipStream_t)stream, d_state_out, d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_DEDQN)
-        dedqn_launch_step(make_params(b), b->lds_bytes, (hipStream_t)stream, (const int32_t*)d_actions, d_state_out, d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_NRLPSO)
-        nrlpso_launch_steps(make_params(b), b->nrlpso_cached, (hipStream_t)stream, (const int32_t*)d_actions, nullptr, 1, nullptr, nullptr, nullptr, nullptr,
-                            d_state_out, d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_QLPSO)
-        hipLaunchKernelGGL(k_qlpso_step<false>, dim3(b->B), dim3(kThreads), (size_t)ql_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double),
-                           (hipStream_t)stream, make_params(b), (const int32_t*)d_actions, (const double*)nullptr, 1, d_state_out,
-                           d_reward_out, d_done_out, (int32_t*)nullptr);
-    else if (b->cfg.algo == MBX_ALGO_GLEET && b->fixed_geometry == 5)
-        hipLaunchKernelGGL((k_gleet_step<100, 10>), dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b),
-                           (const float*)d_actions, d_state_out, d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_GLEET)
-        hipLaunchKernelGGL(k_gleet_step<>, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b),
-                           (const float*)d_actions, d_state_out, d_reward_out, d_done_out);
-    else if (b->cfg.algo == MBX_ALGO_RLPSO)
-        hipLaunchKernelGGL(k_rlpso_step<false>, dim3(b->B), dim3(kThreads), (size_t)rp_lds_doubles(1, b->cfg.dim, 0) * sizeof(double),
-                           (hipStream_t)stream, make_params(b), (const float*)d_actions, GaussMlp{}, 1, d_state_out, d_reward_out,
-                           d_done_out, (float*)nullptr);
-    else {
-        if (!d_state_out) return fail(MBX_E_ARG, "mbx_step: this algorithm needs d_state_out");
-        if (b->cfg.algo == MBX_ALGO_LDE && b->fixed_geometry == 3)
-            hipLaunchKernelGGL((k_lde_step<MBX_LDE50_STEP_THREADS, 50, 30>), dim3(b->B), dim3(MBX_LDE50_STEP_THREADS), b->lds_bytes, (hipStream_t)stream, make_params(b),
-                               (const float*)d_actions, d_state_out, d_reward_out, d_done_out);
-        else if (b->cfg.algo == MBX_ALGO_LDE && b->fixed_geometry == 6)
-            hipLaunchKernelGGL((k_lde_step<MBX_LDE100_STEP_THREADS, 100, 30>), dim3(b->B), dim3(MBX_LDE100_STEP_THREADS), b->lds_bytes, (hipStream_t)stream, make_params(b),
-                               (const float*)d_actions, d_state_out, d_reward_out, d_done_out);
-        else if (b->cfg.algo == MBX_ALGO_LDE && b->threads == 512)
-            hipLaunchKernelGGL(k_lde_step<512>, dim3(b->B), dim3(512), b->lds_bytes, (hipStream_t)stream, make_params(b),
-                               (const float*)d_actions, d_state_out, d_reward_out, d_done_out);
-        else if (b->cfg.algo == MBX_ALGO_LDE)
-            hipLaunchKernelGGL(k_lde_step<kThreads>, dim3(b->B), dim3(kThreads), b->lds_bytes, (hipStream_t)stream, make_params(b),
-                               (const float*)d_actions, d_state_out, d_reward_out, d_done_out);
-        else if (b->fixed_geometry == 4)
-            hipLaunchKernelGGL((k_dq_step<100, 12>), dim3(b->B), dim3(kDqStepThreads), (size_t)dq_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double), (hipStream_t)stream, make_params(b),
-                               (const int32_t*)d_actions, d_state_out, d_reward_out, d_done_out);
-        else
-            hipLaunchKernelGGL(k_dq_step<>, dim3(b->B), dim3(kDqStepThreads), (size_t)dq_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double), (hipStream_t)stream, make_params(b),
-                               (const int32_t*)d_actions, d_state_out, d_reward_out, d_done_out);
-    }
+    if (!b || (!d_actions && b->ops->takes_actions)) return fail(MBX_E_ARG, "mbx_step: bad arguments");
+    if (b->ops->needs_state_out && !d_state_out) return fail(MBX_E_ARG, "mbx_step: this algorithm needs d_state_out");
+    if (int rc = b->ops->step(b, (hipStream_t)stream, d_actions, d_state_out, d_reward_out, d_done_out)) return rc;
     HIP_TRY(hipGetLastError());
     return MBX_OK;
 }
@@ -1392,7 +1394,7 @@ extern "C" int mbx_qlpso_rollout(mbx_batch* b, const double* d_q_table, int n_st
     if (b->cfg.algo != MBX_ALGO_QLPSO) return fail(MBX_E_UNSUPPORTED, "mbx_qlpso_rollout: the batch is not a QLPSO batch");
     if (n_steps < 1) return fail(MBX_E_ARG, "mbx_qlpso_rollout: n_steps must be >= 1");
     if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_qlpso_rollout: a replay tape holds one step");
-    const size_t lds = (size_t)ql_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double);
+    const size_t lds = qlpso_step_lds(b);
     if (n_steps == 1)
         hipLaunchKernelGGL(k_qlpso_step<false>, dim3(b->B), dim3(kThreads), lds, (hipStream_t)stream, make_params(b), (const int32_t*)nullptr,
                            d_q_table, 1, d_state_out, d_reward_out, d_done_out, d_actions_out);
@@ -1497,11 +1499,7 @@ extern "C" int mbx_batch_launch_info(const mbx_batch* b, int32_t out[4])
 {
     if (!b || !out) return fail(MBX_E_ARG, "mbx_batch_launch_info: bad arguments");
     out[0] = b->threads; out[1] = (int32_t)b->lds_bytes; out[2] = b->fixed_geometry; out[3] = (int32_t)b->state_stride;
-    if (b->cfg.algo == MBX_ALGO_NRLPSO) out[1] = (int32_t)(nrlpso_lds_doubles(b->cfg.np, b->cfg.dim, true, b->nrlpso_cached) * sizeof(double));   // the step kernels' (the reset's carve-up is smaller at np = 100)
-    if (b->cfg.algo == MBX_ALGO_LDE && b->fixed_geometry == 3) out[0] = MBX_LDE50_STEP_THREADS;       // k_lde_step's own workgroup size (k_lde_reset keeps b->threads)
-    if (b->cfg.algo == MBX_ALGO_DEDDQN) {                      // the step kernel (small workgroups, one-row evaluator scratch), not k_dq_reset
-        out[0] = kDqStepThreads; out[1] = (int32_t)(dq_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double));
-    }
+    if (b->ops->launch_info) b->ops->launch_info(b, out);
     return MBX_OK;
 }
 

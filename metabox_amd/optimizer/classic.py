@@ -12,53 +12,18 @@ respect to the reference; DE's tournament uses Python's unseeded ``random`` ther
 All arithmetic runs in metabox_amd/csrc/mbx_classic.hpp; ``run_episode`` is the B = 1 view, ``run_batch`` runs many (problem x run)
 pairs in lock step.
 """
-import numpy as np
-import torch
-
 from .._abi import ALGO_CMAES, ALGO_DE, ALGO_PSO
-from .basic_optimizer import Basic_Optimizer
+from .basic_optimizer import Batched_Baseline
 
 
-class _Classic(Basic_Optimizer):
-    _ALGO = None
+class _Classic(Batched_Baseline):
     _NP = 50
-
-    def __init__(self, config):
-        super().__init__(config)
-        self._config = config
-        self.log_interval = config.log_interval
-        self.cost = None
-        self.log_index = None
-
-    def make_batch(self, suite, problem_idx, seeds, early_stop=True):
-        from ..suite import Batch
-        c = self._config
-        return Batch(suite, self._ALGO, problem_idx, seeds, self._NP, c.maxFEs, c.log_interval, c.n_logpoint, early_stop=early_stop)
+    _KEEPS_BATCH = False
 
     def _n_steps(self):
         c = self._config
         evals = c.maxFEs if self._ALGO == ALGO_CMAES else c.maxFEs - self._NP        # CMA-ES evaluates nothing at construction
         return -(-evals // self._NP)
-
-    def run_batch(self, suite, problem_idx, seeds):
-        """-> dict of device tensors (cost [B, n_logpoint+1] padded, fes [B], cost_len [B], ...)."""
-        batch = self.make_batch(suite, problem_idx, seeds)
-        batch.reset()
-        for _ in range(self._n_steps()):
-            batch.step(None)
-        res = batch.results()
-        torch.cuda.synchronize()
-        batch.close()
-        return res
-
-    def run_episode(self, problem):
-        problem.reset()
-        suite = problem._bound_suite()
-        seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2654435761 + int(np.random.randint(0, 2 ** 31 - 1))
-        res = self.run_batch(suite, [problem._suite_index], [seed])
-        n = int(res['cost_len'][0].item())
-        self.cost = [float(v) for v in res['cost'][0, :n].cpu().numpy()]
-        return {'cost': self.cost, 'fes': int(res['fes'][0].item())}
 
 
 class DEAP_DE(_Classic):

@@ -9,29 +9,13 @@ metabox_amd/csrc/mbx_jde21.hpp, pinned to reference traces by tape replay (tests
 F and Cr, and gbest is overwritten, so nothing observable carries over from one episode to the next (the reset / copy counters of the
 reference are counters only; the state block restarts them at every reset).
 """
-import numpy as np
-import torch
-
 from .._abi import ALGO_JDE21
-from .basic_optimizer import Basic_Optimizer
+from .basic_optimizer import Batched_Baseline
 
 
-class JDE21(Basic_Optimizer):
+class JDE21(Batched_Baseline):
+    _ALGO = ALGO_JDE21
     _NP = 170                 # bNP 160 + sNP 10
-
-    def __init__(self, config):
-        super().__init__(config)
-        self._config = config
-        self.log_interval = config.log_interval
-        self.cost = None
-        self.log_index = None
-        self._batch = None
-        self._batch_key = None
-
-    def make_batch(self, suite, problem_idx, seeds, early_stop=True):
-        from ..suite import Batch
-        c = self._config
-        return Batch(suite, ALGO_JDE21, problem_idx, seeds, self._NP, c.maxFEs, c.log_interval, c.n_logpoint, early_stop=early_stop)
 
     @staticmethod
     def _step_bound(max_fes):
@@ -48,7 +32,7 @@ class JDE21(Basic_Optimizer):
                 marks.pop(0)
         return steps
 
-    def _run(self, batch):
+    def _run(self, batch, single=False):
         # the number of updates depends on which halvings an instance meets: launch until every instance is done
         n = self._step_bound(self._config.maxFEs)
         done = None
@@ -57,32 +41,3 @@ class JDE21(Basic_Optimizer):
             if (k % 8 == 7 or k == n - 1) and bool(done.all().item()):
                 break
         assert done is None or bool(done.all().item()), 'JDE21: an instance outlived the step bound'
-
-    def run_batch(self, suite, problem_idx, seeds):
-        """-> dict of device tensors (cost [B, n_logpoint+1] padded, fes [B], cost_len [B], ...)."""
-        batch = self.make_batch(suite, problem_idx, seeds)
-        batch.reset()
-        self._run(batch)
-        res = batch.results()
-        torch.cuda.synchronize()
-        batch.close()
-        return res
-
-    def run_episode(self, problem):
-        problem.reset()
-        suite = problem._bound_suite()
-        seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2654435761 + int(np.random.randint(0, 2 ** 31 - 1))
-        if self._batch is not None and self._batch_key == id(suite):
-            self._batch.rebind([problem._suite_index], [seed])
-        else:
-            if self._batch is not None:
-                self._batch.close()
-            self._batch = self.make_batch(suite, [problem._suite_index], [seed])
-            self._batch_key = id(suite)
-        self._batch.reset()
-        self._run(self._batch)
-        sc = self._batch.read_public(0)
-        n = int(sc[3])
-        self.log_index = int(sc[2])
-        self.cost = [float(v) for v in sc[16:16 + n]]
-        return {'cost': self.cost, 'fes': int(sc[1])}

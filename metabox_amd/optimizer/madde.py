@@ -14,33 +14,18 @@ reset by __init_population.  The batched ``Tester`` tables therefore differ from
 single object through its 51 runs x problems, while every instance of an independent-instance table starts at pm = 1/3.
 """
 import numpy as np
-import torch
 
 from .._abi import ALGO_MADDE
-from .basic_optimizer import Basic_Optimizer
+from .basic_optimizer import Batched_Baseline
 
 
-class MadDE(Basic_Optimizer):
+class MadDE(Batched_Baseline):
+    _ALGO = ALGO_MADDE
     _NMIN = 4
-
-    def __init__(self, config):
-        super().__init__(config)
-        self._config = config
-        self.log_interval = config.log_interval
-        self.cost = None
-        self.log_index = None
-        self._batch = None
-        self._batch_key = None
 
     @staticmethod
     def population_size(dim):
         return 2 * dim * dim
-
-    def make_batch(self, suite, problem_idx, seeds, early_stop=True):
-        from ..suite import Batch
-        c = self._config
-        return Batch(suite, ALGO_MADDE, problem_idx, seeds, self.population_size(suite.dim), c.maxFEs, c.log_interval, c.n_logpoint,
-                     early_stop=early_stop)
 
     @classmethod
     def n_updates(cls, dim, max_fes):
@@ -53,20 +38,10 @@ class MadDE(Basic_Optimizer):
             steps += 1
         return steps
 
-    def _run(self, batch):
+    def _run(self, batch, single=False):
         # done instances stay frozen, so the launches past an early stop change nothing
         for _ in range(self.n_updates(batch.cfg.dim, self._config.maxFEs)):
             batch.step(None)
-
-    def run_batch(self, suite, problem_idx, seeds):
-        """-> dict of device tensors (cost [B, n_logpoint+1] padded, fes [B], cost_len [B], ...)."""
-        batch = self.make_batch(suite, problem_idx, seeds)
-        batch.reset()
-        self._run(batch)
-        res = batch.results()
-        torch.cuda.synchronize()
-        batch.close()
-        return res
 
     def _pm_slice(self):
         D = self._batch.cfg.dim
@@ -74,30 +49,7 @@ class MadDE(Basic_Optimizer):
         o = 3 * n0 * D + 6 * n0 + int(2.3 * n0) * D + 20 * D      # MBX_MADDE_ST_PM (include/mbx_layout.h §13)
         return slice(o, o + 3)
 
-    def run_episode(self, problem):
-        problem.reset()
-        suite = problem._bound_suite()
-        seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2654435761 + int(np.random.randint(0, 2 ** 31 - 1))
-        if self._batch is not None and self._batch_key == id(suite):
-            self._batch.rebind([problem._suite_index], [seed])
-        else:
-            pm = None
-            if self._batch is not None:
-                pm = self._batch.read_state(0)[self._pm_slice()].copy()
-                self._batch.close()
-            self._batch = self.make_batch(suite, [problem._suite_index], [seed])
-            self._batch_key = id(suite)
-            if pm is not None:
-                blk = self._batch.read_state(0)
-                blk[self._pm_slice()] = pm
-                self._batch.write_state(0, blk)
-        self._batch.reset()
-        self._run(self._batch)
-        sc = self._batch.read_public(0)
-        n = int(sc[3])
-        self.log_index = int(sc[2])
-        self.cost = [float(v) for v in sc[16:16 + n]]
-        return {'cost': self.cost, 'fes': int(sc[1])}
+    _carry_slice = _pm_slice
 
     def pm(self):
         """The strategy probabilities the next episode of the B = 1 view starts with."""

@@ -13,29 +13,13 @@ replay (tests/test_sahlpso.py).
 early; instances that do are frozen by the kernel.  ``run_episode`` is the B = 1 view; the reset clears everything, so nothing carries over
 from one episode to the next.
 """
-import numpy as np
-import torch
-
 from .._abi import ALGO_SAHLPSO
-from .basic_optimizer import Basic_Optimizer
+from .basic_optimizer import Batched_Baseline
 
 
-class SAHLPSO(Basic_Optimizer):
+class SAHLPSO(Batched_Baseline):
+    _ALGO = ALGO_SAHLPSO
     _NP = 40
-
-    def __init__(self, config):
-        super().__init__(config)
-        self._config = config
-        self.log_interval = config.log_interval
-        self.cost = None
-        self.log_index = None
-        self._batch = None
-        self._batch_key = None
-
-    def make_batch(self, suite, problem_idx, seeds, early_stop=True):
-        from ..suite import Batch
-        c = self._config
-        return Batch(suite, ALGO_SAHLPSO, problem_idx, seeds, self._NP, c.maxFEs, c.log_interval, c.n_logpoint, early_stop=early_stop)
 
     @classmethod
     def n_generations(cls, max_fes):
@@ -52,35 +36,8 @@ class SAHLPSO(Basic_Optimizer):
                 NP = NP_
         return gens
 
-    def run_batch(self, suite, problem_idx, seeds):
-        """-> dict of device tensors (cost [B, n_logpoint+1] padded, fes [B], cost_len [B], ...)."""
-        batch = self.make_batch(suite, problem_idx, seeds)
-        batch.reset()
+    def _run(self, batch, single=False):
         for _ in range(self.n_generations(self._config.maxFEs)):
-            batch.step(None)
-        res = batch.results()
-        torch.cuda.synchronize()
-        batch.close()
-        return res
-
-    def run_episode(self, problem):
-        problem.reset()
-        suite = problem._bound_suite()
-        seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2654435761 + int(np.random.randint(0, 2 ** 31 - 1))
-        if self._batch is not None and self._batch_key == id(suite):
-            self._batch.rebind([problem._suite_index], [seed])
-        else:
-            if self._batch is not None:
-                self._batch.close()
-            self._batch = self.make_batch(suite, [problem._suite_index], [seed])
-            self._batch_key = id(suite)
-        self._batch.reset()
-        for _ in range(self.n_generations(self._config.maxFEs)):
-            _, _, done = self._batch.step(None)
-            if bool(done[0].item()):
+            _, _, done = batch.step(None)
+            if single and bool(done[0].item()):           # the B = 1 view stops launching at the end of its episode
                 break
-        sc = self._batch.read_public(0)
-        n = int(sc[3])
-        self.log_index = int(sc[2])
-        self.cost = [float(v) for v in sc[16:16 + n]]
-        return {'cost': self.cost, 'fes': int(sc[1])}

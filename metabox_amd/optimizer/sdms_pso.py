@@ -14,31 +14,15 @@ would reach it (above 103 272) is rejected when the batch is created, and so is 
 ``run_batch`` runs many (problem x run) pairs in lock step.  ``run_episode`` is the B = 1 view; __reset clears everything, so nothing
 carries over from one episode to the next.
 """
-import numpy as np
-import torch
-
 from .._abi import ALGO_SDMSPSO
-from .basic_optimizer import Basic_Optimizer
+from .basic_optimizer import Batched_Baseline
 
 
-class sDMS_PSO(Basic_Optimizer):
+class sDMS_PSO(Batched_Baseline):
+    """``make_batch`` accepts `early_stop` for the callers' sake; it has no effect: the reference evaluates `done` only after its last update."""
+    _ALGO = ALGO_SDMSPSO
     _NP = 99
     _LP = 10
-
-    def __init__(self, config):
-        super().__init__(config)
-        self._config = config
-        self.log_interval = config.log_interval
-        self.cost = None
-        self.log_index = None
-        self._batch = None
-        self._batch_key = None
-
-    def make_batch(self, suite, problem_idx, seeds, early_stop=True):
-        """`early_stop` is accepted for the callers' sake and has no effect: the reference evaluates `done` only after its last update."""
-        from ..suite import Batch
-        c = self._config
-        return Batch(suite, ALGO_SDMSPSO, problem_idx, seeds, self._NP, c.maxFEs, c.log_interval, c.n_logpoint, early_stop=early_stop)
 
     @classmethod
     def n_updates(cls, max_fes):
@@ -56,34 +40,3 @@ class sDMS_PSO(Basic_Optimizer):
 
     def _n_steps(self):
         return self.n_updates(self._config.maxFEs)[0]
-
-    def run_batch(self, suite, problem_idx, seeds):
-        """-> dict of device tensors (cost [B, n_logpoint+1] padded, fes [B], cost_len [B], ...)."""
-        batch = self.make_batch(suite, problem_idx, seeds)
-        batch.reset()
-        for _ in range(self._n_steps()):
-            batch.step(None)
-        res = batch.results()
-        torch.cuda.synchronize()
-        batch.close()
-        return res
-
-    def run_episode(self, problem):
-        problem.reset()
-        suite = problem._bound_suite()
-        seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2654435761 + int(np.random.randint(0, 2 ** 31 - 1))
-        if self._batch is not None and self._batch_key == id(suite):
-            self._batch.rebind([problem._suite_index], [seed])
-        else:
-            if self._batch is not None:
-                self._batch.close()
-            self._batch = self.make_batch(suite, [problem._suite_index], [seed])
-            self._batch_key = id(suite)
-        self._batch.reset()
-        for _ in range(self._n_steps()):
-            self._batch.step(None)
-        sc = self._batch.read_public(0)
-        n = int(sc[3])
-        self.log_index = int(sc[2])
-        self.cost = [float(v) for v in sc[16:16 + n]]
-        return {'cost': self.cost, 'fes': int(sc[1])}

@@ -1,0 +1,89 @@
+"""The device-free queries of the library (mbx_state_dim, mbx_action_dim, mbx_tape_stride and the text mbx_last_error leaves behind) over every
+algorithm id, pinned to the answers recorded in tests/golden/algo_queries.json.  The file was recorded from the library as it stood before the
+per-algorithm descriptor table (``AlgoOps`` in metabox_amd/csrc/mbx.hip) replaced the if-chains over ``cfg.algo``: the table must answer
+the same, messages and the order of the checks included.  Re-record with ``MBX_LIB=<library> python tests/test_algo_queries.py``.
+"""
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'algo_queries.json')
+
+SHAPES = ((100, 10), (170, 10), (200, 10), (99, 10), (40, 10), (16, 10), (50, 30), (1000, 10), (100, 65))
+RLEPSO, MADDE, SDMSPSO, SAHLPSO, LES = 1, 15, 18, 20, 21
+
+
+def _cfg(algo, np_, dim, max_fes=20000, log_interval=400, n_logpoint=50, n_group=5, flags=0):
+    return dict(algo=algo, np=np_, dim=dim, max_fes=max_fes, log_interval=log_interval, n_logpoint=n_logpoint, early_stop=1, n_group=n_group, flags=flags)
+
+
+def cases():
+    """name -> cfg fields: the grid of every id 0..23 (the unassigned ones included) over SHAPES, then the single-fault cases and one doubly-wrong cfg."""
+    out = {}
+    for algo in range(24):
+        for np_, dim in SHAPES:
+            out[f'grid-{algo}-{np_}-{dim}'] = _cfg(algo, np_, dim)
+    out['rlepso-n_group-0'] = _cfg(RLEPSO, 100, 10, n_group=0)
+    out['rlepso-n_group-17'] = _cfg(RLEPSO, 100, 10, n_group=17)
+    out['sdmspso-max_fes-np'] = _cfg(SDMSPSO, 99, 10, max_fes=99)
+    out['sahlpso-max_fes-np'] = _cfg(SAHLPSO, 40, 10, max_fes=40)
+    out['les-max_fes-np'] = _cfg(LES, 16, 10, max_fes=16)
+    out['sdmspso-last-budget-before-quasi-newton'] = _cfg(SDMSPSO, 99, 10, max_fes=103272)
+    out['sdmspso-quasi-newton-generation'] = _cfg(SDMSPSO, 99, 10, max_fes=103273)
+    out['sdmspso-quasi-newton-generation-far'] = _cfg(SDMSPSO, 99, 10, max_fes=400000)
+    out['log_interval-0'] = _cfg(RLEPSO, 100, 10, log_interval=0)
+    out['flag-bit-9'] = _cfg(RLEPSO, 100, 10, flags=1 << 9)
+    out['madde-dim-41'] = _cfg(MADDE, 2 * 41 * 41, 41)
+    out['madde-np-wrong-and-dim-65'] = _cfg(MADDE, 100, 65)          # two faults: the algorithm's own limits are checked before the common dim range
+    return out
+
+
+def answers():
+    """name -> [state_dim, action_dim, tape_stride, message]; message is the text a refusal leaves in mbx_last_error, '' where the cfg is valid."""
+    from metabox_amd._abi import AlgoCfg, load_lib
+    lib = load_lib()
+    out = {}
+    for name, f in cases().items():
+        cfg = AlgoCfg(**f)
+        row = []
+        msgs = set()
+        for fn in (lib.mbx_state_dim, lib.mbx_action_dim, lib.mbx_tape_stride):
+            v = int(fn(C.byref(cfg)))
+            row.append(v)
+            if v < 0:
+                msgs.add(lib.mbx_last_error().decode())
+        assert len(msgs) <= 1, (name, msgs)              # the three queries refuse a cfg for the same reason
+        assert bool(msgs) == (row[0] < 0) == (row[2] < 0), (name, row)
+        out[name] = row + [msgs.pop() if msgs else '']
+    return out
+
+
+def test_queries_answer_as_recorded():
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    got = answers()
+    assert sorted(got) == sorted(want)
+    wrong = {k: (got[k], want[k]) for k in got if got[k] != want[k]}
+    assert not wrong, wrong
+
+
+def test_the_examples_of_the_record():
+    """Three answers one can check by hand, so that a re-recorded file cannot drift unnoticed."""
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    assert want['grid-1-100-10'] == [1, 35, 6900, '']
+    assert want['grid-13-100-10'] == [-1, -1, -1, 'JDE21 runs np = 170 (160 + 10 rows), not 100']
+    assert want['grid-12-100-10'][:3] == [-3, -3, -3]
+    assert want['madde-np-wrong-and-dim-65'][3].startswith('MadDE runs dim in [2, ')
+    assert 'quasi-Newton' in want['sdmspso-quasi-newton-generation'][3] and want['sdmspso-last-budget-before-quasi-newton'][3] == ''
+    assert len(want) == 24 * len(SHAPES) + 12
+
+
+if __name__ == '__main__':
+    with open(GOLDEN, 'w') as f:
+        f.write('{\n' + ',\n'.join(f'{json.dumps(k)}: {json.dumps(v)}' for k, v in sorted(answers().items())) + '\n}\n')
+    print(f'wrote {GOLDEN}')

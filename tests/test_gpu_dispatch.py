@@ -1,0 +1,112 @@
+"""Every algorithm id through mbx_batch_create, mbx_reset, one mbx_step and mbx_read_public, bit for bit against tests/golden/dispatch_step.json.
+
+The file was recorded on an MI355X from the library as it stood before the per-algorithm descriptor table (``AlgoOps`` in metabox_amd/csrc/mbx.hip)
+replaced the if-chains over ``cfg.algo``.  The kernels draw from Philox with fixed seeds and use no cross-workgroup atomics, so the same kernel
+with the same workgroup size, LDS size and arguments repeats exactly on the same hardware: equality here says that every row of the table still
+launches what its branch of the chains launched.  Re-record with ``MBX_LIB=<library> python tests/test_gpu_dispatch.py <output.json>`` on the GPU.
+"""
+import ctypes as C
+import functools
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, 'tests')):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+GOLDEN = os.path.join(ROOT, 'tests', 'golden')
+MBX_E_ARG = -1
+
+# id -> (name, np): the smallest valid population, 16 where the algorithm leaves it free
+ALGOS = {1: ('RLEPSO', 16), 2: ('LDE', 16), 3: ('DEDDQN', 16), 4: ('RANDOM_SEARCH', 16), 5: ('RLPSO', 16), 6: ('GLEET', 16), 7: ('QLPSO', 16), 8: ('DE', 16),
+         9: ('PSO', 16), 10: ('CMAES', 16), 11: ('GLPSO', 16), 13: ('JDE21', 170), 15: ('MADDE', 200), 16: ('DEDQN', 16), 18: ('SDMSPSO', 99),
+         19: ('NRLPSO', 16), 20: ('SAHLPSO', 40), 21: ('LES', 16)}
+assert len(ALGOS) == 18              # every id include/mbx.h assigns: 1 .. 21 without 12, 14 and 17
+INT_ACTIONS = (3, 7, 16, 19)         # DE-DDQN, QLPSO, DEDQN, NRLPSO choose among discrete actions
+AGENTS = (1, 2, 3, 5, 6, 7, 16, 19)
+NEED_STATE_OUT = (2, 3)              # LDE, DE-DDQN
+MAX_FES, LOG_INTERVAL, N_LOGPOINT = 2000, 400, 5
+
+
+@functools.lru_cache(maxsize=None)
+def _suite():
+    from helpers import problems
+    from metabox_amd.suite import Suite
+    ps = problems('bbob', 10)
+    return Suite([ps[1], ps[10]])           # Sphere and the rotated Ellipsoidal
+
+
+def _batch(algo):
+    from metabox_amd.suite import Batch
+    b = Batch(_suite(), algo, [0, 1], [1000 + algo, 2000 + algo], ALGOS[algo][1], MAX_FES, LOG_INTERVAL, N_LOGPOINT)
+    if algo == 21:
+        with np.load(os.path.join(GOLDEN, 'les_policy.npz')) as z:
+            b.les_set_params(z['bbob/best_x'])
+    return b
+
+
+def run(algo):
+    """-> {'launch_info': {...}, 'public': [[hex, ...] per instance]} after reset and one step with all-zero actions."""
+    import torch
+    b = _batch(algo)
+    b.reset()
+    act = None
+    if b.action_dim > 0:
+        act = torch.zeros(b.B, b.action_dim, dtype=torch.int32 if algo in INT_ACTIONS else torch.float32, device='cuda')
+    b.step(act)
+    torch.cuda.synchronize()
+    out = {'launch_info': {k: int(v) for k, v in b.launch_info().items()}, 'public': [[float(v).hex() for v in b.read_public(i)] for i in range(b.B)]}
+    b.close()
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _want():
+    with open(os.path.join(GOLDEN, 'dispatch_step.json')) as f:
+        return json.load(f)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('algo', sorted(ALGOS), ids=lambda a: ALGOS[a][0])
+def test_reset_and_one_step_as_recorded(algo):
+    got, want = run(algo), _want()[ALGOS[algo][0]]
+    assert len(want['public']) == 2 and len(want['public'][0]) == 16 + N_LOGPOINT + 1
+    assert float.fromhex(want['public'][0][1]) >= ALGOS[algo][1], 'the record must hold a batch that has evaluated its population'
+    assert got == want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('algo', AGENTS, ids=lambda a: ALGOS[a][0])
+def test_step_refuses_null_actions_of_an_agent_algorithm(algo):
+    from metabox_amd._abi import load_lib
+    from metabox_amd.suite import _ptr, _stream
+    lib, b = load_lib(), _batch(algo)
+    rc = lib.mbx_step(b._h, C.c_void_p(), _ptr(b.state), _ptr(b.reward), _ptr(b.done), _stream())        # returns before anything is launched
+    assert rc == MBX_E_ARG and lib.mbx_last_error() == b'mbx_step: bad arguments'
+    b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('algo', NEED_STATE_OUT, ids=lambda a: ALGOS[a][0])
+def test_reset_and_step_refuse_a_null_state_out_where_the_kernel_writes_features(algo):
+    import torch
+    from metabox_amd._abi import load_lib
+    from metabox_amd.suite import _ptr, _stream
+    lib, b = load_lib(), _batch(algo)
+    assert lib.mbx_reset(b._h, C.c_void_p(), _stream()) == MBX_E_ARG                                      # returns before anything is launched
+    assert lib.mbx_last_error() == b'mbx_reset: this algorithm needs d_state_out'
+    act = torch.zeros(b.B, b.action_dim, dtype=torch.int32 if algo in INT_ACTIONS else torch.float32, device='cuda')
+    assert lib.mbx_step(b._h, _ptr(act), C.c_void_p(), _ptr(b.reward), _ptr(b.done), _stream()) == MBX_E_ARG
+    assert lib.mbx_last_error() == b'mbx_step: this algorithm needs d_state_out'
+    b.close()
+
+
+if __name__ == '__main__':
+    rec = {ALGOS[a][0]: run(a) for a in sorted(ALGOS)}
+    with open(sys.argv[1], 'w') as f:
+        f.write('{\n' + ',\n'.join(f'{json.dumps(k)}: {json.dumps(v)}' for k, v in sorted(rec.items())) + '\n}\n')
+    print(f'wrote {sys.argv[1]}')
