@@ -200,7 +200,14 @@ int mbx_step(mbx_batch* b, const void* d_actions, double* d_state_out, double* d
 /* Per-instance results, the fields rollout_episode returns (src/agent/rlepso_agent.py:294-303):
  * cost curve `optimizer.cost` padded to n_logpoint+1 entries with its last value
  * (src/tester.py:204-205), fes, return (sum of rewards), executed env-steps, and the live length of the
- * cost list.  Any pointer may be NULL. */
+ * cost list.  Any pointer may be NULL.
+ *
+ * The curve bound.  The reference appends to `optimizer.cost` at a log point without looking at the list's length (e.g. rlepso_optimizer.py:241-243); only the closing
+ * entry does (:257-261).  A budget with log_interval * (n_logpoint + 1) <= max_fes (maxFEs 976, n_logpoint 50: log_interval 19, 52 entries) therefore grows the list
+ * past n_logpoint + 1.  An instance's curve has n_logpoint + 1 slots (MBX_LES_CURVE_CAP for LES, include/mbx_layout.h), and every kernel keeps to them: a write to
+ * curve index > n_logpoint -- a log-point append or the closing overwrite -- is dropped, and the length goes on counting it.  The stored entries are exactly the first
+ * n_logpoint + 1 of the reference's list, d_cost_len / MBX_SC_COST_LEN is the list's true length (it can exceed n_logpoint + 1), and a configuration whose curve fits
+ * stores what it always did.  The baselines whose reference guards its own append (GL-PSO, JDE21, MadDE, sDMS-PSO, SAHLPSO) never reach the bound. */
 int mbx_results(mbx_batch* b, double* d_cost_curves /* [B, n_logpoint+1] */, double* d_fes /* [B] */,
                 double* d_return /* [B] */, int32_t* d_steps /* [B] */, int32_t* d_cost_len /* [B] */,
                 void* stream);

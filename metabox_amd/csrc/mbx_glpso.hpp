@@ -247,12 +247,12 @@ __global__ __launch_bounds__(kThreads) void k_glpso_generation(BatchParams bp, d
         const double fes1 = sc[MBX_SC_FES] + NP, fes = fes1 + NP;
         int log_index = (int)sc[MBX_SC_LOG_INDEX], cost_len = (int)sc[MBX_SC_COST_LEN];
         double* cost = sc + MBX_NSCALAR;
-        if (fes1 >= (double)log_index * bp.log_interval) { log_index += 1; if (cost_len <= bp.n_logpoint) cost[cost_len++] = gbest; }
+        if (fes1 >= (double)log_index * bp.log_interval) { log_index += 1; if (cost_len <= bp.n_logpoint) curve_put(cost, bp.n_logpoint, cost_len++, gbest); }
         bool done = fes >= bp.max_fes;
         if (!isnan(P.optimum) && bp.early_stop) done = done || gbest <= 1e-8;
         if (done) {
-            if (cost_len >= bp.n_logpoint + 1) cost[cost_len - 1] = gbest;
-            else cost[cost_len++] = gbest;
+            if (cost_len >= bp.n_logpoint + 1) curve_put(cost, bp.n_logpoint, cost_len - 1, gbest);
+            else curve_put(cost, bp.n_logpoint, cost_len++, gbest);
         }
         sc[MBX_SC_GBEST] = gbest; sc[MBX_SC_FES] = fes; sc[MBX_SC_LOG_INDEX] = log_index; sc[MBX_SC_COST_LEN] = cost_len;
         sc[MBX_SC_DONE] = done ? 1. : 0.; sc[MBX_SC_GEN] = gen;

@@ -838,12 +838,12 @@ __device__ __noinline__ int lde_run_generations(int b_, int gen0_, int episode_,
             bool dn;
             {   // log_and_terminate (mbx_rlepso.hpp) on the argument block's fields
                 double* cost = sc + MBX_NSCALAR;
-                if (fes_next >= (double)log_index * ar.bp.log_interval) { log_index += 1; cost[cost_len++] = bsf_next; }
+                if (fes_next >= (double)log_index * ar.bp.log_interval) { log_index += 1; curve_put(cost, ar.bp.n_logpoint, cost_len++, bsf_next); }
                 dn = fes_next >= ar.bp.max_fes;
                 if (!isnan(P.optimum) && ar.bp.early_stop) dn = dn || bsf_next <= 1e-8;
                 if (dn) {
-                    if (cost_len >= ar.bp.n_logpoint + 1) cost[cost_len - 1] = bsf_next;
-                    else cost[cost_len++] = bsf_next;
+                    if (cost_len >= ar.bp.n_logpoint + 1) curve_put(cost, ar.bp.n_logpoint, cost_len - 1, bsf_next);
+                    else curve_put(cost, ar.bp.n_logpoint, cost_len++, bsf_next);
                 }
             }
             L.SCAL[LR_FES] = fes_next; L.SCAL[LR_HCOUNT] += 1.; L.SCAL[LR_BSF] = bsf_next;      // (fes is in every thread's registers; the new history length is read below, behind the barrier)

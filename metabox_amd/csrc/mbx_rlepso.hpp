@@ -31,16 +31,25 @@ struct BatchParams {
 // optimizer.cost bookkeeping shared by every update() of the reference (e.g. rlepso_optimizer.py:241-261): append gbest when fes
 // reaches the next log point (one append per call at most), decide termination, and on termination overwrite the last entry if the
 // curve is already n_logpoint + 1 long, else append.  `cost` is the instance's curve in HBM; returns is_done.
+//
+// The curve bound (include/mbx.h): the log-point append is unguarded in the reference, so its list can outgrow the n_logpoint + 1 slots of an instance's curve
+// (maxFEs = 976, log_interval = 19: 52 entries).  Every curve write goes through curve_put: a write to an index past n_logpoint -- an append or the closing
+// overwrite -- is dropped, and cost_len goes on counting, so the slots hold the first n_logpoint + 1 entries of the reference's list and MBX_SC_COST_LEN its length.
+__device__ __forceinline__ void curve_put(double* __restrict__ cost, int n_logpoint, int idx, double v)
+{
+    if (idx <= n_logpoint) cost[idx] = v;
+}
+
 template <class PT>
 __device__ __forceinline__ bool log_and_terminate(const BatchParams& bp, const PT& P, double fes, double gbest, int& log_index,
                                                   int& cost_len, double* __restrict__ cost)
 {
-    if (fes >= (double)log_index * bp.log_interval) { log_index += 1; cost[cost_len++] = gbest; }
+    if (fes >= (double)log_index * bp.log_interval) { log_index += 1; curve_put(cost, bp.n_logpoint, cost_len++, gbest); }
     bool done = fes >= bp.max_fes;
     if (!isnan(P.optimum) && bp.early_stop) done = done || gbest <= 1e-8;
     if (done) {
-        if (cost_len >= bp.n_logpoint + 1) cost[cost_len - 1] = gbest;
-        else cost[cost_len++] = gbest;
+        if (cost_len >= bp.n_logpoint + 1) curve_put(cost, bp.n_logpoint, cost_len - 1, gbest);
+        else curve_put(cost, bp.n_logpoint, cost_len++, gbest);
     }
     return done;
 }
@@ -1309,12 +1318,12 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         // ---- logging, termination, reward (:241-261): the counters are scalars (see above), the two float64 compares on gbest are made wave-uniform by a ballot;
         // thread 0 writes the curve.  (fes and the log point are integers below 2^31 and 2^62: the integer compare is the reference's float64 one)
 #ifndef MBX_ABLATE_LOG
-        if ((int64_t)fes >= (int64_t)log_index * ar().bp.log_interval) { log_index += 1; if (tid == 0) cost[cost_len] = gbest; cost_len += 1; }
+        if ((int64_t)fes >= (int64_t)log_index * ar().bp.log_interval) { log_index += 1; if (tid == 0) curve_put(cost, ar().bp.n_logpoint, cost_len, gbest); cost_len += 1; }
         done = fes >= ar().bp.max_fes;
         if (!isnan(P.optimum) && ar().bp.early_stop) done = done || __builtin_amdgcn_ballot_w64(gbest <= 1e-8) != 0ull;
         if (done) {
-            if (cost_len >= ar().bp.n_logpoint + 1) { if (tid == 0) cost[cost_len - 1] = gbest; }
-            else { if (tid == 0) cost[cost_len] = gbest; cost_len += 1; }
+            if (cost_len >= ar().bp.n_logpoint + 1) { if (tid == 0) curve_put(cost, ar().bp.n_logpoint, cost_len - 1, gbest); }
+            else { if (tid == 0) curve_put(cost, ar().bp.n_logpoint, cost_len, gbest); cost_len += 1; }
         }
         const bool improved = __builtin_amdgcn_ballot_w64(gbest < pre_gbest) != 0ull;
         ret += improved ? 1 : -1;

@@ -300,14 +300,14 @@ __global__ __launch_bounds__(kThreads) void k_sahlpso_generation(BatchParams bp,
         fes += 1;                                                     // :92
         if ((double)fes >= (double)log_index * bp.log_interval) {    // :110-112, once
             log_index += 1;
-            if (cost_len <= bp.n_logpoint) { if (tid == 0) cost[cost_len] = gbest; cost_len += 1; }
+            if (cost_len <= bp.n_logpoint) { if (tid == 0) curve_put(cost, bp.n_logpoint, cost_len, gbest); cost_len += 1; }
         }
         done = fes >= bp.max_fes || (stop_rule && gbest <= 1e-8);     // :114-117
     }
     if (tid == 0) {
         if (done) {                                                   // :119-124
-            if (cost_len >= bp.n_logpoint + 1) cost[cost_len - 1] = gbest;
-            else cost[cost_len++] = gbest;
+            if (cost_len >= bp.n_logpoint + 1) curve_put(cost, bp.n_logpoint, cost_len - 1, gbest);
+            else curve_put(cost, bp.n_logpoint, cost_len++, gbest);
         } else {
             if (step % MBX_SAHL_LP == 0) {                            // :126-147
                 double sum = 0.;

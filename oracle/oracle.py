@@ -728,6 +728,7 @@ def _classic_lib():
         L.orc_classic_step.argtypes = [C.c_void_p]
         L.orc_classic_result.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int), _dp, _dp]
         L.orc_classic_population.argtypes = [C.c_void_p, _dp, _dp]
+        L.orc_classic_pbest.argtypes = [C.c_void_p, _dp, _dp]
         L.orc_classic_cma_state.argtypes = [C.c_void_p, _dp]
         L.orc_classic_set_cma_state.argtypes = [C.c_void_p, _dp]
         L._classic_ready = True
@@ -764,6 +765,12 @@ class ClassicOracle:
         X, c = np.empty((self.cfg.np, self.cfg.dim)), np.empty(self.cfg.np)
         _classic_lib().orc_classic_population(self._h, _p(X), _p(c))
         return X, c
+
+    def pbest(self):
+        """PSO only: personal-best positions and costs."""
+        PB, c = np.empty((self.cfg.np, self.cfg.dim)), np.empty(self.cfg.np)
+        _classic_lib().orc_classic_pbest(self._h, _p(PB), _p(c))
+        return PB, c
 
     def cma_state(self):
         """CMA-ES only: the state block in the kernel's layout (include/mbx_layout.h §10)."""

@@ -385,7 +385,9 @@ def _pairs(algo, st, NP, D):
 @pytest.mark.parametrize('name,D,NP,geom,generic', [('lde', 10, 50, 9, False), ('lde', 30, 50, 3, False), ('lde', 30, 100, 6, False),
                                                     ('lde', 10, 50, 0, True), ('gleet', 10, 100, 5, False), ('gleet', 10, 100, 0, True),
                                                     ('rlpso', 10, 100, 0, False), ('qlpso', 10, 100, 0, False), ('de', 10, 50, 0, False),
-                                                    ('pso', 10, 50, 0, False)])
+                                                    ('pso', 10, 50, 0, False)] +
+                         # edge geometries (tests/test_gpu_geometry_edges.py): NP D odd at 63 x 7 and 65 x 33, more than one wave, the widest rows
+                         [(name, D, NP, 0, False) for name in ('lde', 'gleet', 'rlpso', 'qlpso', 'de', 'pso') for NP, D in ((63, 7), (65, 33), (100, 40))])
 def test_other_optimizers_natural_episodes(name, D, NP, geom, generic):
     """Every stored (position, cost) pair after the reset and after each of five generations, on all 24 kinds plus the noisy suite's
     functions with the noise switched off."""

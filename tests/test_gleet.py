@@ -100,34 +100,15 @@ def test_hip_gleet_tape_replay_matches_reference():
 
 @pytest.mark.gpu
 def test_hip_gleet_philox_parity_with_oracle():
-    import torch
+    import parity
     from metabox_amd.suite import Batch, Suite
     ps = problems('bbob-noisy', 10)
     ids = sorted(ps)
     s = Suite([ps[i] for i in ids])
     B, G = len(ids), 40
-    rs = np.random.RandomState(21)
-    actions = rs.rand(G, B, NP).astype(np.float32)
-    seeds = np.arange(B, dtype=np.uint64) * 53 + 17
+    seeds = parity.seeds_for('gleet', B)
     b = Batch(s, ALGO_GLEET, np.arange(B), seeds, NP, 20000, 400, 50)
-    st0 = b.reset().cpu().numpy().reshape(B, NP, 27).copy()
-    hist = []
-    for g in range(G):
-        st, r, d = b.step(torch.from_numpy(actions[g]).cuda())
-        hist.append((st.cpu().numpy().reshape(B, NP, 27).copy(), r.cpu().numpy().copy()))
-    cfg = oracle.make_cfg(ALGO_GLEET, NP, 10, 20000, 400, 50)
-    for k in range(B):
-        p = s.problems[k]
-        o = oracle.GleetOracle(p.desc(), p.bias, cfg, seed=int(seeds[k]))
-        f0 = o.reset()
-        assert _feat_close(st0[k], f0), ids[k]
-        for g in range(G):
-            f, rew, d = o.step(actions[g, k])
-            assert _feat_close(hist[g][0][k], f), (ids[k], g)
-            assert abs(rew - hist[g][1][k]) <= 1e-5 * abs(rew) + 1e-9, (ids[k], g)
-        fin, ref = oracle.split_gleet_state(b.read_state(k), NP, 10, 50), oracle.split_gleet_state(o.state(), NP, 10, 50)
-        assert close(fin['pbest'], ref['pbest']) and np.array_equal(fin['pni'], ref['pni']) and close(fin['scalars'][:7], ref['scalars'][:7])
-        assert np.abs(fin['pfeat'] - ref['pfeat']).max() <= 1e-7 and np.abs(fin['gfeat'] - ref['gfeat']).max() <= 1e-7
+    parity.canonical('gleet', b, s.problems, seeds, NP, 10, (20000, 400, 50), G, ids)
     b.close()
 
 

@@ -94,33 +94,13 @@ def test_lde_tape_replay_matches_reference_episodes(suite, dim, NP):
 def test_lde_philox_parity_with_oracle(suite, dim, NP):
     from metabox_amd.suite import Batch
     from metabox_amd._abi import ALGO_LDE
+    import parity
     s, ids = _suite(suite, dim)
     B, G = len(ids), 30
     maxfes = 2000 * dim
-    rs = np.random.RandomState(5)
-    actions = rs.uniform(0, 1, size=(G, B, 2 * NP)).astype(np.float32)
-    seeds = np.arange(B, dtype=np.uint64) * 104729 + 3
+    seeds = parity.seeds_for('lde', B)
     batch = Batch(s, ALGO_LDE, np.arange(B), seeds, NP, maxfes, maxfes // 50, 50)
-    st0 = batch.reset().cpu().numpy().copy()
-    hist = []
-    for g in range(G):
-        st, r, d = batch.step(torch.from_numpy(actions[g]).cuda())
-        hist.append((st.cpu().numpy().copy(), r.cpu().numpy().copy()))
-    cfg = oracle.make_cfg(2, NP, dim, maxfes, maxfes // 50, 50)
-    for b in range(B):
-        p = s.problems[b]
-        o = oracle.LdeOracle(p.desc(), p.bias, cfg, seed=int(seeds[b]))
-        f0 = o.reset()
-        assert np.abs(f0 - st0[b]).max() <= 1e-7, ids[b]
-        for g in range(G):
-            f, rew, d = o.step(actions[g, b])
-            assert np.abs(f - hist[g][0][b]).max() <= 1e-5, (ids[b], g)
-            assert abs(rew - hist[g][1][b]) <= 1e-5 * abs(rew) + 1e-9, (ids[b], g)
-        want = oracle.split_lde_state(o.state(), NP, dim, 50)
-        got = oracle.split_lde_state(batch.read_state(b), NP, dim, 50)
-        assert close(got['fit'], want['fit']), ids[b]
-        assert np.abs(got['pop'] - want['pop']).max() <= 1e-9, ids[b]
-        assert np.array_equal(got['hsum'][:5], want['hsum'][:5])       # (slot 5: the kernel's packed copy of the last histogram)
+    parity.canonical('lde', batch, s.problems, seeds, NP, dim, (maxfes, maxfes // 50, 50), G, ids)
     batch.close()
 
 

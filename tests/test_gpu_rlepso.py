@@ -706,9 +706,9 @@ def test_end_to_end_statistics_match_the_reference():
 @pytest.mark.parametrize('dim', [5, 7])
 def test_odd_dimension_single_coordinate_work_items(dim):
     """Odd D takes the one-coordinate work-item path of the move phase (even D pairs coordinates): HIP == oracle under Philox for
-    RLEPSO, and the other generation kernels run at the same dimension."""
+    RLEPSO, and for LDE and GLEET at the same dimension."""
     from metabox_amd.suite import Batch, Suite
-    from metabox_amd._abi import ALGO_GLEET, ALGO_LDE, ALGO_RLEPSO
+    from metabox_amd._abi import ALGO_RLEPSO
     ps = problems('bbob', dim)
     ids = [1, 3, 8, 15, 17, 21]
     s = Suite([ps[i] for i in ids])
@@ -722,12 +722,13 @@ def test_odd_dimension_single_coordinate_work_items(dim):
     ledger, exact_until = _hip_vs_oracle(batch, s.problems, seeds, actions, dim, maxfes, maxfes // nlog, nlog, f'bbob d={dim}')
     print_ledger(ledger)
     batch.close()
-    for algo, np_, adim in ((ALGO_LDE, 50, 100), (ALGO_GLEET, 100, 100)):
-        bt = Batch(s, algo, np.arange(B), seeds, np_, maxfes, maxfes // nlog, nlog)
-        st0 = bt.reset().clone()
-        st1, r, d = bt.step(torch.rand(B, adim, device='cuda'))
-        assert torch.isfinite(st1).all() and torch.isfinite(r).all() and not torch.equal(st0, st1)
-        bt.close()
+    import parity
+    for name, np_ in (('lde', 50), ('gleet', 100)):                   # six generations against the oracle, a view after every one (tests/parity.py)
+        ledger = []
+        total, info, _, _ = parity.hip_vs_oracle(name, [ps[i] for i in ids], np_, dim, (maxfes, maxfes // nlog, nlog), 6, ledger)
+        assert info['fixed_geometry'] == 0, info
+        print(f'{name} d={dim}: worst deviation / tolerance {max(total.values()):.3g}')
+        print_ledger(ledger)
 
 
 def test_compile_time_geometry_kernel_equals_generic_kernel(env, monkeypatch):

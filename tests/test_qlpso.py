@@ -151,27 +151,11 @@ def test_hip_qlpso_philox_parity_and_fused_rollout():
     ps = problems('bbob-noisy', 10)
     ids = sorted(ps)
     s = Suite([ps[i] for i in ids])
+    import parity
     B, G = len(ids), 100
-    rs = np.random.RandomState(31)
-    actions = rs.randint(0, 4, size=(G, B)).astype(np.int32)
-    seeds = np.arange(B, dtype=np.uint64) * 71 + 2
+    seeds = parity.seeds_for('qlpso', B)
     b = Batch(s, ALGO_QLPSO, np.arange(B), seeds, NP, 2500, 50, 50)
-    st0 = b.reset().cpu().numpy().copy()
-    hist = []
-    for g in range(G):
-        st, r, d = b.step(torch.from_numpy(actions[g]).cuda())
-        hist.append((st.cpu().numpy().copy(), r.cpu().numpy().copy()))
-    cfg = oracle.make_cfg(ALGO_QLPSO, NP, 10, 2500, 50, 50)
-    for k in range(B):
-        p = s.problems[k]
-        o = oracle.QlpsoOracle(p.desc(), p.bias, cfg, seed=int(seeds[k]))
-        assert o.reset() == int(st0[k, 0]), ids[k]
-        for g in range(G):
-            sn, rew, d = o.step(int(actions[g, k]))
-            assert sn == int(hist[g][0][k, 0]) and rew == hist[g][1][k], (ids[k], g)
-        fin, ref = oracle.split_qlpso_state(b.read_state(k), NP, 10, 50), oracle.split_qlpso_state(o.state(), NP, 10, 50)
-        assert close(fin['cost'], ref['cost']) and np.abs(fin['pop'] - ref['pop']).max() <= 1e-9 and close(fin['scalars'][:7], ref['scalars'][:7])
-        assert fin['scalars'][oracle.SC_QLPSO_DIVERSITY] == pytest.approx(ref['scalars'][oracle.SC_QLPSO_DIVERSITY], rel=1e-12)
+    parity.canonical('qlpso', b, s.problems, seeds, NP, 10, (2500, 50, 50), G, ids)
     b.close()
     # fused: multi-step == single-step launches
     q = torch.from_numpy(Q).cuda()

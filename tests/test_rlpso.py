@@ -97,36 +97,15 @@ def test_hip_rlpso_tape_replay_matches_reference():
 
 @pytest.mark.gpu
 def test_hip_rlpso_philox_parity_with_oracle():
-    import torch
+    import parity
     from metabox_amd.suite import Batch, Suite
     ps = problems('bbob-noisy', 10)
     ids = sorted(ps)
     s = Suite([ps[i] for i in ids])
     B, G = len(ids), 230                                        # > 2 sweeps over the swarm
-    rs = np.random.RandomState(11)
-    actions = (rs.rand(G, B) * 1.4 - 0.2).astype(np.float32)
-    seeds = np.arange(B, dtype=np.uint64) * 37 + 9
+    seeds = parity.seeds_for('rlpso', B)
     b = Batch(s, ALGO_RLPSO, np.arange(B), seeds, NP, 2500, 50, 50)
-    st0 = b.reset().cpu().numpy().copy()
-    hist = []
-    for g in range(G):
-        st, r, d = b.step(torch.from_numpy(actions[g]).cuda())
-        hist.append((st.cpu().numpy().copy(), r.cpu().numpy().copy(), d.cpu().numpy().copy()))
-    cfg = oracle.make_cfg(ALGO_RLPSO, NP, 10, 2500, 50, 50)
-    for k in range(B):
-        p = s.problems[k]
-        o = oracle.RlpsoOracle(p.desc(), p.bias, cfg, seed=int(seeds[k]))
-        f0 = o.reset()
-        assert np.all(np.abs(f0 - st0[k]) <= 1e-12 * np.abs(f0) + 1e-13), ids[k]
-        for g in range(G):
-            f, rew, d = o.step(actions[g, k])
-            got = hist[g][0][k]
-            assert np.all(np.abs(f - got) <= 1e-9 * np.abs(f) + 1e-11), (ids[k], g)
-            assert abs(rew - hist[g][1][k]) <= 1e-5 * abs(rew) + 1e-9, (ids[k], g)
-            assert bool(hist[g][2][k]) == d
-        fin, ref = oracle.split_rlpso_state(b.read_state(k), NP, 10, 50), oracle.split_rlpso_state(o.state(), NP, 10, 50)
-        assert close(fin['pbest'], ref['pbest']) and close(fin['scalars'][:7], ref['scalars'][:7]), ids[k]
-        assert np.abs(fin['pbpos'] - ref['pbpos']).max() <= 1e-9
+    parity.canonical('rlpso', b, s.problems, seeds, NP, 10, (2500, 50, 50), G, ids)
     b.close()
 
 
