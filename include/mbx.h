@@ -113,6 +113,7 @@ int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, double* d_f,
 #define MBX_ALGO_DEDQN  16  /* src/optimizer/dedqn_optimizer.py     one step = one trial vector + the landscape analysis (2 NP FEs), np in [4, 128], dim <= 40 */
 #define MBX_ALGO_NRLPSO 19  /* src/optimizer/nrlpso_optimizer.py    one step = one particle (1 FE, 3 when the neighbourhood mutation fires), np in [8, 128], dim <= 40 */
 #define MBX_ALGO_LES    21  /* src/optimizer/les_optimizer.py      one step = one generation (16 FEs) of a learned diagonal ES; np = 16, dim <= 40, max_fes > 16; parameters per instance (mbx_les_set_params) */
+#define MBX_ALGO_RLHPSDE 24 /* src/optimizer/rl_hpsde_optimizer.py  one step = one update (NP FEs) + the landscape walk (201 FEs), np = 18 dim shrinking towards 4, dim <= 40, max_fes > np + 201; rollout entry point: include/mbx_rlhpsde.h (22 and 23 are not assigned and stay rejected) */
 #define MBX_ALGO_SAHLPSO 20 /* src/optimizer/sahlpso.py            one step = one pass over the live particles (NP FEs, NP shrinking 40 -> 4; fewer when the episode ends inside the pass), np = 40, dim <= 40, max_fes > 40 -- classic baseline, no agent */
 
 typedef struct mbx_algo_cfg {

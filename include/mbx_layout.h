@@ -871,6 +871,98 @@
 #define MBX_SITE_LES_NOISE_A 64u
 #define MBX_SITE_LES_NOISE_B 65u
 
+/* ---------------------------------------------------------------- 19. RL-HPSDE (rl_hpsde_optimizer.py) layouts
+ * SHADE-style DE with a success-history memory MF / MCr of H = int(0.5 D) entries, linear population size reduction from N0 = 18 D rows towards 4,
+ * and a tabular agent whose action picks the mutation (action & 1: cur_to_rand_1 / cur_to_best_1) and the law of F (action >> 1: Cauchy / Levy).
+ * After the reset and after EVERY update a progressive random walk of 201 points is drawn, evaluated and billed, and two landscape bits make the
+ * state = DFDC + 2 DRIE in 0..3.  mbx_reset is init_population (:123-131), mbx_step one update (:231-287) with the caller's int32 action,
+ * mbx_rlhpsde_rollout (include/mbx_rlhpsde.h) n_steps updates in one launch with the 4 x 4 Q-table.  cfg.np must be 18 dim, 2 <= dim <= 40,
+ * max_fes > np + 201.  state [1] = the landscape state, action [1] int32.  Rules and the quirks kept: the header of mbx_rlhpsde.hpp.
+ * state block: pop[2][N0*D] (two buffers, MBX_SC_HP_LIVE names the live one; rows sorted by (cost, row)) cost[N0] MF[H] MCr[H] u[N0*D] (trial rows)
+ *   ncost[N0] F[N0] Cr[N0] r[3*N0] (the indices of the last mutation, r[3 i + c]) z[N0] x[N0] (the standard normal behind Cr and the Cauchy / Levy
+ *   variate behind F of the last update, so that a Philox run can be fed back as a tape) walk[201*D] wcost[201] feat[MBX_RLHPSDE_FEAT_SLOTS]
+ *   scalars[16] cost_curve[n_logpoint + 1].  feat: the correlation r, the entropy, its level, the improved rows of the last update, then the
+ *   transition counts count[level][class] of the nine levels (classes in the reference's order: -1>0, -1>1, 0>-1, 0>1, 1>-1, 1>0).
+ * The tape has one walk section in front, shared by reset and step, then the reset's or the step's own part:
+ *   walk:  zone_u[D] | off_u[D] | step_u[200*D] | rD | choice_u | wnoise[3*201]      (draw order :152, :155, :157, :163; choice_u: the agent's uniform,
+ *          read by mbx_rlhpsde_rollout only)
+ *   reset: pos_u[N0*D] | noise[3*N0]
+ *   step:  mem[N0] | z[N0] | x[N0] | r[3*N0] | jrand[N0] | noise[3*N0] | cross_u[N0*D]    (rows past the live NP are not read)
+ *          z: the standard normal behind Cr (Cr = clip(MCr[mem] + 0.1 z)); x: the standard Cauchy or Levy variate (F = 0.1 x + MF[mem]);
+ *          r: the RESOLVED indices of generate_random_int (mutate.py:12-33), r[3 i + c]; column 2 is not read by cur_to_best_1.
+ * A tape holds one update: with a tape n_steps must be 1.
+ * Philox, counter (index, site, gen, episode); reset gen = 0, update gen = number of the update:
+ *   MBX_SITE_HP_PAR(i)        mulhi(w0, H) = mem, mulhi(w1, D) = jrand
+ *   MBX_SITE_HP_NORM(i)       box_muller(u53(w0,w1), u53(w2,w3)): the cosine half = z, the sine half s gives the Levy variate x = 1 / s^2
+ *   MBX_SITE_HP_CAUCHY(i)     tan(pi (u53(w0,w1) - 0.5)) = the Cauchy variate x
+ *   MBX_SITE_HP_IDX(i*32+a)   attempt a = 0..25 of the bounded redraw: mulhi(w0, NP) = r0, mulhi(w1, NP) = r1, mulhi(w2, NP) = r2, each column with
+ *                             its own attempt counter
+ *   MBX_SITE_HP_CROSS(i*D+d)  u53(w0,w1) = cross_u;  reset: index e, u53(w0,w1) = pos_u
+ *   MBX_SITE_HP_NOISE_A/B(i)  evaluation of trial row i;  reset: MBX_SITE_NOISE1_A/B(i)
+ *   MBX_SITE_HP_WALK(e)       e < D: u53(w0,w1) = zone_u[e], u53(w2,w3) = off_u[e];  e = D + k: u53(w0,w1) = step_u[k];  e = 201 D: mulhi(w0, D) = rD
+ *   MBX_SITE_HP_WNOISE_A/B(j) evaluation of walk point j
+ *   MBX_SITE_POLICY(0)        u53(w0,w1) = choice_u                                                                                             */
+#define MBX_RLHPSDE_NP(D)                (18 * (D))
+#define MBX_RLHPSDE_DIM_MAX              40
+#define MBX_RLHPSDE_MEM(D)                 ((int64_t)((D) / 2))
+#define MBX_RLHPSDE_WALK                 201     /* rw_steps + 1 points */
+#define MBX_RLHPSDE_NLEVEL               9
+#define MBX_RLHPSDE_NCLASS               6
+#define MBX_RLHPSDE_FEAT_R               0
+#define MBX_RLHPSDE_FEAT_H               1
+#define MBX_RLHPSDE_FEAT_LEVEL           2
+#define MBX_RLHPSDE_FEAT_NOPT            3
+#define MBX_RLHPSDE_FEAT_COUNTS          10
+#define MBX_RLHPSDE_FEAT_SLOTS           64
+#define MBX_RLHPSDE_TAPE_ZONE(NP, D)     ((int64_t)0)
+#define MBX_RLHPSDE_TAPE_OFF(NP, D)      ((int64_t)(D))
+#define MBX_RLHPSDE_TAPE_STEPU(NP, D)    (2 * (int64_t)(D))
+#define MBX_RLHPSDE_TAPE_RD(NP, D)       (202 * (int64_t)(D))
+#define MBX_RLHPSDE_TAPE_CHOICE(NP, D)   (202 * (int64_t)(D) + 1)
+#define MBX_RLHPSDE_TAPE_WNOISE(NP, D)   (202 * (int64_t)(D) + 2)
+#define MBX_RLHPSDE_TAPE_BASE(NP, D)     (202 * (int64_t)(D) + 2 + 3 * MBX_RLHPSDE_WALK + 1)
+#define MBX_RLHPSDE_TAPE_POS(NP, D)      MBX_RLHPSDE_TAPE_BASE(NP, D)
+#define MBX_RLHPSDE_TAPE_NOISE_INIT(NP, D) (MBX_RLHPSDE_TAPE_BASE(NP, D) + (int64_t)(NP) * (D))
+#define MBX_RLHPSDE_TAPE_MEM(NP, D)      MBX_RLHPSDE_TAPE_BASE(NP, D)
+#define MBX_RLHPSDE_TAPE_Z(NP, D)        (MBX_RLHPSDE_TAPE_BASE(NP, D) + (int64_t)(NP))
+#define MBX_RLHPSDE_TAPE_X(NP, D)        (MBX_RLHPSDE_TAPE_BASE(NP, D) + 2 * (int64_t)(NP))
+#define MBX_RLHPSDE_TAPE_R(NP, D)        (MBX_RLHPSDE_TAPE_BASE(NP, D) + 3 * (int64_t)(NP))
+#define MBX_RLHPSDE_TAPE_JRAND(NP, D)    (MBX_RLHPSDE_TAPE_BASE(NP, D) + 6 * (int64_t)(NP))
+#define MBX_RLHPSDE_TAPE_NOISE(NP, D)    (MBX_RLHPSDE_TAPE_BASE(NP, D) + 7 * (int64_t)(NP))
+#define MBX_RLHPSDE_TAPE_CROSS(NP, D)    (MBX_RLHPSDE_TAPE_BASE(NP, D) + 10 * (int64_t)(NP))
+#define MBX_RLHPSDE_TAPE_STRIDE(NP, D)   (MBX_RLHPSDE_TAPE_BASE(NP, D) + 10 * (int64_t)(NP) + (int64_t)(NP) * (D))
+#define MBX_RLHPSDE_ST_POP(NP, D)        ((int64_t)0)
+#define MBX_RLHPSDE_ST_COST(NP, D)       (2 * (int64_t)(NP) * (D))
+#define MBX_RLHPSDE_ST_MF(NP, D)         (MBX_RLHPSDE_ST_COST(NP, D) + (NP))
+#define MBX_RLHPSDE_ST_MCR(NP, D)        (MBX_RLHPSDE_ST_MF(NP, D) + MBX_RLHPSDE_MEM(D))
+#define MBX_RLHPSDE_ST_U(NP, D)          (MBX_RLHPSDE_ST_MCR(NP, D) + MBX_RLHPSDE_MEM(D))
+#define MBX_RLHPSDE_ST_NCOST(NP, D)      (MBX_RLHPSDE_ST_U(NP, D) + (int64_t)(NP) * (D))
+#define MBX_RLHPSDE_ST_F(NP, D)          (MBX_RLHPSDE_ST_NCOST(NP, D) + (NP))
+#define MBX_RLHPSDE_ST_CR(NP, D)         (MBX_RLHPSDE_ST_F(NP, D) + (NP))
+#define MBX_RLHPSDE_ST_R(NP, D)          (MBX_RLHPSDE_ST_CR(NP, D) + (NP))
+#define MBX_RLHPSDE_ST_Z(NP, D)          (MBX_RLHPSDE_ST_R(NP, D) + 3 * (int64_t)(NP))
+#define MBX_RLHPSDE_ST_X(NP, D)          (MBX_RLHPSDE_ST_Z(NP, D) + (NP))
+#define MBX_RLHPSDE_ST_WALK(NP, D)       (MBX_RLHPSDE_ST_X(NP, D) + (NP))
+#define MBX_RLHPSDE_ST_WCOST(NP, D)      (MBX_RLHPSDE_ST_WALK(NP, D) + MBX_RLHPSDE_WALK * (int64_t)(D))
+#define MBX_RLHPSDE_ST_FEAT(NP, D)       (MBX_RLHPSDE_ST_WCOST(NP, D) + MBX_RLHPSDE_WALK)
+#define MBX_RLHPSDE_ST_SCALARS(NP, D)    (MBX_RLHPSDE_ST_FEAT(NP, D) + MBX_RLHPSDE_FEAT_SLOTS)
+#define MBX_RLHPSDE_STATE_DOUBLES(NP, D, NLOG) (MBX_RLHPSDE_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)
+#define MBX_SC_HP_NP       10
+#define MBX_SC_HP_K        11
+#define MBX_SC_HP_LIVE     12
+#define MBX_SC_HP_STATE    13
+#define MBX_SC_HP_ACTION   14
+#define MBX_SITE_HP_PAR      66u
+#define MBX_SITE_HP_NORM     67u
+#define MBX_SITE_HP_CAUCHY   68u
+#define MBX_SITE_HP_IDX      69u
+#define MBX_SITE_HP_CROSS    70u
+#define MBX_SITE_HP_NOISE_A  71u
+#define MBX_SITE_HP_NOISE_B  72u
+#define MBX_SITE_HP_WALK     73u
+#define MBX_SITE_HP_WNOISE_A 74u
+#define MBX_SITE_HP_WNOISE_B 75u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

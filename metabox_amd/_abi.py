@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/mbx.h and include/mbx_les.h (libmbx.so).
+"""ctypes binding of the C-ABI in include/mbx.h, include/mbx_les.h and include/mbx_rlhpsde.h (libmbx.so).
 
 This is the stub a maintainer of the reference would add to reach the HIP path (INTEGRATION.md shows it
 in isolation).  The library is built in-tree by ``__graft_entry__.build()`` / ``make -C metabox_amd/csrc``;
@@ -71,6 +71,7 @@ ALGO_DEDQN = 16
 ALGO_NRLPSO = 19
 ALGO_SAHLPSO = 20
 ALGO_LES = 21
+ALGO_RLHPSDE = 24    # (22 and 23 are not assigned)
 POLICY_RLEPSO, POLICY_RLPSO = 0, 1
 _ARRAY_FIELDS = ('dshift', 'm1', 'm2', 'v0', 'v1', 'v2', 'py', 'pc', 'pw')
 
@@ -114,7 +115,7 @@ class MbxError(RuntimeError):
 
 
 def load_lib():
-    """Load libmbx.so and declare the prototypes of every symbol in include/mbx.h and include/mbx_les.h."""
+    """Load libmbx.so and declare the prototypes of every symbol in include/mbx.h, include/mbx_les.h and include/mbx_rlhpsde.h."""
     global _lib
     if _lib is not None:
         return _lib
@@ -163,6 +164,7 @@ def load_lib():
         'mbx_nrlpso_rollout': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
         'mbx_les_set_params': (C.c_int, [vp, vp, C.c_int, vp]),
         'mbx_les_rollout': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        'mbx_rlhpsde_rollout': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
         'mbx_gleet_policy': (C.c_int, [vp, C.POINTER(GleetActor), vp, vp, vp, vp]),
         'mbx_debug_math': (C.c_int, [C.c_int, vp, vp, vp, C.c_int, vp]),
         'mbx_debug_rlepso_draws': (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
@@ -196,6 +198,9 @@ EXPORTED_SYMBOLS = ('mbx_suite_create', 'mbx_suite_destroy', 'mbx_suite_size', '
 
 # the entry points of include/mbx_les.h (LES), beside the 44 of include/mbx.h
 LES_SYMBOLS = ('mbx_les_set_params', 'mbx_les_rollout')
+
+# the entry point of include/mbx_rlhpsde.h (RL-HPSDE)
+RLHPSDE_SYMBOLS = ('mbx_rlhpsde_rollout',)
 
 
 def check(rc):

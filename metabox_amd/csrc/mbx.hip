@@ -1,5 +1,5 @@
 // mbx.hip — libmbx.so: kernels' launch code and the C-ABI of include/mbx.h.
-// Build: make -C metabox_amd/csrc  (ten translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
+// Build: make -C metabox_amd/csrc  (eleven translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip, mbx_run_rlhpsde.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -46,6 +46,7 @@
 #include "mbx_run_dedqn.hip"           // the DEDQN kernels and their launch code, in this file as well
 #include "mbx_run_nrlpso.hip"          // ... and the NRLPSO ones
 #include "mbx_run_les.hip"
+#include "mbx_run_rlhpsde.hip"
 #endif
 
 using namespace mbx;
@@ -932,6 +933,34 @@ static int les_prepare_batch(mbx_batch* b, const AlgoGeom& g)
 MBX_RESET_FN(les_reset) { les_launch_reset(make_params(b), stream, d_state_out); }
 MBX_STEP_FN(les_step) { (void)d_actions; return mbx_les_rollout(b, 1, 0, MBX_OUT, stream); }   // one generation of the budget route
 
+// ---- RL-HPSDE: mbx_run_rlhpsde.hip
+static int rlhpsde_check(const mbx_algo_cfg& c)
+{
+    // 18 dim rows shrinking towards 4, a thread owns a block of rows; the initial evaluation and the first walk (201 points) are spent by mbx_reset
+    if (c.dim < 2 || c.dim > MBX_RLHPSDE_DIM_MAX) return fail(MBX_E_ARG, "RL-HPSDE runs dim in [2, %d], not %d", MBX_RLHPSDE_DIM_MAX, c.dim);
+    if (c.np != MBX_RLHPSDE_NP(c.dim)) return fail(MBX_E_ARG, "RL-HPSDE runs np = 18 dim = %d, not %d", MBX_RLHPSDE_NP(c.dim), c.np);
+    if (c.max_fes <= c.np + MBX_RLHPSDE_WALK)
+        return fail(MBX_E_ARG, "RL-HPSDE needs max_fes > %d (the initial evaluation and the first walk), not %d", c.np + MBX_RLHPSDE_WALK, c.max_fes);
+    return MBX_OK;
+}
+
+static AlgoGeom rlhpsde_geom(const mbx_algo_cfg& c) { return MBX_GEOM(RLHPSDE, rlhpsde_lds_doubles(c.np, c.dim), 1, 1); }
+static int rlhpsde_prepare_batch(mbx_batch* b, const AlgoGeom& g)
+{
+    HIP_TRY(rlhpsde_prepare(lds_of(g)));
+    // DRIE's frequencies are n / 200 (and 1e-15 for an empty class): their logarithms, correctly rounded (extended precision, then one rounding to double), so that
+    // the kernel's entropies do not depend on the device's log (mbx_rlhpsde.hpp: hp_walk_state); the batch's table pointer `pci` carries them
+    std::vector<double> lt(MBX_RLHPSDE_WALK, 0.);
+    lt[0] = (double)std::log((long double)1e-15);
+    for (int n = 1; n < MBX_RLHPSDE_WALK - 1; ++n) lt[n] = (double)std::log((long double)((double)n / (double)(MBX_RLHPSDE_WALK - 1)));
+    HIP_TRY(hipMalloc(&b->d_pci, lt.size() * sizeof(double)));
+    HIP_TRY(hipMemcpy(b->d_pci, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
+    return MBX_OK;
+}
+
+MBX_RESET_FN(rlhpsde_reset) { rlhpsde_launch_reset(make_params(b), b->lds_bytes, stream, d_state_out); }
+MBX_STEP_FN(rlhpsde_step) { rlhpsde_launch_step(make_params(b), b->lds_bytes, stream, (const int32_t*)d_actions, MBX_OUT); return MBX_OK; }
+
 // ---- QLPSO
 static AlgoGeom qlpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(QLPSO, ql_lds_doubles(c.np, c.np, c.dim), 1, 1); }
 static int qlpso_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_qlpso_reset, k_qlpso_step<false>, k_qlpso_step<true>); }
@@ -994,6 +1023,7 @@ static const AlgoOps kAlgoOps[] = {
     {MBX_ALGO_NRLPSO, "NRLPSO", true, false, nrlpso_check, nrlpso_geom, nrlpso_prepare_batch, nrlpso_reset, nrlpso_step, nrlpso_launch_info},
     {MBX_ALGO_SAHLPSO, "SAHLPSO", false, false, sahlpso_check, sahlpso_geom, sahlpso_prepare_batch, sahlpso_reset, sahlpso_step, nullptr},
     {MBX_ALGO_LES, "LES", false, false, les_check, les_geom, les_prepare_batch, les_reset, les_step, nullptr},
+    {MBX_ALGO_RLHPSDE, "RL-HPSDE", true, false, rlhpsde_check, rlhpsde_geom, rlhpsde_prepare_batch, rlhpsde_reset, rlhpsde_step, nullptr},
 };
 
 static const AlgoOps* ops_of(int algo)      // null for the ids that are not assigned (0, 12, 14, 17) and anything out of range
@@ -1341,6 +1371,20 @@ extern "C" int mbx_nrlpso_rollout(mbx_batch* b, const double* d_q_table, int n_s
     if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_nrlpso_rollout: a replay tape holds one step");
     nrlpso_launch_steps(make_params(b), b->nrlpso_cached, (hipStream_t)stream, nullptr, d_q_table, n_steps, d_traj_actions, d_traj_state, d_traj_reward,
                         d_actions_out, d_state_out, d_reward_out, d_done_out);
+    HIP_TRY(hipGetLastError());
+    return MBX_OK;
+}
+
+extern "C" int mbx_rlhpsde_rollout(mbx_batch* b, const double* d_q_table, int n_steps, int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward,
+                                   int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
+{
+    if (!b) return fail(MBX_E_ARG, "mbx_rlhpsde_rollout: null batch");
+    if (b->cfg.algo != MBX_ALGO_RLHPSDE) return fail(MBX_E_UNSUPPORTED, "mbx_rlhpsde_rollout: the batch is not an RL-HPSDE batch");
+    if (!d_q_table) return fail(MBX_E_ARG, "mbx_rlhpsde_rollout: no Q-table (d_q_table is NULL)");
+    if (n_steps < 1) return fail(MBX_E_ARG, "mbx_rlhpsde_rollout: n_steps must be >= 1");
+    if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_rlhpsde_rollout: a replay tape holds one step");
+    rlhpsde_launch_run(make_params(b), b->lds_bytes, (hipStream_t)stream, d_q_table, n_steps, d_traj_actions, d_traj_state, d_traj_reward, d_actions_out,
+                       d_state_out, d_reward_out, d_done_out);
     HIP_TRY(hipGetLastError());
     return MBX_OK;
 }

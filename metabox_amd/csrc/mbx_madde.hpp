@@ -185,6 +185,8 @@ __host__ __device__ inline int md_np_at(int N0, double fes, double max_fes)
     return n < 1 ? 1 : n > N0 ? N0 : n;
 }
 
+// (mbx_rlhpsde.hpp uses the device pieces above in a translation unit of its own, which must not define MadDE's kernels a second time)
+#ifndef MBX_MADDE_PIECES_ONLY
 // ------------------------------------------------------------------------------------------------ reset (__init_population :179-195)
 __global__ __launch_bounds__(kThreads) void k_madde_reset(BatchParams bp, double* __restrict__ state_out)
 {
@@ -516,5 +518,7 @@ __global__ __launch_bounds__(kThreads) void k_madde_generation(BatchParams bp, d
         if (done_out) done_out[b] = done ? 1 : 0;
     }
 }
+
+#endif  // MBX_MADDE_PIECES_ONLY
 
 }  // namespace mbx

@@ -63,3 +63,14 @@ void les_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state
 void les_launch_run(const BatchParams& bp, hipStream_t stream, const float* d_params, const int32_t* d_set_of, int n_sets, const float* d_ts, int horizon,
                     int n_gens, int skip, int step0, int skip_total, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
 }  // namespace mbx
+// RL-HPSDE (mbx_rlhpsde.hpp): likewise in mbx_run_rlhpsde.hip
+namespace mbx {
+int64_t rlhpsde_lds_doubles(int np, int dim);
+hipError_t rlhpsde_prepare(size_t lds_bytes);
+void rlhpsde_launch_reset(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, double* d_state_out);
+void rlhpsde_launch_step(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, const int32_t* d_actions, double* d_state_out, double* d_reward_out,
+                         uint8_t* d_done_out);
+// the policy decides in the kernel: d_q_table is the 4 x 4 Q-table
+void rlhpsde_launch_run(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, const double* d_q_table, int n_steps, int32_t* d_traj_actions,
+                        double* d_traj_state, double* d_traj_reward, int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
+}  // namespace mbx

@@ -142,7 +142,7 @@ class Batch:
         """actions: CUDA tensor [B, action_dim] (float32).  Returns (state, reward, done) device tensors that are
         overwritten by the next call."""
         if self.action_dim > 0:
-            want = torch.int32 if self.cfg.algo in (_abi.ALGO_DEDDQN, _abi.ALGO_QLPSO, _abi.ALGO_DEDQN, _abi.ALGO_NRLPSO) else torch.float32
+            want = torch.int32 if self.cfg.algo in (_abi.ALGO_DEDDQN, _abi.ALGO_QLPSO, _abi.ALGO_DEDQN, _abi.ALGO_NRLPSO, _abi.ALGO_RLHPSDE) else torch.float32
             assert actions.is_cuda and actions.is_contiguous() and actions.dtype == want
             assert actions.numel() == self.B * self.action_dim
         else:
@@ -211,6 +211,25 @@ class Batch:
         t = traj or {}
         _abi.check(self.lib.mbx_nrlpso_rollout(self._h, _ptr(q_table), n_steps, _ptr(t.get('actions')), _ptr(t.get('state')), _ptr(t.get('reward')),
                                                _ptr(self._iactions), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
+        return (self.state, self.reward, self.done, self._iactions, traj) if trajectory else (self.state, self.reward, self.done, self._iactions)
+
+    def rlhpsde_rollout(self, q_table, n_steps, trajectory=False):
+        """`n_steps` RL-HPSDE updates of every instance in ONE launch, the tabular policy evaluated in the kernel (``mbx_rlhpsde_rollout``); bit-identical
+        to `n_steps` one-step calls and to step() fed the same actions.  q_table: [4, 4] float64 CUDA tensor.  Returns (state, reward summed over the
+        executed updates, done, last actions int32 [B]) and, with ``trajectory=True``, a dict of per-step records: actions [n_steps, B] int32 (-1 where
+        not written), state / reward [n_steps, B] float64 (zero after an instance's termination)."""
+        assert q_table.is_cuda and q_table.dtype == torch.float64 and q_table.is_contiguous() and tuple(q_table.shape) == (4, 4)
+        n_steps = int(n_steps)
+        if getattr(self, '_iactions', None) is None:
+            self._iactions = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        traj = None
+        if trajectory:
+            traj = {'actions': torch.full((n_steps, self.B), -1, dtype=torch.int32, device=self.device),
+                    'state': torch.zeros(n_steps, self.B, dtype=torch.float64, device=self.device),
+                    'reward': torch.zeros(n_steps, self.B, dtype=torch.float64, device=self.device)}
+        t = traj or {}
+        _abi.check(self.lib.mbx_rlhpsde_rollout(self._h, _ptr(q_table), n_steps, _ptr(t.get('actions')), _ptr(t.get('state')), _ptr(t.get('reward')),
+                                                _ptr(self._iactions), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
         return (self.state, self.reward, self.done, self._iactions, traj) if trajectory else (self.state, self.reward, self.done, self._iactions)
 
     def les_set_params(self, params, set_of_instance=None):

@@ -2657,8 +2657,219 @@ def gen_les():
         print(os.path.basename(path), os.path.getsize(path))
         assert os.path.getsize(path) <= 1000 * 1024, (path, os.path.getsize(path))
 
+# ------------------------------------------------------------------------------------------------ RL-HPSDE
+# rlhpsde_policy.npz : the Q-table of the shipped bbob_easy agent.
+# rlhpsde_traces*.npz: seeded reference episodes, recorded per update (run_rlhpsde_episode).  The numpy draws are NOT stored: the tests regenerate
+#                      them from the seed in the reference's call order.  Per case the seed, whether the shipped policy chose the actions (one
+#                      np.random.choice uniform per step) or the generator forced them, the actions, the recorded trial and walk costs of every
+#                      step, state / reward / fes / NP / k / MF / MCr / gbest / r / entropy per step, F and Cr for the cases that ask for them,
+#                      population snapshots at a few steps, the final curve and the stream position at the end.
+# The generator asserts the margins |r - 0.15| >= 1e-6 and |H - 0.5| >= 1e-6 at every recorded step, and that no vector handed to np.argsort holds
+# two equal values unless the rows are identical or the order it returns is the stable one; a candidate episode that breaks either is replaced by
+# another seed and counted (`replaced`).
+RLHPSDE_MARGIN = 1e-6
 
-SECTIONS = {'les': gen_les, 'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+
+class _HpReplace(Exception):
+    pass
+
+
+def run_rlhpsde_episode(problem, config, q_table, forced=None, fcr=False, max_steps=None):
+    """One reference RL-HPSDE episode on the global numpy stream (the caller seeds it).  Row 0 of every per-step array is the state after
+    init_population, row g the state after update number g.  forced: None = the agent's own choice rule with `q_table`, else the actions cycle
+    through this tuple and no choice uniform is drawn."""
+    from optimizer.rl_hpsde_optimizer import RL_HPSDE_Optimizer
+    import copy
+    opt = RL_HPSDE_Optimizer(copy.deepcopy(config))
+    problem.reset()
+    pop_of = lambda: getattr(opt, '_RL_HPSDE_Optimizer__population')          # noqa: E731
+    rec = dict(action=[], state=[], reward=[], fes=[], np=[], k=[], MF=[], MCr=[], gbest=[], r=[], H=[], done=[])
+    ncost, wcost, snaps, fcrs, seen = [], [], {}, [], {'evals': []}
+    orig_eval, orig_argsort = problem.eval, np.argsort
+
+    def ev(x):
+        y = orig_eval(x)
+        seen['evals'].append(np.array(y, dtype=np.float64) - (0. if problem.optimum is None else problem.optimum))
+        return y
+
+    def argsort(a, *args, **kw):
+        a = np.asarray(a)
+        res = orig_argsort(a, *args, **kw)
+        if len(np.unique(a)) < a.size:                               # equal costs: fine between identical rows, or where the order is the stable one
+            stable = orig_argsort(a, kind='stable')
+            group = pop_of().group
+            if a.size != len(group) or not np.array_equal(group[res], group[stable]):
+                raise _HpReplace('a sort of equal values of different rows in another order than the stable one')
+            seen['ties'] = seen.get('ties', 0) + 1
+        return res
+
+    def dfdc(sample, cost):
+        s, c = sample[1:], cost[1:]
+        dist = np.linalg.norm(s - pop_of().gbest_solution, ord=2, axis=-1)
+        seen['r'] = np.mean((c - c.mean()) * (dist - dist.mean())) / (c.std() * dist.std())
+        return orig_dfdc(sample, cost)
+
+    def drie(cost):
+        diff = cost[1:] - cost[:200]
+        e_star = np.max(np.abs(diff))
+        best = None
+        for scale in [0, 1 / 128, 1 / 64, 1 / 32, 1 / 16, 1 / 8, 1 / 4, 1 / 2, 1]:
+            sym = (diff < (-scale * e_star)) * (-1) + ((scale * e_star) < diff) * 1
+            a, b = sym[:-1], sym[1:]
+            prob = np.array([np.sum((a == x) & (b == y)) for x, y in ((-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0))], dtype=np.float64)
+            prob /= 200
+            prob[prob < 1e-15] = 1e-15
+            h = -np.sum(prob * np.log(prob) / np.log(6))
+            best = h if best is None else max(best, h)
+        seen['H'] = best
+        return orig_drie(cost)
+    orig_dfdc, orig_drie = getattr(opt, '_RL_HPSDE_Optimizer__DFDC'), getattr(opt, '_RL_HPSDE_Optimizer__DRIE')
+    setattr(opt, '_RL_HPSDE_Optimizer__DFDC', dfdc)
+    setattr(opt, '_RL_HPSDE_Optimizer__DRIE', drie)
+    problem.eval = ev
+    np.argsort = argsort
+
+    def snap(action, state, reward, done):
+        P = pop_of()
+        if abs(seen['r'] - 0.15) < RLHPSDE_MARGIN or abs(seen['H'] - 0.5) < RLHPSDE_MARGIN or not np.isfinite(seen['r']):
+            raise _HpReplace('a landscape margin')
+        rec['action'].append(action); rec['state'].append(int(state)); rec['reward'].append(float(reward)); rec['fes'].append(int(opt.fes))
+        rec['np'].append(int(P.NP)); rec['k'].append(int(P.k)); rec['MF'].append(np.array(P.MF, dtype=np.float64)); rec['MCr'].append(np.array(P.MCr, dtype=np.float64))
+        rec['gbest'].append(float(P.gbest)); rec['r'].append(float(seen['r'])); rec['H'].append(float(seen['H'])); rec['done'].append(int(done))
+        assert len(seen['evals']) == 2, len(seen['evals'])
+        ncost.append(seen['evals'][0]); wcost.append(seen['evals'][1])
+        seen['evals'] = []
+    try:
+        state = opt.init_population(problem)
+        snap(-1, state, 0., False)
+        snaps[0] = (np.array(pop_of().group), np.array(pop_of().cost))
+        done, g = False, 0
+        while not done and (max_steps is None or g < max_steps):
+            if forced is None:
+                e = np.exp(q_table[state])
+                action = int(np.random.choice(4, size=1, p=e / e.sum())[0])
+            else:
+                action = forced[g % len(forced)]
+            if fcr:
+                P = pop_of()
+                orig_choose = P.choose_F_Cr
+                P.choose_F_Cr = lambda d, o=orig_choose: (lambda cr_f: (fcrs.append(np.stack([cr_f[1].copy(), cr_f[0].copy()])), cr_f)[1])(o(d))
+            state, reward, done = opt.update(action, problem)
+            if fcr:
+                del P.choose_F_Cr
+            g += 1
+            snap(action, state, reward, done)
+            if g in (1, 2, 7, 30) or done:
+                snaps[g] = (np.array(pop_of().group), np.array(pop_of().cost))
+    finally:
+        problem.eval = orig_eval
+        np.argsort = orig_argsort
+    out = {k: np.array(v, dtype=np.float64 if k in ('reward', 'MF', 'MCr', 'gbest', 'r', 'H') else np.int32) for k, v in rec.items()}
+    out['ncost'] = np.concatenate(ncost)
+    out['wcost'] = np.stack(wcost)
+    out['snap_gens'] = np.array(sorted(snaps), dtype=np.int32)
+    for g in sorted(snaps):
+        out[f'snap{g}/pop'], out[f'snap{g}/cost'] = snaps[g]
+    out['cost'] = np.array(opt.cost, dtype=np.float64)
+    out['ties'] = np.int32(seen.get('ties', 0))
+    if fcr:
+        out['fcr'] = np.concatenate(fcrs, axis=1)
+    return out
+
+
+def gen_rlhpsde():
+    scratch = tempfile.mkdtemp()
+    agent = load_shipped(os.path.join(ref_import.REF_SRC, 'agent_model/test/bbob_easy/RL_HPSDE_Agent.pkl'))
+    q_table = np.array(agent._RL_HPSDE_Agent__q_table, dtype=np.float64)
+    np.savez_compressed(os.path.join(OUT, 'rlhpsde_policy.npz'), q_table=q_table)
+    data, cases, replaced = {}, [], 0
+
+    def config_for(suite, dim, max_fes):
+        argv = ['--problem', suite] + ([] if suite == 'protein' else ['--dim', str(dim)])
+        config = ref_import.ref_config(argv, scratch)
+        config.maxFEs = max_fes
+        config.log_interval = max_fes // config.n_logpoint
+        return config
+    # (suite, dim, function, first seed, max_fes, forced actions or None, record F / Cr, wanted state after the reset or None, step limit)
+    jobs = [('bbob', 10, 15, 0, 20000, None, False, None, None), ('bbob', 10, 5, 1, 20000, None, False, None, None),
+            ('bbob', 10, 22, 2, 6000, (0, 1, 2, 3), False, None, None), ('bbob', 10, 7, 4, 6000, (3, 2, 1, 0), False, None, None),
+            ('bbob', 10, 1, 5, 6000, None, False, None, None),
+            ('bbob-noisy', 10, 101, 6, 4000, None, False, None, None), ('bbob-noisy', 10, 102, 7, 4000, (2, 3, 0, 1), False, None, None),
+            ('bbob-noisy', 10, 103, 8, 4000, None, False, None, None),
+            ('bbob', 3, 12, 3, 3000, None, False, 0, None), ('bbob', 2, 8, 9, 3000, (0, 1, 2, 3), True, None, None),
+            ('protein', 12, '1ATN_7', 10, 1500, (1, 2, 3, 0), True, None, None)]
+    problems = {}
+    for suite, dim, fid, seed, max_fes, forced, fcr, want0, limit in jobs:
+        if suite == 'protein':
+            problem = protein_problems()[0][fid]
+        else:
+            if (suite, dim) not in problems:
+                tr, te, _ = all_problems(suite, dim)
+                problems[(suite, dim)] = {fid_of(p): p for p in tr + te}
+            problem = problems[(suite, dim)][fid]
+        config = config_for(suite, dim, max_fes)
+        for s in range(seed, seed + 400, 13):
+            np.random.seed(s)
+            try:
+                rec = run_rlhpsde_episode(problem, config, q_table, forced, fcr, limit)
+            except _HpReplace as e:
+                replaced += 1
+                print('replaced', suite, dim, fid, s, e)
+                continue
+            if want0 is None or rec['state'][0] == want0:
+                break
+        else:
+            raise AssertionError(('no seed', suite, dim, fid))
+        key = f'{suite}/{dim}/{fid}/{s}'
+        cases.append(key)
+        for k, v in rec.items():
+            data[f'{key}/{k}'] = v
+        data[f'{key}/max_fes'] = np.float64(max_fes)
+        data[f'{key}/policy'] = np.int32(forced is None)
+        data[f'{key}/next_rand'] = np.float64(np.random.rand())      # stream position after the episode
+        print(key, len(rec['fes']) - 1, rec['fes'][-1], rec['gbest'][-1], int(rec['np'][-1]), sorted(set(rec['state'].tolist())), len(rec['cost']))
+    data['cases'] = np.array(cases)
+    data['replaced'] = np.int32(replaced)
+    # final results of free-running episodes with the shipped Q-table, a fresh optimizer object each: [runs, (final cost, fes, steps, final NP)]
+    from optimizer.rl_hpsde_optimizer import RL_HPSDE_Optimizer
+    import copy
+    config = config_for('bbob', 10, 20000)
+    for fid in (8, 15, 21):
+        fin = []
+        for s in range(100, 132):
+            np.random.seed(s)
+            p = problems[('bbob', 10)][fid]
+            p.reset()
+            opt = RL_HPSDE_Optimizer(copy.deepcopy(config))
+            state, done, steps = opt.init_population(p), False, 0
+            while not done:
+                e = np.exp(q_table[state])
+                state, _, done = opt.update(int(np.random.choice(4, size=1, p=e / e.sum())[0]), p)
+                steps += 1
+            fin.append((opt.cost[-1], opt.fes, steps, getattr(opt, '_RL_HPSDE_Optimizer__population').NP))
+        data[f'finals/bbob/10/{fid}'] = np.array(fin, dtype=np.float64)
+        print('finals', fid, np.median(np.array(fin), 0))
+    parts, sizes, owner = [], [], {}
+    for key in data:
+        prefix = '/'.join(key.split('/')[:4])
+        if prefix not in owner:
+            need = sum(data[k].nbytes for k in data if '/'.join(k.split('/')[:4]) == prefix)
+            for n in range(len(parts) + 1):
+                if n == len(parts):
+                    parts.append({}); sizes.append(0)
+                if sizes[n] + need <= 600 * 1024:
+                    break
+            owner[prefix] = n
+            sizes[n] += need
+        parts[owner[prefix]][key] = data[key]
+    for n, d in enumerate(parts):
+        path = os.path.join(OUT, 'rlhpsde_traces%s.npz' % ('' if n == 0 else '_' + 'abcdefgh'[n]))
+        np.savez_compressed(path, **d)
+        print(os.path.basename(path), os.path.getsize(path))
+        assert os.path.getsize(path) <= 800 * 1024, (path, os.path.getsize(path))
+
+
+SECTIONS = {'rlhpsde': gen_rlhpsde, 'les': gen_les, 'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso|les] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso|les|rlhpsde] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -280,6 +280,42 @@ if 'nrlpso' in which:
             print(json.dumps({'path': f'{k}, bbob d={dim}, {B} instances', 'us_per_step_median': float(np.median(v)), 'windows': [round(x, 1) for x in v],
                               'launch_info': (bc if 'cached' in k else br if 'recompute' in k else bq).launch_info()}))
         for b in (bq, bc, br): b.close()
+if 'rlhpsde' in which:
+    # RL-HPSDE (one update = NP trials, NP = 18 D shrinking towards 4, the memory update, the sort, and the 201-point landscape walk with its evaluations)
+    # next to Random_search's 100-row kernel in the same process: bbob round-robin, 4096 instances at D = 10, the reference's budget of 20 000 without the
+    # early stop, so that every instance runs the 70 updates of the integer schedule.  k_rlhpsde_run: 10 updates per launch with the shipped Q-table in the
+    # kernel, the seven launches of an episode timed one by one (the population shrinks, so the first windows are the dear ones); k_rlhpsde_step: one launch per
+    # update with the action from the host side, over the first 10 updates.  Wall times, launch gaps included; each window ends with a device synchronise.
+    from metabox_amd._abi import ALGO_RANDOM_SEARCH, ALGO_RLHPSDE
+    from metabox_amd.suite import Batch, Suite
+    q = torch.from_numpy(np.load(os.path.join(os.path.dirname(__file__), '..', 'tests', 'golden', 'rlhpsde_policy.npz'))['q_table']).cuda()
+    dim, B = 10, 4096
+    cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+    tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+    s = Suite(ps)
+    b = Batch(s, ALGO_RANDOM_SEARCH, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, 100, 10 ** 9, 10 ** 7, 50, early_stop=False)
+    b.reset()
+    def run(n):
+        for _ in range(n): b.step(None)
+    run(3); dt = timed(run, 30)
+    print(json.dumps({'path': f'k_rs_population bbob d={dim} NP=100, {B} instances', 'us_per_step': dt / 30 * 1e6, 'ns_per_row': dt / 30 / (100 * B) * 1e9}))
+    b.close()
+    b = Batch(s, ALGO_RLHPSDE, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, 18 * dim, 20000, 400, 50, early_stop=False)
+    episodes = []
+    for rep in range(3):
+        b.reset()
+        episodes.append([timed(lambda n: b.rlhpsde_rollout(q, 10), 1) / 10 * 1e3 for _ in range(7)])
+    assert bool(b.done.all())
+    med = np.median(np.array(episodes), 0)
+    print(json.dumps({'path': f'k_rlhpsde_run bbob d={dim} NP=180 -> 3, {B} instances, 10 updates per launch, Q-table in the kernel', 'ms_per_step_by_window': [round(float(x), 3) for x in med],
+                      'ms_per_step_episode_mean': float(med.mean()), 'ms_per_episode': float(med.sum() * 10), 'launch_info': b.launch_info()}))
+    b.reset()
+    acts = torch.full((B,), 1, dtype=torch.int32, device='cuda')
+    def run_step(n):
+        for _ in range(n): b.step(acts)
+    dt = timed(run_step, 10)
+    print(json.dumps({'path': f'k_rlhpsde_step bbob d={dim}, {B} instances, one launch per update, the first 10 updates', 'ms_per_step': dt / 10 * 1e3}))
+    b.close()
 if 'sdmspso' in which:
     # sDMS_PSO (one mbx_step = one update: 99 evaluated rows) next to GL-PSO (one generation: 200 evaluated rows and the exemplar breeding) in the
     # same process, alternating: bbob round-robin, 4096 instances, every instance live for the whole window (sDMS_PSO has no early stop; its
