@@ -963,6 +963,82 @@
 #define MBX_SITE_HP_WNOISE_A 74u
 #define MBX_SITE_HP_WNOISE_B 75u
 
+/* ---------------------------------------------------------------- 20. NL_SHADE_LBC (nl_shade_lbc.py) layouts
+ * SHADE-style DE, a classic baseline without an agent: success-history memory MF / MCr of H = 20 D entries, an archive of up to N0 rows, a population that
+ * shrinks non-linearly from N0 = 23 D rows to 4, rank-weighted r2, a binomial and an exponential crossover computed side by side.  mbx_reset is
+ * __init_population (:149-160), mbx_step (actions = NULL) one __update (:163-273), mbx_nlshade_run (include/mbx_nlshade.h) n updates in one launch.
+ * cfg.np must be 23 dim, 2 <= dim <= 40, max_fes > np.  state [1] = fes / max_fes, no action.  Rules and the quirks kept: the header of mbx_nlshade.hpp.
+ * The population schedule is a per-batch table built by the host at mbx_batch_create (bp.pci: count G, then N after update 0 .. G, long double power).
+ * state block: pop[2][N0*D] (two buffers, MBX_SC_NL_LIVE names the live one; rows sorted by (cost, row)) cost[N0] arc[N0*D] MF[H] MCr[H] u[N0*D] (trial
+ *   rows) ncost[N0] F[N0] Cr[N0] (SORTED ascending, Cr[i] is row i's) idx[4*N0] (pbs, r1, r2, archive index of the last mutation, idx[4 i + c]; -1 where
+ *   the row did not use it) z[N0] c[N0] u2[N0] (the standard normal behind Cr, the Cauchy variate behind F and the uniform behind r2 of the last update,
+ *   so that a Philox run can be fed back as a tape) carry[2] (pb, NA: what __init_population does not reset; carry[0] == 0 marks a new batch, which
+ *   starts at pb = 0.4, NA = N0) scalars[16] cost_curve[n_logpoint + 1].
+ * tape:  reset: pos_u[N0*D] | noise[3*N0]
+ *        step:  mem[N0] | z[N0] | c[N0] | pbs[N0] | r1[N0] | u2[N0] | rvs[N0] | aidx[N0] | jrand[N0] | L[N0] | pick[N0] | noise[3*N0] | arcw[N0] |
+ *               crossb_u[N0*D] | crosse_u[N0*D]          (rows past the live NP are not read)
+ *          pbs, r1, aidx: the RESOLVED indices (after the bounded redraws); u2: the uniform of the KEPT np.random.choice draw, the kernel builds the
+ *          cdf and searches it; pick: rand(NP), > 0.5 takes the exponential crossover; arcw[k]: the archive row the improved row of rank k overwrites.
+ * A tape holds one update: with a tape n_updates must be 1.
+ * Philox, counter (index, site, gen, episode); reset gen = 0, update gen = number of the update:
+ *   MBX_SITE_NL_PAR(i)        mulhi(w0, H) = mem, mulhi(w1, D) = jrand, mulhi(w2, D) = L, w3 / 2^32 = pick
+ *   MBX_SITE_NL_NORM(i)       box_muller(u53(w0,w1), u53(w2,w3)): the cosine half = z
+ *   MBX_SITE_NL_CAUCHY(i)     tan(pi (u53(w0,w1) - 0.5)) = c, u53(w2,w3) = rvs
+ *   MBX_SITE_NL_IDX(i*32+a)   attempt a of the bounded redraws, each index with its own attempt counter: pbs = mulhi(w0, pb_upper) at a = 0 and
+ *                             mulhi(w0, NP) at a = 1 (one redraw); r1 = mulhi(w1, NP), a = 0..25; u2 = u53(w2,w3), a = 0..25
+ *   MBX_SITE_NL_ARC(i)        mulhi(w0, rows) = arcw[i], mulhi(w1, rows) = aidx of row i
+ *   MBX_SITE_NL_CROSS(i*D+d)  u53(w0,w1) = crossb_u, u53(w2,w3) = crosse_u;  reset: index e, u53(w0,w1) = pos_u
+ *   MBX_SITE_NL_NOISE_A/B(i)  evaluation of trial row i;  reset: MBX_SITE_NOISE1_A/B(i)                                                        */
+#define MBX_NLSHADE_NP(D)                (23 * (D))
+#define MBX_NLSHADE_DIM_MAX              40
+#define MBX_NLSHADE_H(D)                 (20 * (int64_t)(D))
+#define MBX_NLSHADE_TAPE_POS(NP, D)      ((int64_t)0)
+#define MBX_NLSHADE_TAPE_NOISE_INIT(NP, D) ((int64_t)(NP) * (D))
+#define MBX_NLSHADE_TAPE_MEM(NP, D)      ((int64_t)0)
+#define MBX_NLSHADE_TAPE_Z(NP, D)        ((int64_t)(NP))
+#define MBX_NLSHADE_TAPE_C(NP, D)        (2 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_PBS(NP, D)      (3 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_R1(NP, D)       (4 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_U2(NP, D)       (5 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_RVS(NP, D)      (6 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_AIDX(NP, D)     (7 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_JRAND(NP, D)    (8 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_L(NP, D)        (9 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_PICK(NP, D)     (10 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_NOISE(NP, D)    (11 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_ARCW(NP, D)     (14 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_CROSSB(NP, D)   (15 * (int64_t)(NP))
+#define MBX_NLSHADE_TAPE_CROSSE(NP, D)   (15 * (int64_t)(NP) + (int64_t)(NP) * (D))
+#define MBX_NLSHADE_TAPE_STRIDE(NP, D)   (15 * (int64_t)(NP) + 2 * (int64_t)(NP) * (D))
+#define MBX_NLSHADE_ST_POP(NP, D)        ((int64_t)0)
+#define MBX_NLSHADE_ST_COST(NP, D)       (2 * (int64_t)(NP) * (D))
+#define MBX_NLSHADE_ST_ARC(NP, D)        (MBX_NLSHADE_ST_COST(NP, D) + (NP))
+#define MBX_NLSHADE_ST_MF(NP, D)         (MBX_NLSHADE_ST_ARC(NP, D) + (int64_t)(NP) * (D))
+#define MBX_NLSHADE_ST_MCR(NP, D)        (MBX_NLSHADE_ST_MF(NP, D) + MBX_NLSHADE_H(D))
+#define MBX_NLSHADE_ST_U(NP, D)          (MBX_NLSHADE_ST_MCR(NP, D) + MBX_NLSHADE_H(D))
+#define MBX_NLSHADE_ST_NCOST(NP, D)      (MBX_NLSHADE_ST_U(NP, D) + (int64_t)(NP) * (D))
+#define MBX_NLSHADE_ST_F(NP, D)          (MBX_NLSHADE_ST_NCOST(NP, D) + (NP))
+#define MBX_NLSHADE_ST_CR(NP, D)         (MBX_NLSHADE_ST_F(NP, D) + (NP))
+#define MBX_NLSHADE_ST_IDX(NP, D)        (MBX_NLSHADE_ST_CR(NP, D) + (NP))
+#define MBX_NLSHADE_ST_Z(NP, D)          (MBX_NLSHADE_ST_IDX(NP, D) + 4 * (int64_t)(NP))
+#define MBX_NLSHADE_ST_C(NP, D)          (MBX_NLSHADE_ST_Z(NP, D) + (NP))
+#define MBX_NLSHADE_ST_U2(NP, D)         (MBX_NLSHADE_ST_C(NP, D) + (NP))
+#define MBX_NLSHADE_ST_CARRY(NP, D)      (MBX_NLSHADE_ST_U2(NP, D) + (NP))
+#define MBX_NLSHADE_ST_SCALARS(NP, D)    (MBX_NLSHADE_ST_CARRY(NP, D) + 2)
+#define MBX_NLSHADE_STATE_DOUBLES(NP, D, NLOG) (MBX_NLSHADE_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)
+#define MBX_SC_NL_NP       10
+#define MBX_SC_NL_ARC      11
+#define MBX_SC_NL_K        12
+#define MBX_SC_NL_LIVE     13
+#define MBX_SITE_NL_PAR      76u
+#define MBX_SITE_NL_NORM     77u
+#define MBX_SITE_NL_CAUCHY   78u
+#define MBX_SITE_NL_IDX      79u
+#define MBX_SITE_NL_ARC      80u
+#define MBX_SITE_NL_CROSS    81u
+#define MBX_SITE_NL_NOISE_A  82u
+#define MBX_SITE_NL_NOISE_B  83u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

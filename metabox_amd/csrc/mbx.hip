@@ -1,5 +1,5 @@
 // mbx.hip — libmbx.so: kernels' launch code and the C-ABI of include/mbx.h.
-// Build: make -C metabox_amd/csrc  (eleven translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip, mbx_run_rlhpsde.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
+// Build: make -C metabox_amd/csrc  (twelve translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip, mbx_run_rlhpsde.hip, mbx_run_nlshade.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -47,6 +47,7 @@
 #include "mbx_run_nrlpso.hip"          // ... and the NRLPSO ones
 #include "mbx_run_les.hip"
 #include "mbx_run_rlhpsde.hip"
+#include "mbx_run_nlshade.hip"
 #endif
 
 using namespace mbx;
@@ -961,6 +962,28 @@ static int rlhpsde_prepare_batch(mbx_batch* b, const AlgoGeom& g)
 MBX_RESET_FN(rlhpsde_reset) { rlhpsde_launch_reset(make_params(b), b->lds_bytes, stream, d_state_out); }
 MBX_STEP_FN(rlhpsde_step) { rlhpsde_launch_step(make_params(b), b->lds_bytes, stream, (const int32_t*)d_actions, MBX_OUT); return MBX_OK; }
 
+// ---- NL_SHADE_LBC: mbx_run_nlshade.hip
+static int nlshade_check(const mbx_algo_cfg& c)
+{
+    if (c.dim < 2 || c.dim > MBX_NLSHADE_DIM_MAX) return fail(MBX_E_ARG, "NL_SHADE_LBC runs dim in [2, %d], not %d", MBX_NLSHADE_DIM_MAX, c.dim);
+    if (c.np != MBX_NLSHADE_NP(c.dim)) return fail(MBX_E_ARG, "NL_SHADE_LBC runs np = 23 dim = %d, not %d", MBX_NLSHADE_NP(c.dim), c.np);
+    if (c.max_fes <= c.np) return fail(MBX_E_ARG, "NL_SHADE_LBC needs max_fes > %d (the initial evaluation), not %d", c.np, c.max_fes);
+    return MBX_OK;
+}
+
+static AlgoGeom nlshade_geom(const mbx_algo_cfg& c) { return MBX_GEOM(NLSHADE, nlshade_lds_doubles(c.np, c.dim), 1, 0); }
+static int nlshade_prepare_batch(mbx_batch* b, const AlgoGeom& g)
+{
+    HIP_TRY(nlshade_prepare(lds_of(g)));
+    // the population schedule is a function of (dim, max_fes) alone (mbx_nlshade.hpp, quirk 11); the batch's table pointer `pci` carries it
+    const std::vector<double> t = nlshade_schedule(b->cfg.np, b->cfg.max_fes);
+    HIP_TRY(hipMalloc(&b->d_pci, t.size() * sizeof(double)));
+    HIP_TRY(hipMemcpy(b->d_pci, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+    return MBX_OK;
+}
+MBX_RESET_FN(nlshade_reset) { nlshade_launch_reset(make_params(b), b->lds_bytes, stream, d_state_out); }
+MBX_STEP_FN(nlshade_step) { nlshade_launch_step(make_params(b), b->lds_bytes, stream, MBX_OUT); return MBX_OK; }
+
 // ---- QLPSO
 static AlgoGeom qlpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(QLPSO, ql_lds_doubles(c.np, c.np, c.dim), 1, 1); }
 static int qlpso_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_qlpso_reset, k_qlpso_step<false>, k_qlpso_step<true>); }
@@ -1024,6 +1047,7 @@ static const AlgoOps kAlgoOps[] = {
     {MBX_ALGO_SAHLPSO, "SAHLPSO", false, false, sahlpso_check, sahlpso_geom, sahlpso_prepare_batch, sahlpso_reset, sahlpso_step, nullptr},
     {MBX_ALGO_LES, "LES", false, false, les_check, les_geom, les_prepare_batch, les_reset, les_step, nullptr},
     {MBX_ALGO_RLHPSDE, "RL-HPSDE", true, false, rlhpsde_check, rlhpsde_geom, rlhpsde_prepare_batch, rlhpsde_reset, rlhpsde_step, nullptr},
+    {MBX_ALGO_NLSHADE, "NL_SHADE_LBC", false, false, nlshade_check, nlshade_geom, nlshade_prepare_batch, nlshade_reset, nlshade_step, nullptr},
 };
 
 static const AlgoOps* ops_of(int algo)      // null for the ids that are not assigned (0, 12, 14, 17) and anything out of range
@@ -1385,6 +1409,17 @@ extern "C" int mbx_rlhpsde_rollout(mbx_batch* b, const double* d_q_table, int n_
     if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_rlhpsde_rollout: a replay tape holds one step");
     rlhpsde_launch_run(make_params(b), b->lds_bytes, (hipStream_t)stream, d_q_table, n_steps, d_traj_actions, d_traj_state, d_traj_reward, d_actions_out,
                        d_state_out, d_reward_out, d_done_out);
+    HIP_TRY(hipGetLastError());
+    return MBX_OK;
+}
+
+extern "C" int mbx_nlshade_run(mbx_batch* b, int n_updates, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
+{
+    if (!b) return fail(MBX_E_ARG, "mbx_nlshade_run: null batch");
+    if (b->cfg.algo != MBX_ALGO_NLSHADE) return fail(MBX_E_UNSUPPORTED, "mbx_nlshade_run: the batch is not an NL_SHADE_LBC batch");
+    if (n_updates < 1) return fail(MBX_E_ARG, "mbx_nlshade_run: n_updates must be >= 1");
+    if (b->d_tape && n_updates != 1) return fail(MBX_E_ARG, "mbx_nlshade_run: a replay tape holds one update");
+    nlshade_launch_run(make_params(b), b->lds_bytes, (hipStream_t)stream, n_updates, d_state_out, d_reward_out, d_done_out);
     HIP_TRY(hipGetLastError());
     return MBX_OK;
 }

@@ -74,3 +74,14 @@ void rlhpsde_launch_step(const BatchParams& bp, size_t lds_bytes, hipStream_t st
 void rlhpsde_launch_run(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, const double* d_q_table, int n_steps, int32_t* d_traj_actions,
                         double* d_traj_state, double* d_traj_reward, int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
 }  // namespace mbx
+// NL_SHADE_LBC (mbx_nlshade.hpp): likewise in mbx_run_nlshade.hip
+#include <vector>
+namespace mbx {
+int64_t nlshade_lds_doubles(int np, int dim);
+std::vector<double> nlshade_schedule(int np, int max_fes);      // the batch's table bp.pci: the update count, then N after update 0 .. G
+hipError_t nlshade_prepare(size_t lds_bytes);
+void nlshade_launch_reset(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, double* d_state_out);
+void nlshade_launch_step(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
+void nlshade_launch_run(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, int n_updates, double* d_state_out, double* d_reward_out,
+                        uint8_t* d_done_out);
+}  // namespace mbx

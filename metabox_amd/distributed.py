@@ -66,6 +66,8 @@ COST_NS = {
 # documented rather than measured: a pass is a chain of single-row evaluations whose barrier latency is the same for every function, so the table overstates the spread here too.
 # RL-HPSDE falls back on the table as well, documented rather than measured: an update is NP trial evaluations plus the 201 evaluations of the landscape walk, so it is
 # evaluation-dominated like RLEPSO's generation and the ratios between functions carry over; with early_stop, Sphere and linear slope end early here too.
+# NL_SHADE_LBC falls back on the table too, documented rather than measured: an update is NP trial evaluations, but more than half of an episode is updates of 4 to 8 rows
+# whose fixed phases (two sorts, the scan, the sums) cost the same for every function, so the table overstates the spread between functions.
 EPISODE_COST_US = {
     10: {1: 2.06, 2: 5.49, 3: 6.599, 4: 6.06, 5: 0.882, 6: 4.785, 7: 4.8, 8: 4.582, 9: 4.534, 10: 5.31, 11: 5.267, 12: 5.705, 13: 5.18, 14: 5.018, 15: 6.403,
          16: 6.37, 17: 6.179, 18: 6.174, 19: 4.902, 20: 5.029, 21: 6.566, 22: 6.418, 23: 6.187, 24: 4.828, 101: 2.084, 102: 2.589, 103: 4.86, 104: 4.928, 105:

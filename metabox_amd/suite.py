@@ -232,6 +232,12 @@ class Batch:
                                                 _ptr(self._iactions), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
         return (self.state, self.reward, self.done, self._iactions, traj) if trajectory else (self.state, self.reward, self.done, self._iactions)
 
+    def nlshade_run(self, n_updates):
+        """`n_updates` NL_SHADE_LBC updates of every instance in ONE launch (``mbx_nlshade_run``); bit-identical to `n_updates` calls of step(None).
+        Returns (state = fes / max_fes, reward = 0, done)."""
+        _abi.check(self.lib.mbx_nlshade_run(self._h, int(n_updates), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
+        return self.state, self.reward, self.done
+
     def les_set_params(self, params, set_of_instance=None):
         """LES: the parameter sets of the batch and the set of every instance (``mbx_les_set_params``).  params: [n_sets, 246] (or [246]) in the
         reference's ``vector2nn`` order, attention first; float64 input is cast to float32 here, as the reference's ``torch.FloatTensor`` does.

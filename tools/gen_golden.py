@@ -2869,7 +2869,255 @@ def gen_rlhpsde():
         assert os.path.getsize(path) <= 800 * 1024, (path, os.path.getsize(path))
 
 
-SECTIONS = {'rlhpsde': gen_rlhpsde, 'les': gen_les, 'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+# ------------------------------------------------------------------------------------------------ NL_SHADE_LBC
+NL_MARGIN = 1e-9
+
+
+class _NlReplace(Exception):
+    pass
+
+
+def nl_lehmer(df, s, pg, dtype=np.float64):
+    """sum(w s^pg) / sum(w s^(pg - 1.5)), w = df / sum(df), in `dtype` (np.longdouble: the yardstick E_ref is measured against)."""
+    df, s, pg = df.astype(dtype), s.astype(dtype), dtype(pg)
+    with np.errstate(all='ignore'):
+        w = df / np.sum(df)
+        return np.sum(w * (s ** pg)) / np.sum(w * (s ** (pg - dtype(1.5))))
+
+
+def run_nlshade_episode(problem, config, opt=None, mf0=None, max_updates=None):
+    """One reference NL_SHADE_LBC episode on the global numpy stream (the caller seeds it).  Row 0 of every per-update array is the state after
+    __init_population, row g the state after __update number g.  `ncost` is ragged and stored flattened: the costs of the initial rows in draw
+    order, then the NP trial costs of every update (one double per FE).  `carry0` is (pb, NA) the episode started with (they live on the
+    object).  `tie`: an argsort whose order differs from the stable one.  `margin`: the smallest distance of a np.random.choice uniform from
+    its two neighbouring cdf entries.  `eref`: the largest relative distance of the float64 MF[k] / MCr[k] from their np.longdouble evaluation.
+    Snapshots (population, costs, archive, MF, MCr) after the reset, at a few updates where population + archive are small, and at the end.
+    mf0: the memory MF the generator puts on the object after __init_population (recorded as `mf0`), max_updates: stop after that many updates
+    (`cost` is then the curve so far, without run_episode's final entry): a reference update from a state no reference episode reaches."""
+    from optimizer import NL_SHADE_LBC
+    import copy
+    SNAP_DOUBLES = 3000
+    opt = opt if opt is not None else NL_SHADE_LBC(copy.deepcopy(config))
+    problem.reset()
+    get = lambda name: getattr(opt, '_NL_SHADE_LBC__' + name)          # noqa: E731
+    rec = dict(gbest=[], fes=[], np=[], narc=[], na=[], k=[], pb=[], mem=[], n_opt=[], n_over=[], cmin=[], csum=[], tie=[])
+    ncost, snaps, seen = [], {}, {'tie': 0, 'margin': 1.0, 'eref': 0.0}
+    carry0 = np.array([get('pb'), get('NA')], dtype=np.float64)
+    orig_eval, orig_arc, orig_mem, orig_argsort, orig_choice = problem.eval, get('update_archive'), get('update_M_F_Cr'), np.argsort, np.random.choice
+
+    def ev(x):
+        y = orig_eval(x)
+        seen['eval'] = np.array(y, dtype=np.float64) - (0. if problem.optimum is None else problem.optimum)
+        return y
+
+    def upd(i):
+        seen['n_opt'] += 1
+        seen['n_over'] += int(get('archive').shape[0] >= get('NA'))
+        return orig_arc(i)
+
+    def mem(SF, SCr, df):
+        if SF.shape[0] > 0 and np.sum(df) > 0.:
+            mf = config.maxFEs
+            for s, p_ini in ((SF, 3.5), (SCr, 1.0)):
+                pg = (mf - get('FEs')) * (p_ini - 1.5) / mf + 1.5
+                a, b = nl_lehmer(df, s, pg), nl_lehmer(df, s, pg, np.longdouble)
+                if np.isfinite(a) and np.isfinite(b) and b != 0:
+                    seen['eref'] = max(seen['eref'], float(abs(np.longdouble(a) - b) / abs(b)))
+        return orig_mem(SF, SCr, df)
+
+    def argsort(a, *args, **kw):
+        a = np.asarray(a)
+        r = orig_argsort(a, *args, **kw)
+        if not np.array_equal(r, orig_argsort(a, kind='stable')):
+            seen['tie'] = 1
+        return r
+
+    def choice(a, size=None, replace=True, p=None):
+        state = np.random.get_state()
+        want = orig_choice(a, size=size, replace=replace, p=p)
+        np.random.set_state(state)
+        cdf = np.asarray(p).cumsum()
+        cdf /= cdf[-1]
+        u = np.random.random_sample(size)
+        idx = cdf.searchsorted(u, side='right')
+        assert np.array_equal(idx, want)
+        if u.size:
+            lo = np.where(idx > 0, cdf[np.maximum(idx - 1, 0)], -1.0)
+            seen['margin'] = min(seen['margin'], float(np.min(np.minimum(u - lo, cdf[np.minimum(idx, len(cdf) - 1)] - u))))
+        return want
+    problem.eval = ev
+    setattr(opt, '_NL_SHADE_LBC__update_archive', upd)
+    setattr(opt, '_NL_SHADE_LBC__update_M_F_Cr', mem)
+    np.argsort, np.random.choice = argsort, choice
+
+    def state():
+        arc = np.array(get('archive'), dtype=np.float64).reshape(-1, config.dim)
+        return (np.array(get('population'), dtype=np.float64), np.array(get('cost'), dtype=np.float64), arc,
+                np.array(get('MF'), dtype=np.float64), np.array(get('MCr'), dtype=np.float64))
+
+    def snap(k_before):
+        cost = np.array(get('cost'), dtype=np.float64)
+        rec['gbest'].append(float(opt.gbest)); rec['fes'].append(float(get('FEs'))); rec['np'].append(int(get('NP')))
+        rec['narc'].append(int(np.array(get('archive')).reshape(-1, config.dim).shape[0])); rec['na'].append(int(get('NA'))); rec['k'].append(int(get('k')))
+        rec['pb'].append(float(get('pb')))
+        rec['mem'].append(np.array([get('MF')[k_before], get('MCr')[k_before]], dtype=np.float64))
+        rec['n_opt'].append(seen.get('n_opt', 0)); rec['n_over'].append(seen.get('n_over', 0))
+        rec['cmin'].append(float(cost.min())); rec['csum'].append(float(np.sum(cost))); rec['tie'].append(seen['tie'])
+        ncost.append(seen['eval'])
+    try:
+        with np.errstate(all='ignore'):
+            getattr(opt, '_NL_SHADE_LBC__init_population')(problem)
+            snap(0)
+            if mf0 is not None:
+                setattr(opt, '_NL_SHADE_LBC__MF', np.array(mf0, dtype=np.float64))
+            snaps[0] = state()
+            done = False
+            while not done and get('FEs') < config.maxFEs and (max_updates is None or len(rec['gbest']) - 1 < max_updates):
+                seen.update(tie=0, n_opt=0, n_over=0)
+                k_before = int(get('k'))
+                done = getattr(opt, '_NL_SHADE_LBC__update')(problem)
+                snap(k_before)
+                g = len(rec['gbest']) - 1
+                if g % 97 == 0 and (get('NP') + rec['narc'][-1]) * config.dim <= SNAP_DOUBLES and len(snaps) < 4:
+                    snaps[g] = state()
+    finally:
+        problem.eval = orig_eval
+        np.argsort, np.random.choice = orig_argsort, orig_choice
+        delattr(opt, '_NL_SHADE_LBC__update_archive'); delattr(opt, '_NL_SHADE_LBC__update_M_F_Cr')
+    # what run_episode does after its loop (:281-284)
+    if max_updates is None:
+        if len(opt.cost) >= config.n_logpoint + 1:
+            opt.cost[-1] = opt.gbest
+        else:
+            opt.cost.append(opt.gbest)
+    snaps[len(rec['gbest']) - 1] = state()
+    out = {k: np.array(v, dtype=np.float64 if k in ('gbest', 'fes', 'pb', 'mem', 'cmin', 'csum') else np.int32) for k, v in rec.items()}
+    out['ncost'] = np.concatenate(ncost)
+    out['carry0'] = carry0
+    if mf0 is not None:
+        out['mf0'] = np.array(mf0, dtype=np.float64)
+    out['snap_gens'] = np.array(sorted(snaps), dtype=np.int32)
+    for g in sorted(snaps):
+        for name, a in zip(('pop', 'cost', 'arc', 'MF', 'MCr'), snaps[g]):
+            out[f'snap{g}/{name}'] = a
+    out['cost'] = np.array(opt.cost, dtype=np.float64)
+    out['margin'] = np.float64(seen['margin'])
+    out['eref'] = np.float64(seen['eref'])
+    # the asserts every kept case must pass
+    if out['tie'].any():
+        raise _NlReplace('an argsort whose order is not the stable one')
+    if out['margin'] < NL_MARGIN:
+        raise _NlReplace('a choice uniform within 1e-9 of a cdf entry')
+    n0 = 23 * config.dim
+    x = out['fes'][1:].astype(np.longdouble) / np.longdouble(config.maxFEs)
+    raw = np.longdouble(n0) + np.longdouble(4 - n0) * np.power(x, 1 - x)
+    if np.any(np.abs(np.abs(raw - np.floor(raw)) - 0.5) < NL_MARGIN):
+        raise _NlReplace('N within 1e-9 of a half-integer')
+    return out, opt
+
+
+def gen_nlshade():
+    """NL_SHADE_LBC (src/optimizer/nl_shade_lbc.py): seeded reference episodes, recorded per update (run_nlshade_episode).  The numpy draws are NOT
+    stored: the tests regenerate them from the seed in the reference's draw order.  Every kept case passes the three asserts of
+    run_nlshade_episode (sort order, choice margin, half-integer margin); a case that misses one is replaced by the next seed.
+    `finals/bbob/10/<fid>`: final gbest and fes of 32 episodes (seeds 100..131, full budget), each on a fresh optimizer object.  `eref`: the
+    maximum over all cases of the float64 memory update's relative distance from its np.longdouble evaluation (E_ref of DESIGN.md §2)."""
+    scratch = tempfile.mkdtemp()
+    data, cases, owner = {}, [], {}
+
+    def config_for(suite, dim, max_fes):
+        argv = ['--problem', suite] + ([] if suite == 'protein' else ['--dim', str(dim)])
+        config = ref_import.ref_config(argv, scratch)
+        config.dim = dim
+        config.maxFEs = max_fes
+        config.log_interval = max_fes // config.n_logpoint
+        return config
+
+    def put(key, rec, max_fes, first=None):
+        cases.append(key)
+        for k, v in rec.items():
+            data[f'{key}/{k}'] = v
+        for k, v in (first or {}).items():
+            data[f'{key}/first/{k}'] = v
+        data[f'{key}/max_fes'] = np.float64(max_fes)
+        data[f'{key}/next_rand'] = np.float64(np.random.rand())      # stream position after the episode(s)
+        print(key, len(rec['gbest']) - 1, rec['fes'][-1], rec['gbest'][-1], int(rec['np'][-1]), int(rec['na'][-1]), int(rec['narc'].max()), int(rec['n_over'].sum()),
+              len(rec['cost']), float(rec['margin']), float(rec['eref']))
+    jobs = [('bbob', 10, 15, 81, 20000), ('bbob', 10, 20, 220, 20000), ('bbob', 10, 21, 83, 20000), ('bbob-noisy', 10, 102, 84, 20000),
+            ('bbob', 2, 3, 85, 4000), ('bbob', 40, 10, 86, 8000)]
+    problems = {}
+    for suite, dim, fid, seed, max_fes in jobs:
+        if (suite, dim) not in problems:
+            tr, te, _ = all_problems(suite, dim)
+            problems[(suite, dim)] = {fid_of(p): p for p in tr + te}
+        config = config_for(suite, dim, max_fes)
+        for s in range(seed, seed + 400, 17):
+            np.random.seed(s)
+            try:
+                rec, _ = run_nlshade_episode(problems[(suite, dim)][fid], config)
+                break
+            except _NlReplace as e:
+                print('replaced', suite, dim, fid, s, e)
+        put(f'{suite}/{dim}/{fid}/{s}', rec, max_fes)
+    byid, _, _ = protein_problems()
+    config = config_for('protein', 12, 1000)
+    np.random.seed(87)
+    rec, _ = run_nlshade_episode(byid['1ATN_7'], config)
+    put('protein/12/1ATN_7/87', rec, 1000)
+    # two episodes on one optimizer object: (pb, NA) carry over
+    config = config_for('bbob', 10, 3000)
+    np.random.seed(88)
+    first, opt = run_nlshade_episode(problems[('bbob', 10)][15], config)
+    second, _ = run_nlshade_episode(problems[('bbob', 10)][3], config, opt)
+    put('second/10/15-3/88', second, 3000, first)
+    # F reflected and still negative (:119-121) needs a negative location MF[ind]; no reference episode on these suites reaches one (F < 0 reflects to
+    # 2 loc - F > 0 whenever loc > 0, and MF[k] is a quotient of sums of positive terms while every cost is positive).  So that the quirk is pinned to
+    # the reference's own arithmetic all the same, ONE reference update is recorded from a memory the generator makes negative in every odd slot after
+    # __init_population; the improved rows among them put NaN into MF[k] (a negative base under a fractional exponent), as numpy does.
+    mf0 = np.ones(200) * 0.5
+    mf0[1::2] = -0.3
+    np.random.seed(89)
+    rec, _ = run_nlshade_episode(problems[('bbob', 10)][15], config, mf0=mf0, max_updates=1)
+    assert np.isnan(rec['mem'][1][0])
+    put('crafted/10/15/89', rec, 3000)
+    data['cases'] = np.array(cases)
+    data['eref'] = np.float64(max([float(data[f'{c}/eref']) for c in cases] + [float(data[f'{c}/first/eref']) for c in cases if f'{c}/first/eref' in data]))
+    print('E_ref', float(data['eref']))
+    from optimizer import NL_SHADE_LBC
+    import copy
+    config = config_for('bbob', 10, 20000)
+    for fid in (8, 15, 21):
+        fin = []
+        for seed in range(100, 132):
+            np.random.seed(seed)
+            p = problems[('bbob', 10)][fid]
+            p.reset()
+            with np.errstate(all='ignore'):
+                r = NL_SHADE_LBC(copy.deepcopy(config)).run_episode(p)
+            fin.append((r['cost'][-1], r['fes']))
+        data[f'finals/bbob/10/{fid}'] = np.array(fin, dtype=np.float64)
+        print('finals', fid, np.median(np.array(fin), 0))
+    parts, sizes = [], []
+    for key in data:
+        prefix = '/'.join(key.split('/')[:4])
+        if prefix not in owner:
+            need = sum(data[k].nbytes for k in data if '/'.join(k.split('/')[:4]) == prefix)
+            for n in range(len(parts) + 1):
+                if n == len(parts):
+                    parts.append({}); sizes.append(0)
+                if sizes[n] + need <= 800 * 1024:
+                    break
+            owner[prefix] = n
+            sizes[n] += need
+        parts[owner[prefix]][key] = data[key]
+    for n, d in enumerate(parts):
+        path = os.path.join(OUT, 'nlshade_traces%s.npz' % ('' if n == 0 else '_' + 'abcdefgh'[n]))
+        np.savez_compressed(path, **d)
+        print(os.path.basename(path), os.path.getsize(path))
+        assert os.path.getsize(path) < 1024 * 1024
+
+
+SECTIONS = {'nlshade': gen_nlshade, 'rlhpsde': gen_rlhpsde, 'les': gen_les, 'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

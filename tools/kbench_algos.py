@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso|les|rlhpsde] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso|les|rlhpsde|nlshade] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -315,6 +315,39 @@ if 'rlhpsde' in which:
         for _ in range(n): b.step(acts)
     dt = timed(run_step, 10)
     print(json.dumps({'path': f'k_rlhpsde_step bbob d={dim}, {B} instances, one launch per update, the first 10 updates', 'ms_per_step': dt / 10 * 1e3}))
+    b.close()
+if 'nlshade' in which:
+    # NL_SHADE_LBC (one update = NP trials, NP = 23 D collapsing non-linearly to 4, two sorts, the r2 cdf, the memory update): bbob round-robin, 4096 instances at
+    # D = 10, the reference's budget of 20 000 without the early stop, so that every instance runs the 919 updates of the integer schedule.  Per-update time over
+    # the first 10 updates (NP 230 .. 203) and over updates 700 .. 709 (NP = 4); then the whole episode through 919 single-update launches (mbx_step) against the
+    # n-update launch (mbx_nlshade_run, 128 updates per launch, what NL_SHADE_LBC._run does), same batch, same process.  Wall times, launch gaps included; each
+    # window ends with a device synchronise.
+    from metabox_amd._abi import ALGO_NLSHADE
+    from metabox_amd.optimizer import NL_SHADE_LBC
+    from metabox_amd.suite import Batch, Suite
+    dim, B = 10, 4096
+    cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+    tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+    s = Suite(ps)
+    total = NL_SHADE_LBC.n_updates(dim, 20000)
+    b = Batch(s, ALGO_NLSHADE, np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1, 23 * dim, 20000, 400, 50, early_stop=False)
+    def steps(n):
+        for _ in range(n): b.step(None)
+    def chunks(n):
+        while n > 0:
+            b.nlshade_run(min(128, n)); n -= 128
+    b.reset(); steps(2)
+    first = timed(steps, 10) / 10 * 1e3
+    b.nlshade_run(700 - 12)
+    late = timed(steps, 10) / 10 * 1e3
+    print(json.dumps({'path': f'k_nlshade_step bbob d={dim}, {B} instances, one launch per update', 'ms_per_update_first_10': first, 'ms_per_update_at_NP_4': late,
+                      'launch_info': b.launch_info()}))
+    res = {}
+    for name, fn in (('919 single-update launches', steps), ('n-update launches of 128', chunks)) * 2:
+        b.reset(); torch.cuda.synchronize()
+        res.setdefault(name, []).append(timed(fn, total) * 1e3)
+        assert bool(b.done.all())
+    print(json.dumps({'path': f'NL_SHADE_LBC whole episode bbob d={dim}, {B} instances, {total} updates', 'ms_per_episode': {k: [round(x, 2) for x in v] for k, v in res.items()}}))
     b.close()
 if 'sdmspso' in which:
     # sDMS_PSO (one mbx_step = one update: 99 evaluated rows) next to GL-PSO (one generation: 200 evaluated rows and the exemplar breeding) in the
