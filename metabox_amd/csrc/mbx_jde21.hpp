@@ -489,14 +489,7 @@ __global__ __launch_bounds__(kThreads, WAVES) void k_jde21_generation(BatchParam
     }
     if (tid == 0) {
         int log_index = (int)sc[MBX_SC_LOG_INDEX], cost_len = (int)sc[MBX_SC_COST_LEN];
-        double* cost = sc + MBX_NSCALAR;
-        if (fes >= (double)log_index * bp.log_interval) { log_index += 1; if (cost_len <= bp.n_logpoint) curve_put(cost, bp.n_logpoint, cost_len++, gbest); }
-        bool done = fes >= bp.max_fes;
-        if (!isnan(P.optimum) && bp.early_stop) done = done || gbest <= 1e-8;
-        if (done) {
-            if (cost_len >= bp.n_logpoint + 1) curve_put(cost, bp.n_logpoint, cost_len - 1, gbest);
-            else curve_put(cost, bp.n_logpoint, cost_len++, gbest);
-        }
+        const bool done = log_and_terminate_guarded(bp, P, fes, gbest, log_index, cost_len, sc + MBX_NSCALAR);
         sc[MBX_SC_GBEST] = gbest; sc[MBX_SC_FES] = fes; sc[MBX_SC_LOG_INDEX] = log_index; sc[MBX_SC_COST_LEN] = cost_len;
         sc[MBX_SC_DONE] = done ? 1. : 0.; sc[MBX_SC_GEN] = gen; sc[MBX_SC_GBEST_IDX] = gi;
         sc[MBX_SC_JD_BNP] = new_bnp; sc[MBX_SC_JD_CBEST] = cbest; sc[MBX_SC_JD_CBEST_ID] = cbest_id;

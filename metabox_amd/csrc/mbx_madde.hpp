@@ -11,6 +11,9 @@
 // (HBM / L2); LDS holds the evaluator's chunk, the rank -> row lists of the three groups, and, after the evaluations, the archive's
 // write arbitration, one compacted vector for the long sums and the (cost, row) pairs of the sort, which share the chunk's memory.
 // Trials are evaluated in chunks of md_chunk(D) rows by the block-cooperative evaluator, with the noise draws of the whole update.
+// The carve-up and the phases NL_SHADE_LBC and RL-HPSDE have too (chunked evaluation, sorted first population, ranks of the improved rows, archive
+// write arbitration, the memory update's sums, replacement and row move) are in mbx_depop.hpp; this file holds MadDE's own draws, mutation,
+// crossover, strategy credit and bookkeeping.
 //
 // Long sums (memory update :147-152, strategy credit :247): the operands are compacted in rank order into LDS and added in numpy's
 // pairwise order for a contiguous vector (below 8 elements left to right from 0; up to 128 eight running accumulators combined as
@@ -44,139 +47,13 @@
 // Arithmetic follows numpy's expression order with no contraction (the build passes -ffp-contract=off).
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams, log_and_terminate_guarded
+#include "mbx_depop.hpp"    // the carve-up and the phases shared with NL_SHADE_LBC and RL-HPSDE
 
 namespace mbx {
 
 constexpr int kMdTries = 25;
 constexpr double kMdP = 0.18, kMdPqbx = 0.01, kMdM0 = 0.2, kMdNmin = 4.;
-
-// rows per evaluation chunk
-__host__ __device__ inline int md_chunk(int D) { return D <= 12 ? 128 : D <= 30 ? 96 : 64; }
-__host__ __device__ inline int md_pad(int n) { int p = 2; while (p < n) p <<= 1; return p; }
-// LDS of one evaluation chunk of ch rows: X | T | Z
-__host__ __device__ inline int64_t md_ev_doubles(int ch, int D)
-{
-    const int64_t ne = (int64_t)ch * D;
-    return align2(ne) + eval_t_doubles(ch, D) + align2(ne > 2 * kThreads ? ne : 2 * kThreads);
-}
-__host__ __device__ inline int64_t md_win_doubles(int NP) { return align2((MBX_MADDE_ARC(NP) + 1) / 2); }
-// the area the phases of an update share: evaluation chunk | archive winners (int) + compacted vector | sort keys + rows (int)
-__host__ __device__ inline int64_t md_work_doubles(int NP, int D)
-{
-    const int64_t a = md_ev_doubles(md_chunk(D), D), b = md_win_doubles(NP) + align2(NP), c = md_pad(NP) + align2(md_pad(NP) / 2);
-    return a > b ? (a > c ? a : c) : (b > c ? b : c);
-}
-__host__ __device__ inline int64_t md_lds_doubles(int NP, int D)
-{
-    const int64_t DD = align2((int64_t)D * D);
-    return md_work_doubles(NP, D) + 2 * DD + 4 * align2(D) + align2(md_chunk(D)) + 16 + 2 * kThreads + align2((NP + 1) / 2) + align2((NP + 7) / 8);
-}
-
-struct MdLds {
-    double *EV, *M1T, *M2T, *DSH, *V0, *V1, *V2, *TC, *RED, *VEC, *KEY;
-    int *CNT, *LIST, *WIN, *IDX;
-    uint8_t* MU;
-    __device__ __forceinline__ EvalLds eval(int ch, int D, double* f) const
-    {
-        double* T = EV + align2((int64_t)ch * D);
-        return EvalLds{EV, T + eval_t_doubles(ch, D), T, M1T, M2T, DSH, V0, V1, V2, f};
-    }
-};
-
-__device__ __forceinline__ MdLds md_carve(double* base, int NP, int D)
-{
-    const int64_t DD = align2((int64_t)D * D);
-    MdLds L;
-    double* p = base;
-    L.EV = p; L.WIN = reinterpret_cast<int*>(p); L.VEC = p + md_win_doubles(NP); L.KEY = p; L.IDX = reinterpret_cast<int*>(p + md_pad(NP));
-    p += md_work_doubles(NP, D);
-    L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);
-    L.TC = p; p += align2(md_chunk(D));  L.RED = p; p += 16;
-    L.CNT = reinterpret_cast<int*>(p); p += 2 * kThreads;
-    L.LIST = reinterpret_cast<int*>(p); p += align2((NP + 1) / 2);
-    L.MU = reinterpret_cast<uint8_t*>(p);
-    return L;
-}
-
-// Exclusive prefix sums over the threads of three per-thread counts (base) and their totals.  All threads call; ends with a barrier.
-__device__ __forceinline__ void md_scan3(int* CNT, const int (&c)[3], int (&base)[3], int (&tot)[3])
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int g = 0; g < 3; ++g) CNT[g * kThreads + tid] = c[g];
-    __syncthreads();
-    if (tid < 3) {
-        int run = 0;
-        for (int t = 0; t < kThreads; ++t) { const int v = CNT[tid * kThreads + t]; CNT[tid * kThreads + t] = run; run += v; }
-        CNT[3 * kThreads + tid] = run;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int g = 0; g < 3; ++g) { base[g] = CNT[g * kThreads + tid]; tot[g] = CNT[3 * kThreads + g]; }
-    __syncthreads();
-}
-
-// numpy's pairwise sum of a contiguous vector: a block of at most 128 elements ...
-__device__ __noinline__ double md_pw_leaf(const double* a, int n)
-{
-    if (n < 8) {
-        double r = 0.;
-        for (int i = 0; i < n; ++i) r += a[i];
-        return r;
-    }
-    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-        r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3]; r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
-    }
-    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
-// ... and the halving recursion above that, DEPTH levels of it: 128 << DEPTH elements at least (n2 is rounded down, so the right half may
-// be the longer one by up to 8 + 1: the depth is chosen with a level to spare)
-template <int DEPTH>
-__device__ __forceinline__ double md_pw(const double* a, int n)
-{
-    if (n <= 128) return md_pw_leaf(a, n);
-    if constexpr (DEPTH == 0) return NAN;
-    else {
-        int n2 = n / 2;
-        n2 -= n2 % 8;
-        return md_pw<DEPTH - 1>(a, n2) + md_pw<DEPTH - 1>(a + n2, n - n2);
-    }
-}
-__device__ __forceinline__ double md_pairwise(const double* a, int n) { return md_pw<6>(a, n); }      // n <= 3200
-
-// (cost, row) order of the sort; a NaN cost sorts last, as numpy places it
-__device__ __forceinline__ bool md_less(double ka, int ia, double kb, int ib)
-{
-    const bool an = isnan(ka), bn = isnan(kb);
-    if (an || bn) return an == bn ? ia < ib : bn;
-    return ka < kb || (ka == kb && ia < ib);
-}
-
-// Sort the pairs KEY / IDX [0, npad) (npad a power of two, padded with +inf / rows >= n) ascending by md_less.  All threads call; the
-// caller synchronises before, the sort ends with a barrier.
-__device__ __forceinline__ void md_sort(double* KEY, int* IDX, int npad)
-{
-    const int tid = threadIdx.x;
-    for (int k = 2; k <= npad; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-#ifndef MBX_ABLATE_MD_SORT
-            for (int t = tid; t < (npad >> 1); t += kThreads) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const bool up = (i & k) == 0;
-                const double ka = KEY[i], kb = KEY[l];
-                const int ia = IDX[i], ib = IDX[l];
-                if (md_less(kb, ib, ka, ia) == up) { KEY[i] = kb; KEY[l] = ka; IDX[i] = ib; IDX[l] = ia; }
-            }
-#endif
-            __syncthreads();
-        }
-}
 
 // population size after `fes` evaluations (:256): N0 + ((4 - N0) fes) / max_fes, the product exact, rounded half to even
 __host__ __device__ inline int md_np_at(int N0, double fes, double max_fes)
@@ -185,8 +62,6 @@ __host__ __device__ inline int md_np_at(int N0, double fes, double max_fes)
     return n < 1 ? 1 : n > N0 ? N0 : n;
 }
 
-// (mbx_rlhpsde.hpp uses the device pieces above in a translation unit of its own, which must not define MadDE's kernels a second time)
-#ifndef MBX_MADDE_PIECES_ONLY
 // ------------------------------------------------------------------------------------------------ reset (__init_population :179-195)
 __global__ __launch_bounds__(kThreads) void k_madde_reset(BatchParams bp, double* __restrict__ state_out)
 {
@@ -205,36 +80,17 @@ __global__ __launch_bounds__(kThreads) void k_madde_reset(BatchParams bp, double
     const Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), 0u, (uint32_t)episode};
     const double lb = P.lb, ub = P.ub;
     stage_problem(P, L.eval(CH, D, L.TC));
-    for (int c0 = 0; c0 < N0; c0 += CH) {
-        const int n = min(CH, N0 - c0);
-        for (int e = tid; e < n * D; e += kThreads) {
-            const int g = c0 * D + e;
-            double u;
-            if (tape) u = tape[MBX_MADDE_TAPE_POS(N0, D) + g];
-            else { const U4 w = rng.draw((uint32_t)g, MBX_SITE_MD_CROSS); u = u53(w.x, w.y); }
-            const double x = u * (ub - lb) + lb;
-            L.EV[e] = x;
-            gU[g] = x;
-        }
-        __syncthreads();
-        population_costs(P, L.eval(n, D, L.TC), n, rng, tape ? tape + MBX_MADDE_TAPE_NOISE_INIT(N0, D) : nullptr, MBX_SITE_NOISE1_A,
-                         MBX_SITE_NOISE1_B, c0, N0);
-        if (tid < n) gNC[c0 + tid] = L.TC[tid];
-        __syncthreads();
-    }
+    // the rows are drawn chunk by chunk on their way into the evaluator
+    auto draw = [&](int g) -> double {
+        double u;
+        if (tape) u = tape[MBX_MADDE_TAPE_POS(N0, D) + g];
+        else { const U4 w = rng.draw((uint32_t)g, MBX_SITE_MD_CROSS); u = u53(w.x, w.y); }
+        return gU[g] = u * (ub - lb) + lb;
+    };
+    md_eval_rows(P, L, N0, N0, D, draw, gNC, rng, tape ? tape + MBX_MADDE_TAPE_NOISE_INIT(N0, D) : nullptr, MBX_SITE_NOISE1_A, MBX_SITE_NOISE1_B);
     // sort by (cost, row) and move the rows into buffer 0
-    const int npad = md_pad(N0);
-    for (int t = tid; t < npad; t += kThreads) { L.KEY[t] = t < N0 ? gNC[t] : INFINITY; L.IDX[t] = t; }
-    __syncthreads();
-    md_sort(L.KEY, L.IDX, npad);
-    double* pop = S + MBX_MADDE_ST_POP(N0, D);
-    const FastDiv fd(D);
-    for (int e = tid; e < N0 * D; e += kThreads) {
-        const int r = fd.div(e);
-        pop[e] = gU[min(L.IDX[r], N0 - 1) * D + (e - r * D)];             // (clamped: a NaN cost sorts behind the padding)
-    }
+    md_init_sorted(L, gU, gNC, S + MBX_MADDE_ST_POP(N0, D), S + MBX_MADDE_ST_COST(N0, D), N0, D);
     for (int t = tid; t < N0; t += kThreads) {
-        S[MBX_MADDE_ST_COST(N0, D) + t] = L.KEY[t];
         S[MBX_MADDE_ST_F(N0, D) + t] = 0.;
         S[MBX_MADDE_ST_CR(N0, D) + t] = 0.;
         S[MBX_MADDE_ST_Z(N0, D) + t] = 0.;
@@ -378,46 +234,25 @@ __global__ __launch_bounds__(kThreads) void k_madde_generation(BatchParams bp, d
     }
     __syncthreads();
     // ---- evaluation of the trials in row chunks
-    for (int c0 = 0; c0 < NP; c0 += CH) {
-        const int n = min(CH, NP - c0);
-        for (int e = tid; e < n * D; e += kThreads) L.EV[e] = gU[(int64_t)c0 * D + e];
-        __syncthreads();
-        population_costs(P, L.eval(n, D, L.TC), n, rng, tape ? tape + MBX_MADDE_TAPE_NOISE(N0, D) : nullptr, MBX_SITE_MD_NOISE_A,
-                         MBX_SITE_MD_NOISE_B, c0, N0);
-        if (tid < n) gNC[c0 + tid] = L.TC[tid];
-        __syncthreads();
-    }
+    md_eval_rows(P, L, NP, N0, D, [&](int e) { return gU[e]; }, gNC, rng, tape ? tape + MBX_MADDE_TAPE_NOISE(N0, D) : nullptr, MBX_SITE_MD_NOISE_A,
+                 MBX_SITE_MD_NOISE_B);
     // ---- selection (:238): ranks of the improved rows
-    int ocnt[3] = {0, 0, 0}, obase[3], otot[3];
-    for (int i = row0; i < row1; ++i) ocnt[0] += gNC[i] < gC[i];
-    md_scan3(L.CNT, ocnt, obase, otot);
-    const int n_opt = otot[0], n_app = min(max(NA - narc, 0), n_opt), alen = narc + n_app;
+    int obase, n_opt;
+    md_rank_improved(L, gC, gNC, row0, row1, obase, n_opt);
+    const int n_app = min(max(NA - narc, 0), n_opt), alen = narc + n_app;
     // ---- archive (:141-145, :239-240)
 #ifndef MBX_ABLATE_MD_ARC
     if (alen > 0) {
-    for (int t = tid; t < alen; t += kThreads) L.WIN[t] = -1;
-    __syncthreads();
-    auto target = [&](int k) -> int {
-        if (tape) return min(max((int)tape[MBX_MADDE_TAPE_ARC(N0, D) + k], 0), alen - 1);
-        return (int)__umulhi(rng.draw((uint32_t)k, MBX_SITE_MD_ARC).x, (uint32_t)alen);
-    };
-    {
-        int k = obase[0];
-        for (int i = row0; i < row1; ++i)
-            if (gNC[i] < gC[i]) { if (k >= n_app) atomicMax(&L.WIN[target(k)], k); ++k; }
-    }
-    __syncthreads();
-    {
-        int k = obase[0];
-        for (int i = row0; i < row1; ++i)
-            if (gNC[i] < gC[i]) {
-                const int t = k < n_app ? narc + k : target(k);
-                if (k < n_app ? L.WIN[t] < 0 : L.WIN[t] == k)
-                    for (int d = 0; d < D; ++d) arc[(int64_t)t * D + d] = pop[(int64_t)i * D + d];
-                ++k;
-            }
-    }
-    __syncthreads();
+        auto target = [&](int k) -> int {
+            if (tape) return min(max((int)tape[MBX_MADDE_TAPE_ARC(N0, D) + k], 0), alen - 1);
+            return (int)__umulhi(rng.draw((uint32_t)k, MBX_SITE_MD_ARC).x, (uint32_t)alen);
+        };
+        // the parent of an improved row is the row itself: a thread walks its rows with a running rank
+        md_archive_write(L, arc, pop, D, narc, n_app, alen, target, [&](auto put) {
+            int k = obase;
+            for (int i = row0; i < row1; ++i) if (gNC[i] < gC[i]) put(k++, i);
+        });
+        __syncthreads();
     }
 #endif
     // ---- memory (:147-177): weighted Lehmer means over the improved rows, compacted in rank order, numpy's pairwise sums
@@ -426,26 +261,8 @@ __global__ __launch_bounds__(kThreads) void k_madde_generation(BatchParams bp, d
     if (n_opt > 0) {
         // pass 0: df;  1: w SF;  2: w SF^2;  3: w SCr;  4: w SCr^2
         double sums[5];
-        for (int pass = 0; pass < 5; ++pass) {
-            int k = obase[0];
-            for (int i = row0; i < row1; ++i) {
-                const double c = gC[i], nc = gNC[i];
-                if (nc < c) {
-                    const double df = fmax(0., c - nc);
-                    double v = df;
-                    if (pass > 0) {
-                        const double w = df / sums[0], s = pass <= 2 ? gF[i] : gCr[i];
-                        v = (pass & 1) ? w * s : w * (s * s);
-                    }
-                    L.VEC[k++] = v;
-                }
-            }
-            __syncthreads();
-            if (tid == 0) L.RED[0] = md_pairwise(L.VEC, n_opt);
-            __syncthreads();
-            sums[pass] = L.RED[0];
-            __syncthreads();
-        }
+        md_weighted_sums(L, gC, gNC, row0, row1, obase, n_opt, [](double c, double nc) { return fmax(0., c - nc); },
+                         [&](int pass, double w, int i) { const double s = pass <= 2 ? gF[i] : gCr[i]; return (pass & 1) ? w * s : w * (s * s); }, sums);
         newMF = sums[1] > 0.000001 ? sums[2] / sums[1] : 0.5;
         newMCr = sums[3] > 0.000001 ? sums[4] / sums[3] : 0.5;
     }
@@ -477,23 +294,8 @@ __global__ __launch_bounds__(kThreads) void k_madde_generation(BatchParams bp, d
     }
     // ---- replacement, LPSR, sort (:254-261): rows into the other buffer in (cost, row) order
     const double fes = fes0 + NP;
-    const int NPn = min(md_np_at(N0, fes, mf), NP), NAn = (int)(2.3 * NPn), npad = md_pad(NP);
-    for (int t = tid; t < npad; t += kThreads) {
-        double key = INFINITY;
-        if (t < NP) { const double c = gC[t], nc = gNC[t]; key = nc < c ? nc : c; }
-        L.KEY[t] = key; L.IDX[t] = t;
-    }
-    __syncthreads();
-    md_sort(L.KEY, L.IDX, npad);
-#ifndef MBX_ABLATE_MD_SORT
-    const FastDiv fd(D);
-    for (int e = tid; e < NPn * D; e += kThreads) {
-        const int r = fd.div(e), d = e - r * D, p = min(L.IDX[r], NP - 1);      // (clamped: a NaN cost sorts behind the padding)
-        npop[e] = gNC[p] < gC[p] ? gU[(int64_t)p * D + d] : pop[(int64_t)p * D + d];
-    }
-#endif
-    __syncthreads();
-    for (int t = tid; t < NPn; t += kThreads) gC[t] = L.KEY[t];
+    const int NPn = min(md_np_at(N0, fes, mf), NP), NAn = (int)(2.3 * NPn);
+    md_replace_sorted(L, gC, gNC, gU, pop, npop, NP, NPn, D);
     // ---- bookkeeping (:263-272)
     if (tid == 0) {
         const double best = L.KEY[0];
@@ -501,14 +303,7 @@ __global__ __launch_bounds__(kThreads) void k_madde_generation(BatchParams bp, d
         gMF[k_mem] = newMF; gMCr[k_mem] = newMCr;
         gpm[0] = pm0; gpm[1] = pm1; gpm[2] = pm2;
         int log_index = log_index0, cost_len = cost_len0;
-        double* cost = sc + MBX_NSCALAR;
-        if (fes >= (double)log_index * bp.log_interval) { log_index += 1; if (cost_len <= bp.n_logpoint) curve_put(cost, bp.n_logpoint, cost_len++, gbest); }
-        bool done = fes >= mf;
-        if (!isnan(P.optimum) && bp.early_stop) done = done || gbest <= 1e-8;
-        if (done) {
-            if (cost_len >= bp.n_logpoint + 1) curve_put(cost, bp.n_logpoint, cost_len - 1, gbest);
-            else curve_put(cost, bp.n_logpoint, cost_len++, gbest);
-        }
+        const bool done = log_and_terminate_guarded(bp, P, fes, gbest, log_index, cost_len, sc + MBX_NSCALAR);
         sc[MBX_SC_GBEST] = gbest; sc[MBX_SC_FES] = fes; sc[MBX_SC_LOG_INDEX] = log_index; sc[MBX_SC_COST_LEN] = cost_len;
         sc[MBX_SC_DONE] = done ? 1. : 0.; sc[MBX_SC_GEN] = gen; sc[MBX_SC_GBEST_IDX] = 0;
         sc[MBX_SC_MD_NP] = NPn; sc[MBX_SC_MD_ARC] = min(alen, NAn); sc[MBX_SC_MD_NA] = NAn;
@@ -518,7 +313,5 @@ __global__ __launch_bounds__(kThreads) void k_madde_generation(BatchParams bp, d
         if (done_out) done_out[b] = done ? 1 : 0;
     }
 }
-
-#endif  // MBX_MADDE_PIECES_ONLY
 
 }  // namespace mbx

@@ -8,9 +8,11 @@
 // collapses early: more than half of an episode is updates of a handful of rows, where one launch per update is all launch latency).  Step and run
 // are one device body (nl_updates).  One workgroup of 256 threads per instance, dispatched through bp.order; state block and tape:
 // include/mbx_layout.h §20.  A thread owns a contiguous block of ceil(NP / 256) rows.  Population, archive, trial rows and the memory stay in the
-// state block; LDS is MadDE's (md_carve): the evaluator's chunk, which between evaluations holds the sort keys (Cr, then (cost, row)), the cdf of
-// the r2 choice, the archive's write arbitration and the compacted vector of the long sums.  The device pieces (sort, pairwise sums, scan,
-// evaluation chunk) are MadDE's, included under MBX_MADDE_PIECES_ONLY.
+// state block; LDS is the carve-up shared with MadDE (md_carve): the evaluator's chunk, which between evaluations holds the sort keys (Cr, then
+// (cost, row)), the cdf of the r2 choice, the archive's write arbitration and the compacted vector of the long sums.  The carve-up, the sort, the
+// pairwise sums, the scan and the phases MadDE and RL-HPSDE have too (the reset's chunked evaluation and sorted first population, the archive's
+// write arbitration, replacement and row move) are in mbx_depop.hpp; this file holds the algorithm's own draws, mutation, crossovers, memory
+// update and bookkeeping, and the update's evaluation loop and ranking, which measured slower through the shared functions.
 //
 // The reading of the reference, kept on purpose:
 //   1. the sort is by (cost, row), numpy's kind='stable' order (the reference's introsort is not reproducible among equal costs); it runs at the end
@@ -49,8 +51,8 @@
 // Arithmetic follows numpy's expression order with no contraction (the build passes -ffp-contract=off).
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
-#include "mbx_madde.hpp"    // the device pieces: md_carve, md_sort, md_pairwise, md_scan3
+#include "mbx_rlepso.hpp"   // BatchParams, log_and_terminate_guarded
+#include "mbx_depop.hpp"    // the carve-up and the phases shared with MadDE and RL-HPSDE
 
 namespace mbx {
 
@@ -84,36 +86,17 @@ __global__ __launch_bounds__(kThreads) void k_nlshade_reset(BatchParams bp, doub
     const Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), 0u, (uint32_t)episode};
     const double lb = P.lb, ub = P.ub;
     stage_problem(P, L.eval(CH, D, L.TC));
-    for (int c0 = 0; c0 < N0; c0 += CH) {
-        const int n = min(CH, N0 - c0);
-        for (int e = tid; e < n * D; e += kThreads) {
-            const int g = c0 * D + e;
-            double u;
-            if (tape) u = tape[MBX_NLSHADE_TAPE_POS(N0, D) + g];
-            else { const U4 w = rng.draw((uint32_t)g, MBX_SITE_NL_CROSS); u = u53(w.x, w.y); }
-            const double x = u * (ub - lb) + lb;
-            L.EV[e] = x;
-            gU[g] = x;
-        }
-        __syncthreads();
-        population_costs(P, L.eval(n, D, L.TC), n, rng, tape ? tape + MBX_NLSHADE_TAPE_NOISE_INIT(N0, D) : nullptr, MBX_SITE_NOISE1_A,
-                         MBX_SITE_NOISE1_B, c0, N0);
-        if (tid < n) gNC[c0 + tid] = L.TC[tid];
-        __syncthreads();
-    }
+    // the rows are drawn chunk by chunk on their way into the evaluator
+    auto draw = [&](int g) -> double {
+        double u;
+        if (tape) u = tape[MBX_NLSHADE_TAPE_POS(N0, D) + g];
+        else { const U4 w = rng.draw((uint32_t)g, MBX_SITE_NL_CROSS); u = u53(w.x, w.y); }
+        return gU[g] = u * (ub - lb) + lb;
+    };
+    md_eval_rows(P, L, N0, N0, D, draw, gNC, rng, tape ? tape + MBX_NLSHADE_TAPE_NOISE_INIT(N0, D) : nullptr, MBX_SITE_NOISE1_A, MBX_SITE_NOISE1_B);
     // sort by (cost, row) and move the rows into buffer 0
-    const int npad = md_pad(N0);
-    for (int t = tid; t < npad; t += kThreads) { L.KEY[t] = t < N0 ? gNC[t] : INFINITY; L.IDX[t] = t; }
-    __syncthreads();
-    md_sort(L.KEY, L.IDX, npad);
-    double* pop = S + MBX_NLSHADE_ST_POP(N0, D);
-    const FastDiv fd(D);
-    for (int e = tid; e < N0 * D; e += kThreads) {
-        const int r = fd.div(e);
-        pop[e] = gU[min(L.IDX[r], N0 - 1) * D + (e - r * D)];             // (clamped: a NaN cost sorts behind the padding)
-    }
+    md_init_sorted(L, gU, gNC, S + MBX_NLSHADE_ST_POP(N0, D), S + MBX_NLSHADE_ST_COST(N0, D), N0, D);
     for (int t = tid; t < N0; t += kThreads) {
-        S[MBX_NLSHADE_ST_COST(N0, D) + t] = L.KEY[t];
         S[MBX_NLSHADE_ST_F(N0, D) + t] = 0.;
         S[MBX_NLSHADE_ST_CR(N0, D) + t] = 0.;
         S[MBX_NLSHADE_ST_Z(N0, D) + t] = 0.;
@@ -284,6 +267,8 @@ __device__ __forceinline__ void nl_updates(const BatchParams& bp, int n_updates,
         }
         __syncthreads();
         // ---- evaluation of the trials in row chunks
+        // (this loop, the ranking and the sums below are md_eval_rows, md_rank_improved and md_weighted_sums written out: through the shared functions the
+        // update measured 1.5 % to 3 % slower, docs/EXPERIMENTS.md "Shared phases of the sorted-DE kernels")
         for (int c0 = 0; c0 < NP; c0 += CH) {
             const int n = min(CH, NP - c0);
             for (int e = tid; e < n * D; e += kThreads) L.EV[e] = gU[(int64_t)c0 * D + e];
@@ -313,19 +298,11 @@ __device__ __forceinline__ void nl_updates(const BatchParams& bp, int n_updates,
         }
         // ---- archive (:129-133, :244-245): the parent of rank k is population row k
         if (n_opt > 0 && alen > 0) {
-            for (int t = tid; t < alen; t += kThreads) L.WIN[t] = -1;
-            __syncthreads();
             auto target = [&](int k) -> int {
                 if (tape) return min(max((int)tape[MBX_NLSHADE_TAPE_ARCW(N0, D) + k], 0), alen - 1);
                 return (int)__umulhi(rng.draw((uint32_t)k, MBX_SITE_NL_ARC).x, (uint32_t)alen);
             };
-            for (int k = n_app + tid; k < n_opt; k += kThreads) atomicMax(&L.WIN[target(k)], k);
-            __syncthreads();
-            for (int k = tid; k < n_opt; k += kThreads) {
-                const int t = k < n_app ? narc + k : target(k);
-                if (k < n_app ? L.WIN[t] < 0 : L.WIN[t] == k)
-                    for (int d = 0; d < D; ++d) arc[(int64_t)t * D + d] = pop[(int64_t)k * D + d];
-            }
+            md_archive_write(L, arc, pop, D, narc, n_app, alen, target, [&](auto put) { for (int k = tid; k < n_opt; k += kThreads) put(k, k); });
         }
         __syncthreads();
         // ---- memory (:83-109): weighted Lehmer-type means over the improved rows, compacted in rank order, numpy's pairwise sums
@@ -363,34 +340,14 @@ __device__ __forceinline__ void nl_updates(const BatchParams& bp, int n_updates,
         // ---- replacement, NLPSR, sort (:253-262, :135-147): rows into the other buffer in (cost, row) order
         const int Nt = (int)bp.pci[1 + min(max(gen, 0), n_sched)];
         const int NPn = min(max(Nt, 1), NP), A = max(Nt, kNlNmin);
-        for (int t = tid; t < npad; t += kThreads) {
-            double key = INFINITY;
-            if (t < NP) { const double c = gC[t], nc = gNC[t]; key = nc < c ? nc : c; }
-            L.KEY[t] = key; L.IDX[t] = t;
-        }
-        __syncthreads();
-        md_sort(L.KEY, L.IDX, npad);
-        const FastDiv fd(D);
-        for (int e = tid; e < NPn * D; e += kThreads) {
-            const int r = fd.div(e), d = e - r * D, p = min(L.IDX[r], NP - 1);      // (clamped: a NaN cost sorts behind the padding)
-            npop[e] = gNC[p] < gC[p] ? gU[(int64_t)p * D + d] : pop[(int64_t)p * D + d];
-        }
-        __syncthreads();
-        for (int t = tid; t < NPn; t += kThreads) gC[t] = L.KEY[t];
+        md_replace_sorted(L, gC, gNC, gU, pop, npop, NP, NPn, D);
         // ---- bookkeeping (:256-273)
         if (tid == 0) {
             const double best = L.RED[1];
             const double gbest = best < gbest0 ? best : gbest0;
             gMF[k_mem] = newMF; gMCr[k_mem] = newMCr;
             int log_index = log_index0, cost_len = cost_len0;
-            double* cost = sc + MBX_NSCALAR;
-            if (fes >= (double)log_index * bp.log_interval) { log_index += 1; if (cost_len <= bp.n_logpoint) curve_put(cost, bp.n_logpoint, cost_len++, gbest); }
-            bool dn = fes >= mf;
-            if (!isnan(P.optimum) && bp.early_stop) dn = dn || gbest <= 1e-8;
-            if (dn) {
-                if (cost_len >= bp.n_logpoint + 1) curve_put(cost, bp.n_logpoint, cost_len - 1, gbest);
-                else curve_put(cost, bp.n_logpoint, cost_len++, gbest);
-            }
+            const bool dn = log_and_terminate_guarded(bp, P, fes, gbest, log_index, cost_len, sc + MBX_NSCALAR);
             sc[MBX_SC_GBEST] = gbest; sc[MBX_SC_FES] = fes; sc[MBX_SC_LOG_INDEX] = log_index; sc[MBX_SC_COST_LEN] = cost_len;
             sc[MBX_SC_DONE] = dn ? 1. : 0.; sc[MBX_SC_GEN] = gen; sc[MBX_SC_GBEST_IDX] = 0;
             sc[MBX_SC_NL_NP] = NPn; sc[MBX_SC_NL_ARC] = A < alen ? A : alen; sc[MBX_SC_NL_K] = n_opt > 0 ? (k_mem + 1) % H : k_mem;

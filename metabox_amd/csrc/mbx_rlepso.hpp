@@ -54,6 +54,23 @@ __device__ __forceinline__ bool log_and_terminate(const BatchParams& bp, const P
     return done;
 }
 
+// The same bookkeeping as MadDE, NL_SHADE_LBC and JDE21 keep it: the log-point append is guarded, so once the curve holds its n_logpoint + 1
+// entries no further log point is appended and cost_len stops counting there.  (RL-HPSDE, which shares its other phases with MadDE and
+// NL_SHADE_LBC, uses the unguarded rule above.)
+template <class PT>
+__device__ __forceinline__ bool log_and_terminate_guarded(const BatchParams& bp, const PT& P, double fes, double gbest, int& log_index,
+                                                          int& cost_len, double* __restrict__ cost)
+{
+    if (fes >= (double)log_index * bp.log_interval) { log_index += 1; if (cost_len <= bp.n_logpoint) curve_put(cost, bp.n_logpoint, cost_len++, gbest); }
+    bool done = fes >= bp.max_fes;
+    if (!isnan(P.optimum) && bp.early_stop) done = done || gbest <= 1e-8;
+    if (done) {
+        if (cost_len >= bp.n_logpoint + 1) curve_put(cost, bp.n_logpoint, cost_len - 1, gbest);
+        else curve_put(cost, bp.n_logpoint, cost_len++, gbest);
+    }
+    return done;
+}
+
 // LDS carve-up (all offsets in doubles; base is 16-byte aligned, every array starts 16-byte aligned)
 struct RlLds {
     double *PB, *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *PBC, *NC, *PNI, *CMUT, *R1, *R2, *GB, *COEF, *RED;

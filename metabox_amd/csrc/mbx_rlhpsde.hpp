@@ -13,8 +13,9 @@
 // k_rlhpsde_reset is init_population, k_rlhpsde_step one update with the caller's action, k_rlhpsde_run n_steps updates per launch with the 4 x 4
 // Q-table in the workgroup; step and run are the same body (hp_steps), so they are bit-identical by construction.  A finished instance stays
 // frozen.  One workgroup of 256 threads per instance, dispatched through bp.order; state block and tape: include/mbx_layout.h section 19.  As in
-// MadDE (mbx_madde.hpp, whose device pieces are used here: carve-up, prefix scan, numpy's pairwise sums, the bitonic (cost, row) sort, the chunked
-// evaluator) a thread owns a contiguous block of ceil(NP / 256) rows; population, trial rows, costs, F, Cr, the indices and the walk points stay in
+// MadDE and NL_SHADE_LBC (the three share mbx_depop.hpp: carve-up, prefix scan, numpy's pairwise sums, the bitonic (cost, row) sort, and the phases
+// chunked evaluation, sorted first population, ranks of the improved rows, the memory update's sums, replacement and row move; this file holds the
+// algorithm's own draws, mutation, crossover, walk and bookkeeping) a thread owns a contiguous block of ceil(NP / 256) rows; population, trial rows, costs, F, Cr, the indices and the walk points stay in
 // the state block (HBM / L2); LDS holds the evaluator's chunk, the (cost, row) pairs of the sort, the compacted vectors of the long sums, and the
 // walk's costs, distances, differences and transition counts.  The walk is one lane per coordinate with 200 sequential steps.  The means, the
 // variances, the covariance and the row norms follow numpy's pairwise order (mbx_npsum.hpp).  The logarithms of the frequencies n / 200 come from
@@ -40,14 +41,15 @@
 #pragma once
 #include "mbx_device.hpp"
 #include "mbx_rlepso.hpp"   // BatchParams, align2, log_and_terminate
-#include "mbx_madde.hpp"    // MdLds, md_carve, md_scan3, md_pairwise, md_sort, md_chunk, md_pad
+#include "mbx_depop.hpp"    // the carve-up and the phases shared with MadDE and NL_SHADE_LBC
 #include "mbx_npsum.hpp"
 #include "mbx_qchoose.hpp"
 
 namespace mbx {
 
 constexpr int kHpTries = 25, kHpWalk = MBX_RLHPSDE_WALK, kHpSteps = MBX_RLHPSDE_WALK - 1;
-constexpr int kHpFeatDoubles = 752;      // walk costs [202] | distances [200] | differences [202] | entropies [12] | counts: 4 waves x 64 ints
+static_assert(kHpWalk <= kThreads, "one thread per walk point");
+constexpr int kHpFeatDoubles = 752;     // walk costs [202] | distances [200] | differences [202] | entropies [12] | counts: 4 waves x 64 ints
 
 // per-step records of k_rlhpsde_run (each may be nullptr) and the last action of every instance
 struct HpTraj { int32_t* actions; double* state; double* reward; int32_t* last_action; };
@@ -68,7 +70,7 @@ template <class PT>
 __device__ void hp_walk_state(const PT& P, const MdLds& L, double* FT, double* S, int N0, int D, const Rng& rng, const double* tape,
                               const double* best, const double* __restrict__ logtab)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, CH = md_chunk(D);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double* W = S + MBX_RLHPSDE_ST_WALK(N0, D);
     double* gWC = S + MBX_RLHPSDE_ST_WCOST(N0, D);
     double* gFT = S + MBX_RLHPSDE_ST_FEAT(N0, D);
@@ -106,15 +108,9 @@ __device__ void hp_walk_state(const PT& P, const MdLds& L, double* FT, double* S
     }
     __syncthreads();
     // ---- the walk's costs, in row chunks
-    for (int c0 = 0; c0 < kHpWalk; c0 += CH) {
-        const int n = min(CH, kHpWalk - c0);
-        for (int e = tid; e < n * D; e += kThreads) L.EV[e] = W[(int64_t)c0 * D + e];
-        __syncthreads();
-        population_costs(P, L.eval(n, D, L.TC), n, rng, tape ? tape + MBX_RLHPSDE_TAPE_WNOISE(N0, D) : nullptr, MBX_SITE_HP_WNOISE_A,
-                         MBX_SITE_HP_WNOISE_B, c0, kHpWalk);
-        if (tid < n) { WC[c0 + tid] = L.TC[tid]; gWC[c0 + tid] = L.TC[tid]; }
-        __syncthreads();
-    }
+    md_eval_rows(P, L, kHpWalk, kHpWalk, D, [&](int e) { return W[e]; }, WC, rng, tape ? tape + MBX_RLHPSDE_TAPE_WNOISE(N0, D) : nullptr,
+                 MBX_SITE_HP_WNOISE_A, MBX_SITE_HP_WNOISE_B);
+    if (tid < kHpWalk) gWC[tid] = WC[tid];
     // ---- distances to row 0 (np.linalg.norm(., axis=-1): sqrt of a pairwise row sum) and the first differences
     if (tid < kHpSteps) {
         const double* x = W + (int64_t)(tid + 1) * D;
@@ -195,36 +191,18 @@ __global__ __launch_bounds__(kThreads) void k_rlhpsde_reset(BatchParams bp, doub
     const Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), 0u, (uint32_t)episode};
     const double lb = P.lb, ub = P.ub;
     stage_problem(P, L.eval(CH, D, L.TC));
-    for (int c0 = 0; c0 < N0; c0 += CH) {
-        const int n = min(CH, N0 - c0);
-        for (int e = tid; e < n * D; e += kThreads) {
-            const int g = c0 * D + e;
-            double u;
-            if (tape) u = tape[MBX_RLHPSDE_TAPE_POS(N0, D) + g];
-            else { const U4 w = rng.draw((uint32_t)g, MBX_SITE_HP_CROSS); u = u53(w.x, w.y); }
-            const double x = u * (ub - lb) + lb;
-            L.EV[e] = x;
-            gU[g] = x;
-        }
-        __syncthreads();
-        population_costs(P, L.eval(n, D, L.TC), n, rng, tape ? tape + MBX_RLHPSDE_TAPE_NOISE_INIT(N0, D) : nullptr, MBX_SITE_NOISE1_A,
-                         MBX_SITE_NOISE1_B, c0, N0);
-        if (tid < n) gNC[c0 + tid] = L.TC[tid];
-        __syncthreads();
-    }
+    // the rows are drawn chunk by chunk on their way into the evaluator
+    auto draw = [&](int g) -> double {
+        double u;
+        if (tape) u = tape[MBX_RLHPSDE_TAPE_POS(N0, D) + g];
+        else { const U4 w = rng.draw((uint32_t)g, MBX_SITE_HP_CROSS); u = u53(w.x, w.y); }
+        return gU[g] = u * (ub - lb) + lb;
+    };
+    md_eval_rows(P, L, N0, N0, D, draw, gNC, rng, tape ? tape + MBX_RLHPSDE_TAPE_NOISE_INIT(N0, D) : nullptr, MBX_SITE_NOISE1_A, MBX_SITE_NOISE1_B);
     // sort by (cost, row) and move the rows into buffer 0
-    const int npad = md_pad(N0);
-    for (int t = tid; t < npad; t += kThreads) { L.KEY[t] = t < N0 ? gNC[t] : INFINITY; L.IDX[t] = t; }
-    __syncthreads();
-    md_sort(L.KEY, L.IDX, npad);
     double* pop = S + MBX_RLHPSDE_ST_POP(N0, D);
-    const FastDiv fd(D);
-    for (int e = tid; e < N0 * D; e += kThreads) {
-        const int r = fd.div(e);
-        pop[e] = gU[min(L.IDX[r], N0 - 1) * D + (e - r * D)];            // (clamped: a NaN cost sorts behind the padding)
-    }
+    md_init_sorted(L, gU, gNC, pop, S + MBX_RLHPSDE_ST_COST(N0, D), N0, D);
     for (int t = tid; t < N0; t += kThreads) {
-        S[MBX_RLHPSDE_ST_COST(N0, D) + t] = L.KEY[t];
         S[MBX_RLHPSDE_ST_F(N0, D) + t] = 0.;
         S[MBX_RLHPSDE_ST_CR(N0, D) + t] = 0.;
         S[MBX_RLHPSDE_ST_Z(N0, D) + t] = 0.;
@@ -361,65 +339,25 @@ __device__ __forceinline__ void hp_steps(const BatchParams& bp, const int32_t* _
         }
         __syncthreads();
         // ---- evaluation of the trials in row chunks
-        for (int c0 = 0; c0 < NP; c0 += CH) {
-            const int n = min(CH, NP - c0);
-            for (int e = tid; e < n * D; e += kThreads) L.EV[e] = gU[(int64_t)c0 * D + e];
-            __syncthreads();
-            population_costs(P, L.eval(n, D, L.TC), n, rng, tape ? tape + MBX_RLHPSDE_TAPE_NOISE(N0, D) : nullptr, MBX_SITE_HP_NOISE_A,
-                             MBX_SITE_HP_NOISE_B, c0, N0);
-            if (tid < n) gNC[c0 + tid] = L.TC[tid];
-            __syncthreads();
-        }
+        md_eval_rows(P, L, NP, N0, D, [&](int e) { return gU[e]; }, gNC, rng, tape ? tape + MBX_RLHPSDE_TAPE_NOISE(N0, D) : nullptr, MBX_SITE_HP_NOISE_A,
+                     MBX_SITE_HP_NOISE_B);
         // ---- selection (:259): ranks of the improved rows
-        int ocnt[3] = {0, 0, 0}, obase[3], otot[3];
-        for (int i = row0; i < row1; ++i) ocnt[0] += gNC[i] < gC[i];
-        md_scan3(L.CNT, ocnt, obase, otot);
-        const int n_opt = otot[0];
+        int obase, n_opt;
+        md_rank_improved(L, gC, gNC, row0, row1, obase, n_opt);
         // ---- memory (:70-87): weighted Lehmer means over the improved rows, compacted in rank order, numpy's pairwise sums
         double newMF = 0.5, newMCr = 0.5;
         if (n_opt > 0) {
             // pass 0: df;  1: w SF;  2: w SF^2;  3: w SCr;  4: w SCr^2
             double sums[5];
-            for (int pass = 0; pass < 5; ++pass) {
-                int k = obase[0];
-                for (int i = row0; i < row1; ++i) {
-                    const double c = gC[i], nc = gNC[i];
-                    if (nc < c) {
-                        const double df = fmax(0., c - nc);
-                        double v = df;
-                        if (pass > 0) {
-                            const double w = df / sums[0], s = pass <= 2 ? gF[i] : gCr[i];
-                            v = (pass & 1) ? w * s : w * (s * s);
-                        }
-                        L.VEC[k++] = v;
-                    }
-                }
-                __syncthreads();
-                if (tid == 0) L.RED[0] = md_pairwise(L.VEC, n_opt);
-                __syncthreads();
-                sums[pass] = L.RED[0];
-                __syncthreads();
-            }
+            md_weighted_sums(L, gC, gNC, row0, row1, obase, n_opt, [](double c, double nc) { return fmax(0., c - nc); },
+                             [&](int pass, double w, int i) { const double s = pass <= 2 ? gF[i] : gCr[i]; return (pass & 1) ? w * s : w * (s * s); }, sums);
             newMF = sums[1] > 0.000001 ? sums[2] / sums[1] : 0.5;
             newMCr = sums[3] > 0.000001 ? sums[4] / sums[3] : 0.5;
         }
         // ---- replacement, LPSR, sort (:265-271, :90-98): rows into the other buffer in (cost, row) order
         const double fes = fes0 + NP;
-        const int NPn = min(hp_np_at(N0, fes, mf), NP), npad = md_pad(NP);
-        for (int t = tid; t < npad; t += kThreads) {
-            double key = INFINITY;
-            if (t < NP) { const double c = gC[t], nc = gNC[t]; key = nc < c ? nc : c; }
-            L.KEY[t] = key; L.IDX[t] = t;
-        }
-        __syncthreads();
-        md_sort(L.KEY, L.IDX, npad);
-        const FastDiv fd(D);
-        for (int e = tid; e < NPn * D; e += kThreads) {
-            const int r = fd.div(e), d = e - r * D, p = min(L.IDX[r], NP - 1);          // (clamped: a NaN cost sorts behind the padding)
-            npop[e] = gNC[p] < gC[p] ? gU[(int64_t)p * D + d] : pop[(int64_t)p * D + d];
-        }
-        __syncthreads();
-        for (int t = tid; t < NPn; t += kThreads) gC[t] = L.KEY[t];
+        const int NPn = min(hp_np_at(N0, fes, mf), NP);
+        md_replace_sorted(L, gC, gNC, gU, pop, npop, NP, NPn, D);
         // ---- bookkeeping (:273-286)
         if (tid == 0) {
             const double gbest = L.KEY[0], reward = (double)n_opt / (double)NP;

@@ -4,9 +4,6 @@
 #include <cmath>
 #include "mbx_device.hpp"
 #include "mbx_rlepso.hpp"
-#ifndef MBX_SINGLE_TU
-#define MBX_MADDE_PIECES_ONLY             // MadDE's device pieces without its kernels, which mbx.hip defines
-#endif
 #include "mbx_nlshade.hpp"
 #include "mbx_run_kernels.hpp"
 

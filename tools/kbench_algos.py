@@ -197,7 +197,8 @@ if 'madde' in which:
     # round-robin, 4096 instances at D = 10 and 256 at D = 30 (2.3 MB of state each), a budget so large that NP stays at its start
     # value and every instance stays live.  Under rocprofv3 --kernel-trace --stats the per-launch times of k_madde_generation and
     # k_rs_population come from the trace; the wall times here include the launch gaps.  A library built with -DMBX_ABLATE_MD_SORT /
-    # -DMBX_ABLATE_MD_ARC / -DMBX_ABLATE_MD_SUMS (MBX_LIB) gives the step without the sort and row move / the archive update / the pairwise sums.
+    # -DMBX_ABLATE_MD_ARC / -DMBX_ABLATE_MD_SUMS (MBX_LIB) gives the step without the sort and row move / the archive update / the pairwise sums
+    # (the sort and row move are shared code, mbx_depop.hpp: that switch takes them out of the NL_SHADE_LBC and RL-HPSDE kernels of such a build as well).
     from metabox_amd._abi import ALGO_MADDE, ALGO_RANDOM_SEARCH
     from metabox_amd.suite import Batch, Suite
     for dim, B in ((10, 4096), (30, 256)):
