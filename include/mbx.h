@@ -126,7 +126,7 @@ typedef struct mbx_algo_cfg {
     int32_t log_interval;  /* config.log_interval (src/config.py:102)                             */
     int32_t n_logpoint;    /* config.n_logpoint   (src/config.py:77,90)                           */
     int32_t early_stop;    /* 1 = reference rule `done = fes>=maxFEs or gbest<=1e-8`; 0 = fixed horizon (SDMSPSO: no effect, the reference has no early stop there) */
-    int32_t n_group;       /* RLEPSO: 5 (rlepso_optimizer.py:26)                                  */
+    int32_t n_group;       /* RLEPSO: 5 (rlepso_optimizer.py:26); 1 .. 7, np / n_group >= 1        */
     uint32_t flags;        /* MBX_F_* below, OR-ed; 0 = the defaults.  Per batch: two batches of one process may differ. */
 } mbx_algo_cfg;
 

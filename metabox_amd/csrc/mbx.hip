@@ -633,6 +633,9 @@ static int rlepso_check(const mbx_algo_cfg& c)
     if (int rc = check_np(c)) return rc;
     if (int rc = check_dim(c)) return rc;
     if (c.n_group < 1 || c.n_group > 16 || c.np / c.n_group < 1) return fail(MBX_E_ARG, "bad n_group %d", c.n_group);
+    // group g reads actions[g * n_group : g * n_group + 7] (rlepso_optimizer.py:119): inside the 7 * n_group action row only while
+    // (n_group - 1) * n_group + 7 <= 7 * n_group, i.e. up to seven groups; beyond that the reference itself fails on the short slice
+    if (c.n_group > 7) return fail(MBX_E_ARG, "n_group %d: the reference's action slice [g * n_group, g * n_group + 7) is short beyond 7 groups", c.n_group);
     return MBX_OK;
 }
 

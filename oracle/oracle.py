@@ -99,6 +99,9 @@ class RlepsoOracle:
         self.cfg = cfg
         self._h = lib().orc_rlepso_new(C.byref(self._st), float('nan') if optimum is None else float(optimum),
                                        C.byref(cfg), int(seed))
+        if not self._h:
+            raise ValueError(f'RLEPSO oracle: n_group {cfg.n_group} with np {cfg.np} is refused (1 .. 7 groups of at least one particle: group g reads '
+                             f'action[g * n_group : g * n_group + 7], which ends inside the 7 * n_group row up to seven groups only)')
 
     def __del__(self):
         if getattr(self, '_h', None):
@@ -110,6 +113,7 @@ class RlepsoOracle:
 
     def step(self, action, tape=None):
         a = np.ascontiguousarray(action, dtype=np.float32)
+        assert a.size == 7 * self.cfg.n_group, (a.shape, self.cfg.n_group)         # orc_rlepso_step reads that many floats
         out = np.empty(3)
         lib().orc_rlepso_step(self._h, a.ctypes.data_as(C.POINTER(C.c_float)),
                               _p(tape) if tape is not None else None, _p(out))

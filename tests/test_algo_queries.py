@@ -29,6 +29,9 @@ def cases():
             out[f'grid-{algo}-{np_}-{dim}'] = _cfg(algo, np_, dim)
     out['rlepso-n_group-0'] = _cfg(RLEPSO, 100, 10, n_group=0)
     out['rlepso-n_group-17'] = _cfg(RLEPSO, 100, 10, n_group=17)
+    out['rlepso-n_group-7'] = _cfg(RLEPSO, 100, 10, n_group=7)         # the last group count whose action slices [g * n_group, g * n_group + 7) end inside the row
+    out['rlepso-n_group-8'] = _cfg(RLEPSO, 100, 10, n_group=8)
+    out['rlepso-n_group-16'] = _cfg(RLEPSO, 100, 10, n_group=16)
     out['sdmspso-max_fes-np'] = _cfg(SDMSPSO, 99, 10, max_fes=99)
     out['sahlpso-max_fes-np'] = _cfg(SAHLPSO, 40, 10, max_fes=40)
     out['les-max_fes-np'] = _cfg(LES, 16, 10, max_fes=16)
@@ -80,7 +83,11 @@ def test_the_examples_of_the_record():
     assert want['grid-12-100-10'][:3] == [-3, -3, -3]
     assert want['madde-np-wrong-and-dim-65'][3].startswith('MadDE runs dim in [2, ')
     assert 'quasi-Newton' in want['sdmspso-quasi-newton-generation'][3] and want['sdmspso-last-budget-before-quasi-newton'][3] == ''
-    assert len(want) == 24 * len(SHAPES) + 12
+    assert want['rlepso-n_group-7'] == [1, 49, 6900, '']
+    for n in (8, 16):                                     # the last group of eight would read actions 56 .. 62 of 56, the last of sixteen 240 .. 246 of 112
+        assert want[f'rlepso-n_group-{n}'][:3] == [-1, -1, -1] and 'slice' in want[f'rlepso-n_group-{n}'][3], want[f'rlepso-n_group-{n}']
+    assert want['rlepso-n_group-0'] == [-1, -1, -1, 'bad n_group 0'] and want['rlepso-n_group-17'] == [-1, -1, -1, 'bad n_group 17']
+    assert len(want) == 24 * len(SHAPES) + 15
 
 
 if __name__ == '__main__':

@@ -2,14 +2,19 @@
 register tile of the matvec against its one-element loop), odd row counts, the align2 padding of the LDS arrays, a padded state stride (NP D odd), particles across the
 63 / 64 / 65 wave boundary and at 255 / 256, k_lde_step<256> against <512> -- and at budgets that do not divide: max_fes = 3 NP + 17, five log points.  The comparison
 is parity.compare, the one the canonical `*_philox_parity_with_oracle` tests make, plus done / fes / cost_len / curve after every step.  Then every state word of an
-instance alone, inside a batch and inside the permuted batch, and the fused routes against one launch per step, at the same shapes."""
+instance alone, inside a batch and inside the permuted batch, and the fused routes against one launch per step, at the same shapes.
+
+RLEPSO, whose kernels branch on geometry most, has a sweep of its own (parity.RLEPSO_SHAPES: swarm size, dimension AND group count): the ranking's slices of j
+(MBX_NT / NP = 1, 2, 3, ..), the move phase's tables inside Z up to the last rank a byte holds (NP = 256), the 512- and 1024-thread instantiations at D = 2 x waves
+and at odd D with NP off a wave boundary, NP % n_group != 0 and n_group = 1, 3, 7; whole episodes of 12 NP + 17 evaluations; then __reinit, planted on both sides, at
+the same shapes.  What the oracle alone must show there runs without a GPU too (tests/test_rlepso_edge_conditions.py)."""
 import numpy as np
 import pytest
 import torch
 
 import parity
 import policy_exact as pe
-from helpers import load, print_ledger, problems
+from helpers import load, print_ledger
 
 pytestmark = pytest.mark.gpu
 
@@ -17,12 +22,14 @@ ALGOS = ('lde', 'gleet', 'rlpso', 'qlpso', 'de', 'pso')
 SHAPES = [(4, 2), (5, 3), (63, 7), (64, 10), (65, 33), (100, 40), (255, 13), (256, 10)]
 NLOG = 5
 OVER_LONG = (4, 2, 45, 2, 5)               # (NP, D, max_fes, log_interval, n_logpoint): at least three entries too long for every algorithm (tests/test_curve_bound.py)
+OVER_LONG_RLEPSO = (5, 2, 45, 2, 5)        # NP = 4 is refused with five groups; nine entries in six slots (tests/test_rlepso_edge_conditions.py)
+RLEPSO_SHAPES = sorted(parity.RLEPSO_SHAPES)
 MBX_E_UNSUPPORTED = -3
 
 
 def _problems(D):
     """Nine instances: bbob 1, 3, 10, 15, 17, 21 and one noisy function per noise model."""
-    return [problems('bbob', D)[f] for f in (1, 3, 10, 15, 17, 21)] + [problems('bbob-noisy', D)[f] for f in (101, 117, 130)]
+    return parity.edge_problems(D)
 
 
 def _budget(NP):
@@ -75,6 +82,62 @@ def test_lde_sweep_covers_both_workgroup_sizes():
     assert threads == {256, 512}, threads
 
 
+# ------------------------------------------------------------------------------------------------ RLEPSO: edge swarm sizes and group counts
+@pytest.mark.parametrize('NP,D,n_group', RLEPSO_SHAPES)
+def test_rlepso_matches_the_oracle_at_edge_swarm_sizes_and_groups(NP, D, n_group):
+    """k_rlepso_step with run-time geometry, whole episodes (12 NP + 17 evaluations, five log points) of the nine instances against one oracle each: the ranking's
+    slices, the move phase's tables inside Z, the 256 / 512 / 1024-thread instantiations, NP % n_group != 0, n_group = 1, 3, 7."""
+    ledger = []
+    total, info, got, _ = parity.hip_vs_oracle('rlepso', _problems(D), NP, D, parity.rlepso_edge_budget(NP), parity.RLEPSO_STEPS, ledger,
+                                               oracle_check=parity.rlepso_fits_and_ends, n_group=n_group)
+    assert info['fixed_geometry'] == 0 and info['threads'] == parity.RLEPSO_SHAPES[(NP, D, n_group)], info
+    assert all(rec['done'][-1] for rec in got)
+    _report(f'rlepso g{n_group}', NP, D, total, ledger)
+
+
+def test_rlepso_sweep_covers_the_three_workgroup_sizes():
+    from metabox_amd.suite import Batch, Suite
+    threads = set()
+    for NP, D, n_group in RLEPSO_SHAPES:
+        s = Suite(_problems(D))
+        b = Batch(s, parity.ALGO['rlepso'], np.arange(9), parity.seeds_for('rlepso', 9), NP, *parity.rlepso_edge_budget(NP), n_group=n_group)
+        info = b.launch_info()
+        assert info['fixed_geometry'] == 0 and info['threads'] == parity.RLEPSO_SHAPES[(NP, D, n_group)], (NP, D, n_group, info)
+        threads.add(info['threads'])
+        b.close(); s.close()
+    assert threads == {256, 512, 1024}, threads
+
+
+@pytest.mark.parametrize('NP,D,n_group', RLEPSO_SHAPES)
+def test_rlepso_reinit_matches_the_oracle_at_edge_swarm_sizes_and_groups(NP, D, n_group):
+    """__reinit at the same shapes.  Twelve generations of random actions do not reach it, so it is planted on both sides: after reset() every other stagnation counter
+    of the kernel's own state block is set to 100, the block is written back and handed to the oracle, and the actions put c_mutation = 0.01 into every group.  First,
+    on the oracle alone: a noisy instance bills more than NP evaluations in some generation.  Then the comparison of the sweep above, with the __reinit flag and fes exact.
+    (Where NP % n_group != 0 the particles without coefficients do not move: the oracle re-evaluates the position whose cost it was handed in the kernel's words, so on
+    a noise-free function `new_cost < c_cost` is decided by the last bits of two evaluations of the same point -- a proven near-tie at generation 0 that ends that
+    instance's comparison and is printed with the ledger.  The noisy instances, whose costs are redrawn, go through; `compared` insists on one.)"""
+    ps = _problems(D)
+
+    def bills(want):
+        parity.rlepso_reinit_bills(want, NP, ps)
+        assert all(rec['done'][-1] for rec in want) and max(v['sc']['cost_len'] for rec in want for v in rec['views']) <= NLOG + 1
+    ledger = []
+    total, info, got, want = parity.hip_vs_oracle('rlepso', ps, NP, D, parity.rlepso_edge_budget(NP), parity.RLEPSO_STEPS, ledger, oracle_check=bills, n_group=n_group,
+                                                  actions=parity.rlepso_reinit_actions(9, n_group), start=parity.rlepso_stagnant(NP, D))
+    assert info['fixed_geometry'] == 0, info
+    fired = parity.rlepso_reinit_bills(want, NP, ps)                 # the oracles that started from the kernel's own blocks
+    cut = {}                                                        # instance -> the generation at which a proven near-tie ended its comparison
+    for _, case, g0, _ in ledger:
+        if ' pni' in case or ' done' in case:
+            k = int(case.split('#')[1].split()[0])
+            cut[k] = min(g0, cut.get(k, g0))
+    compared = [(k, g) for k, g in fired if g < cut.get(k, parity.RLEPSO_STEPS)]
+    assert compared, (fired, ledger)                                # at least one re-initialising generation of a noisy instance went through the whole comparison
+    for k, g in compared:
+        assert got[k]['views'][g + 1]['sc']['reinit'] and got[k]['views'][g + 1]['sc']['fes'] == want[k]['views'][g + 1]['sc']['fes'] > got[k]['views'][g]['sc']['fes'] + NP
+    _report(f'rlepso g{n_group} reinit', NP, D, total, ledger)
+
+
 @pytest.mark.parametrize('name', ALGOS)
 def test_np256_dim64_is_refused_before_any_launch(name):
     """NE + SC alone is 256 KB at (256, 64)."""
@@ -88,11 +151,11 @@ def test_np256_dim64_is_refused_before_any_launch(name):
     s.close()
 
 
-@pytest.mark.parametrize('name', ALGOS)
+@pytest.mark.parametrize('name', ALGOS + ('rlepso',))
 def test_over_long_curve_keeps_to_its_slots(name):
     """A budget whose reference list outgrows n_logpoint + 1: the kernel reports the oracle's true length and stored entries, and every instance of the batch still
     matches its own oracle -- an append past the slots would land in the first words (a position) of the next instance."""
-    NP, D, max_fes, li, nlog = OVER_LONG
+    NP, D, max_fes, li, nlog = OVER_LONG_RLEPSO if name == 'rlepso' else OVER_LONG
 
     def outgrows(want):
         assert all(rec['done'][-1] and rec['views'][-1]['sc']['cost_len'] >= nlog + 4 for rec in want), name
@@ -121,7 +184,7 @@ def _run_states(name, ps, slots, NP, steps):
 
 
 @pytest.mark.parametrize('NP,D', [(63, 7), (65, 33)])
-@pytest.mark.parametrize('name', ALGOS + ('rs',))
+@pytest.mark.parametrize('name', ALGOS + ('rs', 'rlepso'))
 def test_state_words_do_not_depend_on_the_batch(name, NP, D):
     """NP D odd: the state stride is padded.  An instance alone, in the nine-instance batch and in that batch permuted: the same words."""
     ps = _problems(D)
@@ -176,6 +239,34 @@ def test_rlpso_fused_rollout_equals_policy_plus_step(NP, D):
     _same(a, b)
     ret = a.results()['return']
     assert torch.allclose(ret_a, ret, rtol=1e-12, atol=1e-12) and torch.allclose(ret_b, ret, rtol=1e-12, atol=1e-12) and bool((a.results()['fes'] == max_fes).all())
+    a.close(); b.close(); s.close()
+
+
+@pytest.mark.parametrize('NP,D', [(63, 7), (7, 3), (255, 17)])
+def test_rlepso_rollout_host_loop_equals_one_act_step_per_generation(NP, D):
+    """mbx_rlepso_rollout on its host-loop route (no resident kernel is built for these geometries) in chunks of 1, 5 and the rest past the end of every episode ==
+    one mbx_rlepso_act_step per generation on a twin batch, with a seeded actor table (sigma 0.05 .. 0.35): trajectory records, results and every state word."""
+    max_fes, li, nlog = parity.rlepso_edge_budget(NP)
+    s, a, b = _twins('rlepso', NP, D, max_fes, li, nlog)
+    assert not a.rollout_is_resident() and a.launch_info()['fixed_geometry'] == 0
+    rows = int(a.lib.mbx_rlepso_policy_table_rows(a._h))
+    table = torch.rand(rows, 2, 35, generator=torch.Generator().manual_seed(1000 + 14 * D + NP)).cuda()
+    table[:, 1] = 0.05 + 0.3 * table[:, 1]
+    table = table.contiguous()
+    for chunk in (1, 5, parity.RLEPSO_STEPS - 6 + 3):
+        st, rw, dn, traj = a.rlepso_rollout(table, chunk, trajectory=True)
+        st, rw, dn = st.clone(), rw.clone(), dn.clone()
+        rsum = torch.zeros(9, dtype=torch.float64, device='cuda')
+        for g in range(chunk):
+            live = (b.done == 0).clone()
+            sb, rb, db, acts = b.act_step(table, want_actions=True)
+            assert torch.equal(traj['state'][g], sb[:, 0]) and torch.equal(traj['reward'][g], rb) and torch.equal(traj['done'][g], db), g
+            assert torch.equal(traj['actions'][g][live], acts[live]), g
+            rsum += rb
+        assert torch.equal(st[:, 0], sb[:, 0]) and torch.equal(dn, db) and torch.equal(rw, rsum)
+        _same(a, b)
+    res = a.results()
+    assert bool((a.done == 1).all()) and bool((res['steps'] <= 15).all()) and bool((res['fes'] >= max_fes).any()), res       # the last launch went on past every episode's end
     a.close(); b.close(); s.close()
 
 

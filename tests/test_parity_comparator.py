@@ -1,12 +1,13 @@
 """parity.compare can fail: the oracle against a copy of itself passes with deviation 0, and the same copy with one planted defect is rejected, for each of the
-six algorithms the geometry sweep covers (CPU only: no deliberately wrong kernel is built)."""
+algorithms the geometry sweep covers (CPU only: no deliberately wrong kernel is built).  RLEPSO, whose comparison runs generation by generation, also gets a stagnation
+counter that is off without a near-tie behind it and a wrong __reinit flag."""
 import numpy as np
 import pytest
 
 import parity
 from helpers import problems
 
-ALGOS = ('lde', 'gleet', 'rlpso', 'qlpso', 'de', 'pso')
+ALGOS = ('rlepso', 'lde', 'gleet', 'rlpso', 'qlpso', 'de', 'pso')
 DEFECTS = ('coordinate', 'pbest', 'cost_len', 'curve')
 NP, D = 5, 3
 BUDGET = (3 * NP + 17, (3 * NP + 17) // 5, 5)
@@ -33,3 +34,11 @@ def test_comparator_accepts_the_oracle_and_rejects_every_planted_defect(name):
         for k, bad in planted:
             with pytest.raises(AssertionError):
                 parity.compare(name, bad, recs[k], f'{name} #{k} {defect}', ledger=[])
+
+
+@pytest.mark.parametrize('defect', ['pni', 'reinit', 'fes'])
+def test_comparator_rejects_rlepso_bookkeeping_defects(defect):
+    for k, rec in enumerate(_records('rlepso')):
+        bad = parity.plant(rec, defect)
+        with pytest.raises(AssertionError):
+            parity.compare('rlepso', bad, rec, f'rlepso #{k} {defect}', ledger=[])
