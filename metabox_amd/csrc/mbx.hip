@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "mbx_device.hpp"
+#include "mbx_lds.hpp"
 #include "mbx_rlepso.hpp"
 #include "mbx_lde.hpp"
 #ifndef MBX_LDE100_STEP_THREADS
@@ -187,11 +188,7 @@ __global__ __launch_bounds__(kThreads) void k_eval(const DevProblem* problems, i
     }
 }
 
-static size_t eval_lds_bytes(int rows, int D)
-{
-    const int64_t NE = align2((int64_t)rows * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D);
-    return (size_t)(NE + eval_t_doubles(rows, D) + SC + 2 * DD + 4 * align2(D) + align2(rows)) * sizeof(double);
-}
+static size_t eval_lds_bytes(int rows, int D) { return (size_t)ev_lds_doubles(rows, D) * sizeof(double); }
 
 __global__ void k_init_state(double* state, int64_t stride, int64_t sc_off, int B)
 {
@@ -843,7 +840,7 @@ static int dedqn_check(const mbx_algo_cfg& c)
     return MBX_OK;
 }
 
-static AlgoGeom dedqn_geom(const mbx_algo_cfg& c) { return MBX_GEOM(DEDQN, dedqn_lds_doubles(c.np, c.dim), MBX_DEDQN_NFEAT, 1); }
+static AlgoGeom dedqn_geom(const mbx_algo_cfg& c) { return MBX_GEOM(DEDQN, dd_lds_doubles(c.np, c.dim), MBX_DEDQN_NFEAT, 1); }
 static int dedqn_prepare_batch(mbx_batch* b, const AlgoGeom& g)
 {
     HIP_TRY(dedqn_prepare(lds_of(g)));
@@ -871,8 +868,8 @@ static int nrlpso_check(const mbx_algo_cfg& c)
 static AlgoGeom nrlpso_geom(const mbx_algo_cfg& c)
 {
     // the larger of the reset's carve-up (NP evaluation rows) and the step's (one row, the resident arrays, the distance matrix where it is kept)
-    return MBX_GEOM(NRLPSO, std::max(nrlpso_lds_doubles(c.np, c.dim, false, false),
-                                     nrlpso_lds_doubles(c.np, c.dim, true, nrlpso_cached(c.np, c.dim, c.flags, (size_t)max_lds_bytes()))), 1, 1);
+    return MBX_GEOM(NRLPSO, std::max(nr_lds_doubles(c.np, c.np, c.dim, false, false),
+                                     nr_lds_doubles(1, c.np, c.dim, true, nrlpso_cached(c.np, c.dim, c.flags, (size_t)max_lds_bytes()))), 1, 1);
 }
 
 static int nrlpso_prepare_batch(mbx_batch* b, const AlgoGeom& g)
@@ -886,7 +883,7 @@ MBX_RESET_FN(nrlpso_reset) { nrlpso_launch_reset(make_params(b), stream, d_state
 MBX_STEP_FN(nrlpso_step) { nrlpso_launch_steps(make_params(b), b->nrlpso_cached, stream, (const int32_t*)d_actions, nullptr, 1, nullptr, nullptr, nullptr, nullptr, MBX_OUT); return MBX_OK; }
 
 // the step kernels' LDS (the reset's carve-up is smaller at np = 100)
-static void nrlpso_launch_info(const mbx_batch* b, int32_t out[4]) { out[1] = (int32_t)(nrlpso_lds_doubles(b->cfg.np, b->cfg.dim, true, b->nrlpso_cached) * sizeof(double)); }
+static void nrlpso_launch_info(const mbx_batch* b, int32_t out[4]) { out[1] = (int32_t)(nr_lds_doubles(1, b->cfg.np, b->cfg.dim, true, b->nrlpso_cached) * sizeof(double)); }
 
 // ---- SAHLPSO: mbx_run_sahlpso.hip
 static int sahlpso_check(const mbx_algo_cfg& c)
@@ -898,7 +895,7 @@ static int sahlpso_check(const mbx_algo_cfg& c)
     return MBX_OK;
 }
 
-static AlgoGeom sahlpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(SAHL, sahlpso_lds_doubles(c.dim), 1, 0); }
+static AlgoGeom sahlpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(SAHL, std::max(sh_lds_doubles(MBX_SAHL_NP, c.dim, false), sh_lds_doubles(1, c.dim, true)), 1, 0); }
 static int sahlpso_prepare_batch(mbx_batch*, const AlgoGeom& g) { HIP_TRY(sahlpso_prepare(lds_of(g))); return MBX_OK; }
 MBX_RESET_FN(sahlpso_reset) { sahlpso_launch_reset(make_params(b), stream, d_state_out); }
 MBX_STEP_FN(sahlpso_step) { sahlpso_launch_generation(make_params(b), stream, MBX_OUT); return MBX_OK; }
@@ -916,7 +913,7 @@ static int les_check(const mbx_algo_cfg& c)
 static AlgoGeom les_geom(const mbx_algo_cfg& c)
 {
     return AlgoGeom{MBX_LES_STATE_DOUBLES(c.np, c.dim, MBX_LES_CURVE_CAP(c.max_fes, c.log_interval, c.n_logpoint)), MBX_LES_ST_SCALARS(c.np, c.dim),
-                    MBX_LES_TAPE_STRIDE(c.np, c.dim), les_lds_doubles_of(c.dim), 1, 0};
+                    MBX_LES_TAPE_STRIDE(c.np, c.dim), les_lds_doubles(c.dim), 1, 0};
 }
 
 static int les_prepare_batch(mbx_batch* b, const AlgoGeom& g)
@@ -948,7 +945,7 @@ static int rlhpsde_check(const mbx_algo_cfg& c)
     return MBX_OK;
 }
 
-static AlgoGeom rlhpsde_geom(const mbx_algo_cfg& c) { return MBX_GEOM(RLHPSDE, rlhpsde_lds_doubles(c.np, c.dim), 1, 1); }
+static AlgoGeom rlhpsde_geom(const mbx_algo_cfg& c) { return MBX_GEOM(RLHPSDE, hp_lds_doubles(c.np, c.dim), 1, 1); }
 static int rlhpsde_prepare_batch(mbx_batch* b, const AlgoGeom& g)
 {
     HIP_TRY(rlhpsde_prepare(lds_of(g)));
@@ -974,7 +971,7 @@ static int nlshade_check(const mbx_algo_cfg& c)
     return MBX_OK;
 }
 
-static AlgoGeom nlshade_geom(const mbx_algo_cfg& c) { return MBX_GEOM(NLSHADE, nlshade_lds_doubles(c.np, c.dim), 1, 0); }
+static AlgoGeom nlshade_geom(const mbx_algo_cfg& c) { return MBX_GEOM(NLSHADE, nl_lds_doubles(c.np, c.dim), 1, 0); }
 static int nlshade_prepare_batch(mbx_batch* b, const AlgoGeom& g)
 {
     HIP_TRY(nlshade_prepare(lds_of(g)));

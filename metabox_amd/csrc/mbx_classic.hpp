@@ -9,42 +9,12 @@
 // instance; the sequential part of a step is the evaluator's single-row path, as in mbx_rlpso.hpp.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2, log_and_terminate
+#include "mbx_rlepso.hpp"   // BatchParams, log_and_terminate
+#include "mbx_lds.hpp"
 
 namespace mbx {
-// four waves per SIMD: left alone the compiler takes 126-160 VGPRs for the multi-step / sweep kernels (three resident workgroups per CU
-// although the LDS would hold five); capped at 128 they spill little or nothing (QLPSO rollout 82 -> 69 us, RL-PSO rollout 60 -> 53 us per step)
-#ifndef MBX_N4_WAVES
-#define MBX_N4_WAVES __attribute__((amdgpu_waves_per_eu(4)))
-#endif
 
-struct ClLds {
-    double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *POP, *COST, *GB, *SC, *C, *B, *VEC;
-    int* ORD;
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
-};
-
-// rows: evaluation rows of the launch; pop: 1 if the population is kept in LDS (DE sweeps); cma: 1 for the CMA-ES matrices
-__host__ __device__ inline int64_t cl_lds_doubles(int rows, int NP, int D, int pop, int cma)
-{
-    const int64_t NE = align2((int64_t)rows * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    return NE + eval_t_doubles(rows, D) + SC + 2 * DD + 5 * align2(D) + align2(rows) + 32 + MBX_NSCALAR + P + align2((P + 1) / 2) +
-           (pop ? align2((int64_t)NP * D) : 0) + (cma ? 3 * DD + 8 * align2(D) + P : 0);
-}
-
-__device__ __forceinline__ ClLds cl_carve(double* base, int rows, int NP, int D, int pop, int cma)
-{
-    const int64_t NE = align2((int64_t)rows * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    ClLds L;
-    double* p = base;
-    L.X = p; p += NE;  L.T = p; p += eval_t_doubles(rows, D);  L.Z = p; p += SC;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);  L.GB = p; p += align2(D);
-    L.NC = p; p += align2(rows);  L.RED = p; p += 32;  L.SC = p; p += MBX_NSCALAR;  L.COST = p; p += P;
-    L.ORD = reinterpret_cast<int*>(p); p += align2((P + 1) / 2);
-    L.POP = p; p += pop ? align2((int64_t)NP * D) : 0;
-    L.C = p; L.B = p + DD; L.VEC = p + 3 * DD;                        // only valid when cma (C, B, Jacobi work matrix, vectors, weights)
-    return L;
-}
+// The LDS layout (ClLds, cl_lds_doubles, cl_carve) and MBX_N4_WAVES live in mbx_lds.hpp.
 
 // single-row cost of the point in L.X[0..D): objective, noise (Philox row `row`), optimum.  Thread 0 gets the value.
 __device__ __forceinline__ double cl_cost1(const DevProblem& P, const ClLds& L, const Rng& rng, uint32_t row)

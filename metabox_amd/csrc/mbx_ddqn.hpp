@@ -7,40 +7,12 @@
 // next decision.  One workgroup per instance; the records live in HBM and are staged through LDS.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams
+#include "mbx_lds.hpp"
 
 namespace mbx {
 
-struct DqLds {
-    double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *COST, *REC, *FEAT, *RED, *MISC;
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
-    // REC: N_tot[40] | N_succ[160] | OM_sum[160] | OM_max[160] | OM_W[300]
-    __device__ __forceinline__ double* ntot() const { return REC; }
-    __device__ __forceinline__ double* nsucc() const { return REC + 40; }
-    __device__ __forceinline__ double* omsum() const { return REC + 200; }
-    __device__ __forceinline__ double* ommax() const { return REC + 360; }
-    __device__ __forceinline__ double* omw() const { return REC + 520; }
-};
-constexpr int kDqRec = 820;
-
-// rows: how many candidates the evaluator sees at once -- NP in k_dq_reset, ONE in k_dq_step (a step evaluates a single trial vector:
-// 17.9 KB instead of 40.9 KB at NP = 100, D = 12, so the register budget, not the LDS, decides how many workgroups share a CU)
-__host__ __device__ inline int64_t dq_lds_doubles(int rows, int NP, int D)
-{
-    const int64_t NE = align2((int64_t)rows * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    return NE + eval_t_doubles(rows, D) + SC + 2 * DD + 4 * align2(D) + 2 * P + kDqRec + 100 + 16 + 16 + 2 * align2(D);
-}
-
-__device__ __forceinline__ DqLds dq_carve(double* base, int rows, int NP, int D)
-{
-    const int64_t NE = align2((int64_t)rows * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    DqLds L;
-    double* p = base;
-    L.X = p; p += NE;  L.T = p; p += eval_t_doubles(rows, D);  L.Z = p; p += SC;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);
-    L.NC = p; p += P;  L.COST = p; p += P;  L.REC = p; p += kDqRec;  L.FEAT = p; p += 100;  L.RED = p; p += 16;  L.MISC = p;
-    return L;
-}
+// The LDS layout (DqLds, kDqRec, dq_lds_doubles, dq_carve) lives in mbx_lds.hpp.
 
 __device__ __forceinline__ int dq_slot(int g, int gen) { return (((g - gen) % MBX_DQ_GENMAX) + MBX_DQ_GENMAX) % MBX_DQ_GENMAX; }
 

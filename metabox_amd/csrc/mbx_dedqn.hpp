@@ -20,7 +20,8 @@
 // order (mbx_npsum.hpp); sums that the reference writes as Python loops are sequential on one lane.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2, log_and_terminate
+#include "mbx_rlepso.hpp"   // BatchParams, log_and_terminate
+#include "mbx_lds.hpp"
 #include "mbx_npsum.hpp"
 
 namespace mbx {
@@ -32,33 +33,7 @@ constexpr int kDdRedrawMax = 1024;
 // per-step records of k_dedqn_run (each may be nullptr) and the last action of every instance
 struct DedqnTraj { int32_t* actions; double* state; double* reward; int32_t* last_action; };
 
-struct DdLds {
-    double *POP, *T, *Z, *M1T, *M2T, *DSH, *V0, *V1, *V2, *TRIAL, *GB, *COST, *SURV, *SCOST, *DIST, *SORTED, *DIFF, *RED, *SC, *FEAT, *HS;
-    int *CNT, *IR;
-    __device__ __forceinline__ EvalLds eval(const double* x, double* f) const { return EvalLds{x, Z, T, M1T, M2T, DSH, V0, V1, V2, f}; }
-};
-
-// POP, Z (the evaluator's scratch, then the walk) and T: NP * D each -- 8 KB at NP = 100 / D = 10, 40 KB at NP = 128 / D = 40 (146 KB in all there)
-__host__ __device__ inline int64_t dd_lds_doubles(int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D), ZS = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    return NE + eval_t_doubles(NP, D) + ZS + 2 * DD + 6 * align2(D) + 6 * P + 32 + MBX_NSCALAR + MBX_DEDQN_FEAT_SLOTS + 10 + 64 + 4;
-}
-
-__device__ __forceinline__ DdLds dd_carve(double* base, int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D), ZS = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    DdLds L;
-    double* p = base;
-    L.POP = p; p += NE;  L.T = p; p += eval_t_doubles(NP, D);  L.Z = p; p += ZS;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);
-    L.TRIAL = p; p += align2(D);  L.GB = p; p += align2(D);
-    L.COST = p; p += P;  L.SURV = p; p += P;  L.SCOST = p; p += P;  L.DIST = p; p += P;  L.SORTED = p; p += P;  L.DIFF = p; p += P;
-    L.RED = p; p += 32;  L.SC = p; p += MBX_NSCALAR;  L.FEAT = p; p += MBX_DEDQN_FEAT_SLOTS;  L.HS = p; p += 10;
-    L.CNT = (int*)p; p += 64;                                       // two waves x (9 levels x 6 classes + the descent count)
-    L.IR = (int*)p;
-    return L;
-}
+// The LDS layout (DdLds, dd_lds_doubles, dd_carve) lives in mbx_lds.hpp.
 
 // __cal_feature (:130-142) for the population in L.POP: costs into L.SCOST, the four features and the diagnostics into L.FEAT.
 // tape_walk / tape_noise: the step's (or the reset's) slots of the replay tape, or nullptr.  All threads call; ends with a barrier.

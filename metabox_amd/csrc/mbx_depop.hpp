@@ -11,58 +11,11 @@
 // written out, because it measured slower through md_eval_rows / md_rank_improved / md_weighted_sums (docs/EXPERIMENTS.md).
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // align2
+#include "mbx_lds.hpp"
 
 namespace mbx {
 
-// rows per evaluation chunk
-__host__ __device__ inline int md_chunk(int D) { return D <= 12 ? 128 : D <= 30 ? 96 : 64; }
-__host__ __device__ inline int md_pad(int n) { int p = 2; while (p < n) p <<= 1; return p; }
-// LDS of one evaluation chunk of ch rows: X | T | Z
-__host__ __device__ inline int64_t md_ev_doubles(int ch, int D)
-{
-    const int64_t ne = (int64_t)ch * D;
-    return align2(ne) + eval_t_doubles(ch, D) + align2(ne > 2 * kThreads ? ne : 2 * kThreads);
-}
-__host__ __device__ inline int64_t md_win_doubles(int NP) { return align2((MBX_MADDE_ARC(NP) + 1) / 2); }
-// the area the phases of an update share: evaluation chunk | archive winners (int) + compacted vector | sort keys + rows (int)
-__host__ __device__ inline int64_t md_work_doubles(int NP, int D)
-{
-    const int64_t a = md_ev_doubles(md_chunk(D), D), b = md_win_doubles(NP) + align2(NP), c = md_pad(NP) + align2(md_pad(NP) / 2);
-    return a > b ? (a > c ? a : c) : (b > c ? b : c);
-}
-__host__ __device__ inline int64_t md_lds_doubles(int NP, int D)
-{
-    const int64_t DD = align2((int64_t)D * D);
-    return md_work_doubles(NP, D) + 2 * DD + 4 * align2(D) + align2(md_chunk(D)) + 16 + 2 * kThreads + align2((NP + 1) / 2) + align2((NP + 7) / 8);
-}
-
-struct MdLds {
-    double *EV, *M1T, *M2T, *DSH, *V0, *V1, *V2, *TC, *RED, *VEC, *KEY;
-    int *CNT, *LIST, *WIN, *IDX;
-    uint8_t* MU;
-    __device__ __forceinline__ EvalLds eval(int ch, int D, double* f) const
-    {
-        double* T = EV + align2((int64_t)ch * D);
-        return EvalLds{EV, T + eval_t_doubles(ch, D), T, M1T, M2T, DSH, V0, V1, V2, f};
-    }
-};
-
-__device__ __forceinline__ MdLds md_carve(double* base, int NP, int D)
-{
-    const int64_t DD = align2((int64_t)D * D);
-    MdLds L;
-    double* p = base;
-    L.EV = p; L.WIN = reinterpret_cast<int*>(p); L.VEC = p + md_win_doubles(NP); L.KEY = p; L.IDX = reinterpret_cast<int*>(p + md_pad(NP));
-    p += md_work_doubles(NP, D);
-    L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);
-    L.TC = p; p += align2(md_chunk(D));  L.RED = p; p += 16;
-    L.CNT = reinterpret_cast<int*>(p); p += 2 * kThreads;
-    L.LIST = reinterpret_cast<int*>(p); p += align2((NP + 1) / 2);
-    L.MU = reinterpret_cast<uint8_t*>(p);
-    return L;
-}
+// The LDS layout (MdLds, md_chunk, md_pad, md_work_doubles, md_lds_doubles, md_carve) lives in mbx_lds.hpp.
 
 // Exclusive prefix sums over the threads of three per-thread counts (base) and their totals.  All threads call; ends with a barrier.
 __device__ __forceinline__ void md_scan3(int* CNT, const int (&c)[3], int (&base)[3], int (&tot)[3])

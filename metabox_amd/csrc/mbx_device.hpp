@@ -38,12 +38,17 @@ MBX_MATH double m_exp(double a) { return fm::exp_fast(a); }
 MBX_MATH double m_log(double a) { return fm::log_fast(a); }
 #endif
 
-
 constexpr int kThreads = 256;          // 4 waves of 64: the default workgroup
 // The block-cooperative helpers take the workgroup size from the launch (256, or 512 for the LDS-bound geometries of mbx_rlepso.hpp)
 #define MBX_NT ((int)blockDim.x)
 #define MBX_NW ((int)blockDim.x >> 6)
 constexpr double kTwoPi = 6.283185307179586;
+// LDS traffic between the lanes of ONE wave (a store by one lane, a load of that address by another): the DS unit executes a wave's
+// operations in program order, so all that is needed is that the compiler keeps the order and that the data has landed
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // ------------------------------------------------------------------------------------------------
 // Device copy of a problem (pointers are device addresses inside the suite's constant pool).
@@ -691,15 +696,15 @@ __device__ void eval_rows_protein(const PT& P, const EvalLds& L, int n_rows)
                 const int i = m / 3;
                 ATOM[4 * i + (m - 3 * i)] = s + P.pc[m];
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
             for (int i = lane; i < n; i += 64)
                 ATOM[4 * i + 3] = ATOM[4 * i] * ATOM[4 * i] + ATOM[4 * i + 1] * ATOM[4 * i + 1] + ATOM[4 * i + 2] * ATOM[4 * i + 2];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
             double acc = protein_pair_sum<MBX_PROTEIN_PFW>(ATOM, rec, pij, n_pairs, lane, 64);
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);      // fixed butterfly: every lane ends with the same sum
             if (lane == 0) L.F[r] = (2 * acc) / n;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // the next row overwrites ATOM
+            wave_lds_fence();      // the next row overwrites ATOM
         }
         __syncthreads();
         return;
@@ -1249,7 +1254,6 @@ __device__ void eval_rows(const PT& P, const EvalLds& L, int n, const RowPost* p
     }
     __syncthreads();
 }
-
 
 // cost_i = problem.eval(x_i) [- optimum] for the n rows staged in L.X (the __get_costs of every optimizer, e.g.
 // rlepso_optimizer.py:68-74): objective, then NoisyProblem's noise with draws from the replay tape ([3, n] rows) or from Philox

@@ -9,33 +9,12 @@
 // the block for the velocity phase and the evaluation.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams
+#include "mbx_lds.hpp"
 
 namespace mbx {
 
-struct GlLds {
-    double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *GB, *K1, *K2, *GF;
-    int* IMPR;
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
-};
-
-__host__ __device__ inline int64_t gl_lds_doubles(int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    return NE + eval_t_doubles(NP, D) + SC + 2 * DD + 5 * align2(D) + 3 * P + 16 + 10 + align2((P + 1) / 2);
-}
-
-__device__ __forceinline__ GlLds gl_carve(double* base, int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    GlLds L;
-    double* p = base;
-    L.X = p; p += NE;  L.T = p; p += eval_t_doubles(NP, D);  L.Z = p; p += SC;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);  L.GB = p; p += align2(D);
-    L.NC = p; p += P;  L.K1 = p; p += P;  L.K2 = p; p += P;  L.RED = p; p += 16;  L.GF = p; p += 10;
-    L.IMPR = reinterpret_cast<int*>(p);
-    return L;
-}
+// The LDS layout (GlLds, gl_lds_doubles, gl_carve) lives in mbx_lds.hpp.
 
 // observe() for particle i (:127-152).  x: its row of L.X; pb: its pbest row (== x when it has just improved).
 __device__ __forceinline__ void gl_features(const double* x, const double* pb, const double* gb, int D, double ccost, double pbest,

@@ -18,37 +18,15 @@
 // Arithmetic follows numpy's expression order with no contraction (the build passes -ffp-contract=off); uniform(a, b) = a + (b - a) u.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams
+#include "mbx_lds.hpp"
 
 namespace mbx {
 
 constexpr double kGlW = 0.7298, kGlC1 = 1.49618, kGlPm = 0.01, kGlRho = 0.2;
 constexpr int kGlSg = 7, kGlNsel = MBX_GLPSO_NSEL;
 
-struct GpLds {
-    double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *GB, *PBC, *EXC, *STAG, *RED;
-    int* FLAG;
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
-};
-
-// X: evaluation rows (the swarm, then the new exemplars); Z: evaluator scratch, holds pbest_pos / the exemplars between the evaluations
-__host__ __device__ inline int64_t gp_lds_doubles(int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    return NE + eval_t_doubles(NP, D) + SC + 2 * DD + 5 * align2(D) + 4 * P + 16 + align2((P + 1) / 2);
-}
-
-__device__ __forceinline__ GpLds gp_carve(double* base, int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    GpLds L;
-    double* p = base;
-    L.X = p; p += NE;  L.T = p; p += eval_t_doubles(NP, D);  L.Z = p; p += SC;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);  L.GB = p; p += align2(D);
-    L.NC = p; p += P;  L.PBC = p; p += P;  L.EXC = p; p += P;  L.STAG = p; p += P;  L.RED = p; p += 16;
-    L.FLAG = reinterpret_cast<int*>(p);
-    return L;
-}
+// The LDS layout (GpLds, gp_lds_doubles, gp_carve) lives in mbx_lds.hpp.
 
 // __exemplar_update (:61-66) on the staged swarm: Z = pbest_pos, L.PBC = pbest, L.GB = gbest_pos, L.EXC / L.STAG = exemplar_cost and the
 // counters.  xb: the exemplar block of the tape (nullptr: Philox).  Writes exemplar / exemplar_cost / stag of the state block (S) and

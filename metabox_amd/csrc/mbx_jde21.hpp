@@ -39,68 +39,16 @@
 // Arithmetic follows numpy's expression order with no contraction (the build passes -ffp-contract=off).
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams
+#include "mbx_lds.hpp"
 
 namespace mbx {
 
-constexpr int kJdS = MBX_JDE21_SNP, kJdTries = 25, kJdParts = 8;
+constexpr int kJdTries = 25, kJdParts = 8;
 constexpr double kJdTau = 0.1, kJdFinit = 0.5, kJdCrinit = 0.9, kJdFlB = 0.1, kJdFlS = 0.17, kJdFu = 1.1, kJdCrlB = 0.0, kJdCrlS = 0.1, kJdCru = 1.1;
 constexpr double kJdEps = 1e-12, kJdMyEps = 0.25, kJdDead = 1e15;
 
-// LDS of one evaluation chunk of ch rows: X | T | Z
-__host__ __device__ inline int64_t jd_ev_doubles(int ch, int D)
-{
-    const int64_t ne = (int64_t)ch * D;
-    return align2(ne) + eval_t_doubles(ch, D) + align2(ne > 2 * kThreads ? ne : 2 * kThreads);
-}
-// LDS row stride of the staged population and of the trials.  The lanes of a wave read 16 consecutive rows at once (8 bytes each): with a
-// stride of D doubles they hit distinct banks unless D is a multiple of 4 (D = 12: 2-way, D = 40: 4-way conflicts), where one double of
-// padding makes the stride odd.
-__host__ __device__ inline int jd_stride(int D) { return D % 4 == 0 ? D + 1 : D; }
-__host__ __device__ inline int64_t jd_stage_doubles(int NP, int D) { return align2((int64_t)(NP - kJdS) * jd_stride(D)); }
-// rows per evaluation chunk: at most 80, at least 54 (the big pass in three chunks), what fits the staging area of the big population between
-__host__ __device__ inline int jd_chunk(int NP, int D)
-{
-    int ch = 80;
-    while (ch > 54 && jd_ev_doubles(ch, D) > jd_stage_doubles(NP, D)) --ch;
-    return ch;
-}
-__host__ __device__ inline int64_t jd_ev_area(int NP, int D)
-{
-    const int64_t a = jd_stage_doubles(NP, D), b = jd_ev_doubles(jd_chunk(NP, D), D);
-    return a > b ? a : b;
-}
-__host__ __device__ inline int64_t jd_lds_doubles(int NP, int D)
-{
-    const int64_t DD = align2((int64_t)D * D), P = align2(NP);
-    return jd_stage_doubles(NP, D) + jd_ev_area(NP, D) + 2 * DD + 4 * align2(D) + align2(kJdS * D) + 6 * P + 16 + 6 * align2((P + 1) / 2);
-}
-
-struct JdLds {
-    double *UP, *EV, *M1T, *M2T, *DSH, *V0, *V1, *V2, *SP, *COST, *FF, *CR, *TC, *TF, *TCR, *RED;
-    double* ACC;           // shares TC's memory: the selection reads the trial costs before its barrier and writes ACC after it
-    int *R1, *R2, *R3, *JR, *CID, *WIN;
-    // the evaluator's view of the staging area for a chunk of ch rows, costs into f
-    __device__ __forceinline__ EvalLds eval(int ch, int D, double* f) const
-    {
-        double* T = EV + align2((int64_t)ch * D);
-        return EvalLds{EV, T + eval_t_doubles(ch, D), T, M1T, M2T, DSH, V0, V1, V2, f};
-    }
-};
-
-__device__ __forceinline__ JdLds jd_carve(double* base, int NP, int D)
-{
-    const int64_t DD = align2((int64_t)D * D), P = align2(NP), PI = align2((P + 1) / 2);
-    JdLds L;
-    double* p = base;
-    L.UP = p; p += jd_stage_doubles(NP, D);  L.EV = p; p += jd_ev_area(NP, D);  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);  L.SP = p; p += align2(kJdS * D);
-    L.COST = p; p += P;  L.FF = p; p += P;  L.CR = p; p += P;  L.TC = p; L.ACC = p; p += P;  L.TF = p; p += P;  L.TCR = p; p += P;
-    L.RED = p; p += 16;
-    L.R1 = reinterpret_cast<int*>(p); p += PI;  L.R2 = reinterpret_cast<int*>(p); p += PI;  L.R3 = reinterpret_cast<int*>(p); p += PI;
-    L.JR = reinterpret_cast<int*>(p); p += PI;  L.CID = reinterpret_cast<int*>(p); p += PI;  L.WIN = reinterpret_cast<int*>(p);
-    return L;
-}
+// The LDS layout (JdLds, kJdS, jd_stride, jd_chunk, jd_lds_doubles, jd_carve) lives in mbx_lds.hpp.
 
 // Python's float a % m for m > 0 (:115-116): fmod, then the result takes the divisor's sign
 __device__ __forceinline__ double jd_pymod(double a, double m)

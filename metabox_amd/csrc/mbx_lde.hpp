@@ -7,15 +7,12 @@
 // behind after every __get_feature.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams
+#include "mbx_lds.hpp"
 
 namespace mbx {
 
-struct LdeLds {
-    double *P, *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *FIT, *NC, *SF, *CR, *SORTED, *RED, *HS;
-    int *PIDX, *R0, *R1, *JR, *HIST;
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
-};
+// The LDS layout (LdeLds, lde_lds_doubles, lde_carve) lives in mbx_lds.hpp.
 
 // BASELINE config 3 as written (pop = 100 at D = 30): the kernels of this geometry read the two D x D maps from global memory through scalar
 // loads (matvec_rows_scalar) and keep no copy of them in LDS: 90.8 -> 76.4 KB per workgroup, i.e. TWO resident 512-thread workgroups per CU.
@@ -25,36 +22,6 @@ struct LdeLds {
 __host__ __device__ constexpr bool lde_maps_in_lds(int NP, int D) { return !((NP == 100 || (NP == 50 && !MBX_LDE50_MAPS_IN_LDS)) && D == 30); }
 // chunk of the register-resident row in matvec_rows_scalar_kc (0: whole row, for the 128-VGPR instantiation)
 __host__ __device__ constexpr int lde_matvec_chunk(int NP, int D) { return NP == 50 && D == 30 ? 15 : 0; }
-
-__host__ __device__ inline int64_t lde_lds_doubles(int NP, int D, bool maps = true)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = maps ? align2((int64_t)D * D) : 0,
-                  P = align2(NP), PI = align2((P + 1) / 2);
-    const int64_t TS = eval_t_doubles(NP, D), PT = NE > TS ? NE : TS;     // parents and the evaluator's scratch T share storage
-    return NE + PT + SC + 2 * DD + 4 * align2(D) + 2 * P + 16 + 8 + 4 * PI + 8;      // SF and CR live in Z (SC >= 512 >= 2 P)
-}
-
-__device__ __forceinline__ LdeLds lde_carve(double* base, int NP, int D, bool maps = true)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = maps ? align2((int64_t)D * D) : 0,
-                  P = align2(NP), PI = align2((P + 1) / 2);
-    LdeLds L;
-    double* p = base;
-    const int64_t TS = eval_t_doubles(NP, D);
-    // P (the parents) is dead between the mutation and the selection, exactly while the evaluator needs its scratch T: they share
-    // storage and the unchanged parents are re-read from HBM after the evaluation (12 KB less LDS at NP = 50, D = 30: three resident
-    // workgroups per CU instead of two).
-    L.P = p; L.T = p; p += NE > TS ? NE : TS;  L.X = p; p += NE;  L.Z = p; p += SC;
-    L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);
-    L.FIT = p; p += P;  L.NC = p; p += P;
-    L.SF = L.Z;  L.CR = L.Z + P;                                 // scale factors / crossover rates: last read by the mutation, Z first written by the evaluator
-    L.SORTED = L.NC;                                             // the trials' costs are dead once the selection is done
-    L.RED = p; p += 16;  L.HS = p; p += 8;
-    L.PIDX = (int*)p; p += PI;  L.R0 = (int*)p; p += PI;  L.R1 = (int*)p; p += PI;  L.JR = (int*)p; p += PI;
-    L.HIST = (int*)p;
-    return L;
-}
 
 // np.histogram(a, 5) bin of one value over uniform bins on [first, last] (numpy/lib/_histograms_impl.py)
 __device__ __forceinline__ int lde_hist_bin(double v, double first, double last)

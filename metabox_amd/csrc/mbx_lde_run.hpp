@@ -109,51 +109,7 @@ __host__ __device__ constexpr bool lde_run_kind_ok(int kind, int D, bool two)
 __host__ __device__ constexpr int lde_run_tiles(int NP) { return (NP + 15) / 16; }
 __host__ __device__ constexpr int lde_run_threads(int NP) { return 64 * lde_run_tiles(NP); }
 
-struct LdeRunLds {
-    double *P, *TB, *TB2, *FIT, *A1, *A2, *FEAT, *HS, *RED, *SCAL, *DSH;
-    float *ACT, *HC;
-    uint8_t *RK, *ORDER;         // rank of a physical row / row at a rank (NP <= 255)
-    int *ACC, *HIST, *FLAG;      // ACC: the ranking's per-row counters
-};
-
-// LDS is allocated in 1280-byte granules: 3 workgroups per CU need <= 53 760 B each (pop 100: 52 768 B), 6 need <= 26 880 B (pop 50: 26 880 B)
-__host__ __device__ inline int64_t lde_run_lds_doubles(int NP, int D, int H, bool two)
-{
-    const int64_t NE = align2((int64_t)NP * D), P = align2(NP);
-    return (two ? 3 : 2) * NE + 2 * P + align2(NP + 2 * MBX_LDE_BINS) + 8 + 8 + 8 + P /* ACT: 2 NP floats */ + align2(H) /* h | c */ + align2((P + 1) / 2) + 2 * align2((P + 7) / 8) + 4 + align2(D);
-}
-
-__device__ __forceinline__ LdeRunLds lde_run_carve(double* base, int NP, int D, int H, bool two)
-{
-    const int64_t NE = align2((int64_t)NP * D), P = align2(NP), PI = align2((P + 1) / 2);
-    LdeRunLds L;
-    double* p = base;
-    L.P = p; p += NE;  L.TB = p; p += NE;
-    L.TB2 = nullptr;
-    if (two) { L.TB2 = p; p += NE; }           // second tile array (kinds 3, 4, 5, 15, 20, 24)
-    L.FIT = p; p += P;
-    L.A1 = p; p += P;            // SORTED (from the ranking to the next row sums) | Gallagher: best key per row
-    L.FEAT = p; L.A2 = p; p += align2(NP + 2 * MBX_LDE_BINS);   // features; dead between the policy's input staging and the next feature phase, where
-                                 // the objective uses the storage: F0 (step ellipsoid: |z_hat_0|) | Gallagher: winning peak per row
-    L.HS = p; p += 8;  L.RED = p; p += 8;  L.SCAL = p; p += 8;
-    L.ACT = (float*)p; p += P;
-    L.HC = (float*)p; p += align2(H);
-    L.ACC = (int*)p; p += PI;  L.RK = (uint8_t*)p; p += align2((P + 7) / 8);  L.ORDER = (uint8_t*)p; p += align2((P + 7) / 8);
-    L.HIST = (int*)p;            // [5] bin counts, [6] the done flag
-    L.FLAG = L.HIST + 6;
-    p += 4;
-    L.DSH = p;                   // the problem's shift vector (0 where the objective has none)
-    return L;
-}
-
-// LDS traffic between the lanes of ONE wave (a store by one lane, a load of that address by another): the DS unit executes a wave's
-// operations in program order, so all that is needed is that the compiler keeps the order and that the data has landed
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// The LDS layout (LdeRunLds, lde_run_lds_doubles, lde_run_carve) lives in mbx_lds.hpp, wave_lds_fence in mbx_device.hpp.
 
 // order-preserving map double -> uint64 (for the LDS max of the Gallagher keys)
 __device__ __forceinline__ unsigned long long f64_sortable(double v)

@@ -40,12 +40,13 @@
 // up to max_fes / 16 + 64; only a skip_step call that runs further past the budget takes the device's tanh instead.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams
+#include "mbx_lds.hpp"
 #include "mbx_npsum.hpp"
 
 namespace mbx {
 
-constexpr int kLesNP = MBX_LES_NP, kLesNParam = MBX_LES_NPARAM, kLesNTs = MBX_LES_NTS;
+constexpr int kLesNTs = MBX_LES_NTS;
 constexpr double kLesSigmaRatio = 0.2;
 // offsets inside a parameter set (vector2nn order)
 constexpr int kLesWq = 0, kLesBq = 24, kLesWk = 32, kLesBk = 56, kLesWv = 64, kLesBv = 67, kLesW1 = 68, kLesB1 = 220, kLesW2 = 228, kLesB2 = 244;
@@ -61,44 +62,13 @@ struct LesArgs {
     int step0, skip_total;      // skip route: this launch runs steps step0 .. of a call that ends at step == skip_total
 };
 
-struct LesLds {
-    double *XR, *T, *Z, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *ZN, *MU, *SIG, *PC, *PS;
-    float *PRM, *Q, *K, *V, *A, *W, *AL;
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{XR, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
-};
-
-__host__ __device__ inline int64_t les_lds_doubles(int D)
-{
-    const int64_t NE = align2((int64_t)kLesNP * D), ZS = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D);
-    const int64_t floats = align2(kLesNParam) + 2 * kLesNP * 8 + 3 * kLesNP + 2 * align2(D);
-    return align2(NE + eval_t_doubles(kLesNP, D) + ZS + 2 * DD + 4 * align2(D) + kLesNP + 32 + NE + 8 * align2(D) + (floats + 1) / 2);
-}
-
-__device__ __forceinline__ LesLds les_carve(double* base, int D)
-{
-    const int64_t NE = align2((int64_t)kLesNP * D), ZS = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), DV = align2(D);
-    LesLds L{};
-    double* p = base;
-    L.XR = p; p += NE;  L.T = p; p += eval_t_doubles(kLesNP, D);  L.Z = p; p += ZS;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += DV;  L.V0 = p; p += DV;  L.V1 = p; p += DV;  L.V2 = p; p += DV;  L.NC = p; p += kLesNP;  L.RED = p; p += 32;
-    L.ZN = p; p += NE;  L.MU = p; p += DV;  L.SIG = p; p += DV;  L.PC = p; p += 3 * DV;  L.PS = p; p += 3 * DV;
-    float* q = reinterpret_cast<float*>(p);
-    L.PRM = q; q += align2(kLesNParam);  L.Q = q; q += kLesNP * 8;  L.K = q; q += kLesNP * 8;  L.V = q; q += kLesNP;  L.A = q; q += kLesNP;  L.W = q; q += kLesNP;
-    L.AL = q;
-    return L;
-}
+// The LDS layout (LesLds, kLesNP, kLesNParam, les_lds_doubles, les_carve) lives in mbx_lds.hpp.
 
 // self.timestamp (:51) without an indexed table (a dynamic index into a local array is scratch memory)
 __device__ __forceinline__ int les_stamp(int k)
 {
     return k == 0 ? 1 : k == 1 ? 3 : k == 2 ? 10 : k == 3 ? 30 : k == 4 ? 50 : k == 5 ? 100 : k == 6 ? 250 : k == 7 ? 500 : k == 8 ? 750 : k == 9 ? 1000
          : k == 10 ? 1250 : k == 11 ? 1500 : 2000;
-}
-
-// what lanes of one wave wrote to LDS is visible to the wave's other lanes afterwards
-__device__ __forceinline__ void les_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // np.clip = minimum(maximum(x, lb), ub): a NaN stays a NaN
@@ -276,7 +246,7 @@ __global__ __launch_bounds__(kThreads) void k_les_run(BatchParams bp, LesArgs ar
                 v = fmaf(p[kLesWv], x0, v); v = fmaf(p[kLesWv + 1], x1, v); v = fmaf(p[kLesWv + 2], x2, v);
                 L.V[tid] = v;
             }
-            les_wave_sync();
+            wave_lds_fence();
             if (tid < NP) {                                          // softmax(Q K^T / sqrt(8)) V of row tid (:29-30)
                 float s[kLesNP];
                 float m = -INFINITY;
@@ -296,9 +266,9 @@ __global__ __launch_bounds__(kThreads) void k_les_run(BatchParams bp, LesArgs ar
                 for (int j = 0; j < NP; ++j) a = fmaf(s[j] / sum, L.V[j], a);
                 L.A[tid] = a;
             }
-            les_wave_sync();
+            wave_lds_fence();
             if (tid < NP) L.W[tid] = les_softmax16(L.A, tid);         // softmax over the 16 rows (:30)
-            les_wave_sync();
+            wave_lds_fence();
             if (tid < D) {                                           // cal_mlp_feature (:97-114), LrNet (:38-40), mu and sigma (:140-143)
                 const int d = tid;
                 const double mu = L.MU[d], sg = L.SIG[d];

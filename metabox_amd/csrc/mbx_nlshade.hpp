@@ -58,8 +58,6 @@ namespace mbx {
 
 constexpr int kNlTries = 25, kNlArcMin = 25, kNlNmin = 4;
 
-__host__ __device__ inline int64_t nl_lds_doubles(int N0, int D) { return md_lds_doubles(N0, D); }
-
 // searchsorted(cdf, u, side='right') over cdf[0, n), clamped to a row
 __device__ __forceinline__ int nl_choice(const double* cdf, int n, double u)
 {

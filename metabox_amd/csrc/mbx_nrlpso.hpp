@@ -19,54 +19,17 @@
 // Every operation outside the objective is + - * /, sqrt and clip, in numpy's order (np.sum: mbx_npsum.hpp), with -ffp-contract=off.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2, log_and_terminate
+#include "mbx_rlepso.hpp"   // BatchParams, log_and_terminate
+#include "mbx_lds.hpp"
 #include "mbx_npsum.hpp"
 #include "mbx_qchoose.hpp"
 
 namespace mbx {
 
-constexpr int kNrK = MBX_NRLPSO_K;
-
 // per-step records of the multi-step kernel (each may be nullptr) and the last action of every instance
 struct NrTraj { int32_t* actions; double* state; double* reward; int32_t* last_action; };
 
-struct NrLds {
-    double *X, *T, *Z, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *POP, *PB, *COST, *PBCOST, *STAG, *SS, *DIST, *TMP, *GB, *SC, *DG, *DM;
-    int *PNI, *GNI;
-    __device__ __forceinline__ EvalLds eval(const double* x, double* f) const { return EvalLds{x, Z, T, M1T, M2T, DSH, V0, V1, V2, f}; }
-};
-
-__host__ __device__ inline int nr_stride(int NP) { return NP | 1; }
-
-// rows = evaluation rows of the launch: NP for the reset (its X doubles as the population), 1 for a step (step = true: the resident arrays,
-// and with cached = true the distance matrix: 80.8 KB at NP = 100; 132 KB at NP = 128, which fits the 160 KB up to D = 7 only)
-__host__ __device__ inline int64_t nr_lds_doubles(int rows, int NP, int D, bool step, bool cached)
-{
-    const int64_t NE = align2((int64_t)rows * D), ZS = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    int64_t n = NE + eval_t_doubles(rows, D) + ZS + 2 * DD + 4 * align2(D) + align2(rows) + 32 + P;
-    if (step) n += 2 * align2((int64_t)NP * D) + 6 * P + align2(D) + MBX_NSCALAR + MBX_NRLPSO_DIAG_SLOTS + align2((kNrK * NP + 1) / 2) + 4 +
-                   (cached ? align2((int64_t)NP * nr_stride(NP)) : 0);
-    return n;
-}
-
-__device__ __forceinline__ NrLds nr_carve(double* base, int rows, int NP, int D, bool step, bool cached)
-{
-    const int64_t NE = align2((int64_t)rows * D), ZS = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    NrLds L{};
-    double* p = base;
-    L.X = p; p += NE;  L.T = p; p += eval_t_doubles(rows, D);  L.Z = p; p += ZS;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);
-    L.NC = p; p += align2(rows);  L.RED = p; p += 32;  L.COST = p; p += P;
-    L.POP = L.X;
-    if (step) {
-        L.POP = p; p += align2((int64_t)NP * D);  L.PB = p; p += align2((int64_t)NP * D);
-        L.PBCOST = p; p += P;  L.STAG = p; p += P;  L.SS = p; p += P;  L.DIST = p; p += P;  L.TMP = p; p += 2 * P;
-        L.GB = p; p += align2(D);  L.SC = p; p += MBX_NSCALAR;  L.DG = p; p += MBX_NRLPSO_DIAG_SLOTS;
-        L.PNI = (int*)p; p += align2((kNrK * NP + 1) / 2);  L.GNI = (int*)p; p += 4;
-        L.DM = cached ? p : nullptr;
-    }
-    return L;
-}
+// The LDS layout (NrLds, kNrK, nr_stride, nr_lds_doubles, nr_carve) lives in mbx_lds.hpp.
 
 // sqrt(np.sum((a - b) ** 2, -1)) of two rows
 __device__ __forceinline__ double nr_dist(const double* a, const double* b, int D)

@@ -9,40 +9,14 @@
 // The diversity decides the reward through `d_new > d_old`; its sums follow numpy's pairwise order (np.sum(., 1), np.mean(.)).
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams
+#include "mbx_lds.hpp"
 #include "mbx_npsum.hpp"    // np_sum: numpy's pairwise summation order
 #include "mbx_qchoose.hpp"  // ql_choose: the tabular agents' choice rule
 
 namespace mbx {
-// four waves per SIMD: left alone the compiler takes 126-160 VGPRs for the multi-step / sweep kernels (three resident workgroups per CU
-// although the LDS would hold five); capped at 128 they spill little or nothing (QLPSO rollout 82 -> 69 us, RL-PSO rollout 60 -> 53 us per step)
-#ifndef MBX_N4_WAVES
-#define MBX_N4_WAVES __attribute__((amdgpu_waves_per_eu(4)))
-#endif
 
-struct QlLds {
-    double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *POP, *COST, *MEAN, *DIST, *SC;
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
-};
-
-// rows = evaluation rows of the launch: NP for the reset (its X doubles as the population), 1 for a step
-__host__ __device__ inline int64_t ql_lds_doubles(int rows, int NP, int D)
-{
-    const int64_t NE = align2((int64_t)rows * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    return NE + eval_t_doubles(rows, D) + SC + 2 * DD + 5 * align2(D) + align2(rows) + 16 + align2((int64_t)NP * D) + 2 * P + MBX_NSCALAR;
-}
-
-__device__ __forceinline__ QlLds ql_carve(double* base, int rows, int NP, int D)
-{
-    const int64_t NE = align2((int64_t)rows * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    QlLds L;
-    double* p = base;
-    L.X = p; p += NE;  L.T = p; p += eval_t_doubles(rows, D);  L.Z = p; p += SC;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);  L.MEAN = p; p += align2(D);
-    L.NC = p; p += align2(rows);  L.RED = p; p += 16;  L.POP = p; p += align2((int64_t)NP * D);  L.COST = p; p += P;  L.DIST = p; p += P;
-    L.SC = p;
-    return L;
-}
+// The LDS layout (QlLds, ql_lds_doubles, ql_carve) and MBX_N4_WAVES live in mbx_lds.hpp.
 
 // __cal_diversity (:45-46) of the population in L.POP.  All threads call; the value is returned to every thread.
 __device__ __forceinline__ double ql_diversity(const QlLds& L, int NP, int D)

@@ -9,6 +9,7 @@
 // (pbest/stagnation bookkeeping) is done by thread i; argmin uses wave shuffles.
 #pragma once
 #include "mbx_device.hpp"
+#include "mbx_lds.hpp"
 
 namespace mbx {
 
@@ -71,38 +72,7 @@ __device__ __forceinline__ bool log_and_terminate_guarded(const BatchParams& bp,
     return done;
 }
 
-// LDS carve-up (all offsets in doubles; base is 16-byte aligned, every array starts 16-byte aligned)
-struct RlLds {
-    double *PB, *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *PBC, *NC, *PNI, *CMUT, *R1, *R2, *GB, *COEF, *RED;
-    int *IMPR, *MASK, *RANK;
-    // KB (NE bytes): rank of the FDR exemplar of every (rank, dimension), carved out of the part of Z that R1 / R2 / COEF leave free
-    // (all dead before the evaluator first writes Z)
-    uint8_t* KB;
-    // FL (one uint16 per work item of the FDR pass) / FLN: the items whose scan met a near-tie, appended by their owners and settled wave-cooperatively (fdr_settle); same
-    // free part of Z, behind KB
-    uint16_t* FL;
-    int* FLN;
-    // NCS [NP]: the cost column the FDR scan reads -- NC with the rows that are bitwise copies of the row one rank up (same cost, same position: particles sitting on
-    // the same corner of the box) replaced by a huge value, so that the scan never takes them and never mistakes them for near-ties (rl_mark_copies); same free part of Z
-    double* NCS;
-    int zd;                       // doubles of Z (rl_z_doubles)
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, NC, zd}; }
-};
-
-__host__ __device__ inline int64_t align2(int64_t n) { return (n + 1) & ~(int64_t)1; }
-
-// doubles of the move phase's tables inside Z: KB (NE bytes, padded to 16) | FLN + pad (16 bytes) | FL (up to NE uint16)
-__host__ __device__ inline int64_t rl_aux_doubles(int NP, int D) { const int64_t NE = (int64_t)NP * D; return ((NE + 15) / 16 * 16 + 16 + 2 * NE + 7) / 8; }
-
-// evaluator scratch Z: n*D doubles, at least 2 per thread for the block reductions, and room for the move phase's R1 | R2 | COEF | NCS | tables
-__host__ __device__ inline int64_t rl_z_doubles(int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D);
-    int64_t need = 3 * align2(NP) + 96 + rl_aux_doubles(NP, D);
-    if (need < 2 * kThreads) need = 2 * kThreads;
-    if (D == 12 && need < 4 * 4 * 100) need = 4 * 4 * 100;      // protein docking (D = 12, 100 atoms): one 32-byte-per-atom table per wave of a 256-thread workgroup (eval_rows_protein)
-    return align2(NE > need ? NE : need);
-}
+// The LDS layout (RlLds, rl_z_doubles, rl_lds_doubles, rl_carve) lives in mbx_lds.hpp.
 
 // chunk of the register-resident row in the resident kernel's matvec (matvec_rows_scalar_kc; 0: whole row): at D = 40 the 80 row registers collide
 // with the resident velocities / pbest positions
@@ -119,49 +89,6 @@ __host__ __device__ constexpr int rl_run_matvec_chunk(int D) { return D == 40 ? 
 // The bbob D = 30 geometry of the reference (NP = 100, rlepso_optimizer.py:9; `--dim 30`): its kernels read the two D x D maps from global memory
 // (matvec_rows_scalar) and keep no LDS copy: 90.0 -> 75.6 KB per workgroup, i.e. TWO resident 512-thread workgroups per CU instead of one.
 __host__ __device__ constexpr bool rl_maps_in_lds(int NP, int D) { return !(NP == 100 && D == 30); }
-
-__host__ __device__ inline int64_t rl_lds_doubles(int NP, int D, bool maps = true)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = rl_z_doubles(NP, D), DD = maps ? align2((int64_t)D * D) : 0,
-                  P = align2(NP), TS = eval_t_doubles(NP, D);
-    // PB (aliased by the evaluator's scratch T once the velocity phase is over), X: NE each; Z: SC (R1, R2, COEF and the byte tables of
-    // the move phase, all dead before the first evaluation, live in it); M1T, M2T; DSH, V0, V1, V2, GB: D each; PBC, NC, PNI, CMUT: P each;
-    // RED: 16; 3 int arrays  (29.8 KB at NP = 100, D = 10: five workgroups per CU)
-    return TS + NE + SC + 2 * DD + 4 * P + 5 * align2(D) + 16 + 3 * align2((P + 1) / 2);
-}
-
-__device__ __forceinline__ RlLds rl_carve(double* base, int NP, int D, bool maps = true)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = rl_z_doubles(NP, D), DD = maps ? align2((int64_t)D * D) : 0,
-                  P = align2(NP), TS = eval_t_doubles(NP, D);
-    RlLds L;
-    double* p = base;
-    L.PB = p; L.T = p; p += TS;      // T reuses PB's storage (see rl_commit)
-    L.X = p; p += NE;
-    L.Z = p; L.zd = (int)SC;
-    L.R1 = p; L.R2 = p + P; L.COEF = p + 2 * P;   // per-particle draws and group coefficients: last read in the move phase, Z first written by the evaluator
-    L.NCS = p + 2 * P + 96;
-    L.KB = (uint8_t*)(p + 3 * P + 96);
-    L.FLN = (int*)(L.KB + ((int64_t)NP * D + 15) / 16 * 16);
-    L.FL = (uint16_t*)(L.FLN + 4);
-    p += SC;
-    L.M1T = p; p += DD;
-    L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);
-    L.V0 = p; p += align2(D);
-    L.V1 = p; p += align2(D);
-    L.V2 = p; p += align2(D);
-    L.PBC = p; p += P;
-    L.NC = p; p += P;
-    L.PNI = p; p += P;
-    L.CMUT = p; p += P;
-    L.GB = p; p += align2(D);
-    L.RED = p; p += 16;
-    L.IMPR = (int*)p; p += align2((P + 1) / 2);
-    L.MASK = (int*)p; p += align2((P + 1) / 2);
-    L.RANK = (int*)p;
-    return L;
-}
 
 // pbest / gbest bookkeeping shared by update() and __reinit() (rlepso_optimizer.py:200-222, 145-168).
 // Candidate positions are in L.X, their costs in L.NC.  `stagnation` additionally updates per_no_improve
@@ -1386,7 +1313,6 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         }
     }
 }
-
 
 // The kernel's arguments as the kernarg segment lays them out (a callee cannot name the kernel's parameters; it is handed the segment's address)
 struct RlRunArgs {

@@ -40,7 +40,7 @@
 // Arithmetic follows numpy's expression order with no contraction (the build passes -ffp-contract=off).
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2, log_and_terminate
+#include "mbx_rlepso.hpp"   // BatchParams, log_and_terminate
 #include "mbx_depop.hpp"    // the carve-up and the phases shared with MadDE and NL_SHADE_LBC
 #include "mbx_npsum.hpp"
 #include "mbx_qchoose.hpp"
@@ -49,13 +49,11 @@ namespace mbx {
 
 constexpr int kHpTries = 25, kHpWalk = MBX_RLHPSDE_WALK, kHpSteps = MBX_RLHPSDE_WALK - 1;
 static_assert(kHpWalk <= kThreads, "one thread per walk point");
-constexpr int kHpFeatDoubles = 752;     // walk costs [202] | distances [200] | differences [202] | entropies [12] | counts: 4 waves x 64 ints
 
 // per-step records of k_rlhpsde_run (each may be nullptr) and the last action of every instance
 struct HpTraj { int32_t* actions; double* state; double* reward; int32_t* last_action; };
 
 __host__ __device__ inline int hp_h(int D) { return D / 2 < 1 ? 1 : D / 2; }
-__host__ __device__ inline int64_t hp_lds_doubles(int NP, int D) { return md_lds_doubles(NP, D) + kHpFeatDoubles; }
 
 // population size after `fes` evaluations (:92): int(N0 + ((4 - N0) fes) / max_fes), the product exact, truncated
 __host__ __device__ inline int hp_np_at(int N0, double fes, double max_fes)
@@ -180,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void k_rlhpsde_reset(BatchParams bp, doub
     const int N0 = bp.NP, D = bp.D, CH = md_chunk(D), H = hp_h(D);
     ConstProblem& P = *(ConstProblem*)(bp.problems + bp.problem_idx[b]);   // scalar loads on demand, no SGPR-resident copy
     const MdLds L = md_carve(smem, N0, D);
-    double* FT = smem + md_lds_doubles(N0, D);
+    double* FT = smem + md_lds_hand_doubles(N0, D);
     double* S = bp.state + (int64_t)b * bp.state_stride;
     double* sc = S + MBX_RLHPSDE_ST_SCALARS(N0, D);
     double* gU = S + MBX_RLHPSDE_ST_U(N0, D);
@@ -247,7 +245,7 @@ __device__ __forceinline__ void hp_steps(const BatchParams& bp, const int32_t* _
     }
     ConstProblem& P = *(ConstProblem*)(bp.problems + bp.problem_idx[b]);   // scalar loads on demand, no SGPR-resident copy
     const MdLds L = md_carve(smem, N0, D);
-    double* FT = smem + md_lds_doubles(N0, D);
+    double* FT = smem + md_lds_hand_doubles(N0, D);
     const double* tape = bp.tape ? bp.tape + (int64_t)b * bp.tape_stride : nullptr;
     const uint64_t seed = bp.seeds[b];
     const double lb = P.lb, ub = P.ub, mf = (double)bp.max_fes;

@@ -12,44 +12,12 @@
 // gbest position, the next particle's position, the actor's weights and activations and the problem constants live in LDS.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2, GaussMlp, sample_normal
+#include "mbx_rlepso.hpp"   // BatchParams, GaussMlp, sample_normal
+#include "mbx_lds.hpp"
 
 namespace mbx {
-// four waves per SIMD: left alone the compiler takes 126-160 VGPRs for the multi-step / sweep kernels (three resident workgroups per CU
-// although the LDS would hold five); capped at 128 they spill little or nothing (QLPSO rollout 82 -> 69 us, RL-PSO rollout 60 -> 53 us per step)
-#ifndef MBX_N4_WAVES
-#define MBX_N4_WAVES __attribute__((amdgpu_waves_per_eu(4)))
-#endif
 
-struct RpLds {
-    double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *GB, *XC, *SC;
-    float* ACTV;            // policy activations: input [2D] | h1 [2 h1] | h2 [2 h2] | out [2]
-    float* WTS;             // packed actor weights (mbx_rlpso_rollout only)
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
-};
-
-constexpr int kRpActDoubles = 192;       // room for 2D + 2 h1 + 2 h2 + 2 floats (checked on the host)
-
-// `rows` = evaluation rows the launch needs: NP for the reset, 1 for a step (17 KB instead of 27 KB at D = 10: the step kernel is a
-// chain of short latency-bound phases, so the number of resident workgroups per CU is what buys throughput).
-__host__ __device__ inline int64_t rp_lds_doubles(int rows, int D, int weight_floats)
-{
-    const int64_t NE = align2((int64_t)rows * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(rows);
-    return NE + eval_t_doubles(rows, D) + SC + 2 * DD + 6 * align2(D) + P + 16 + MBX_NSCALAR + kRpActDoubles + align2((weight_floats + 1) / 2);
-}
-
-__device__ __forceinline__ RpLds rp_carve(double* base, int rows, int D)
-{
-    const int64_t NE = align2((int64_t)rows * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(rows);
-    RpLds L;
-    double* p = base;
-    L.X = p; p += NE;  L.T = p; p += eval_t_doubles(rows, D);  L.Z = p; p += SC;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);
-    L.GB = p; p += align2(D);  L.XC = p; p += align2(D);
-    L.NC = p; p += P;  L.RED = p; p += 16;  L.SC = p; p += MBX_NSCALAR;  L.ACTV = reinterpret_cast<float*>(p); p += kRpActDoubles;
-    L.WTS = reinterpret_cast<float*>(p);
-    return L;
-}
+// The LDS layout (RpLds, kRpActDoubles, rp_lds_doubles, rp_carve) and MBX_N4_WAVES live in mbx_lds.hpp.
 
 // ------------------------------------------------------------------------------------------------ reset (init_population :30-60)
 __global__ __launch_bounds__(kThreads) void k_rlpso_reset(BatchParams bp, double* __restrict__ state_out)

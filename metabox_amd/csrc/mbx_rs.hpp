@@ -3,15 +3,12 @@
 // (src/logger.py:94-120) and a ten-line consumer of the block-cooperative evaluator.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"
+#include "mbx_rlepso.hpp"   // BatchParams, log_and_terminate
+#include "mbx_lds.hpp"
 
 namespace mbx {
 
-__host__ __device__ inline int64_t rs_lds_doubles(int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D);
-    return NE + eval_t_doubles(NP, D) + SC + 2 * DD + 4 * align2(D) + align2(NP) + 16;
-}
+// The LDS layout (RsLds, rs_lds_doubles, rs_carve) lives in mbx_lds.hpp.
 
 // `first` = 1: the initial population of run_episode's __reset (:24-29); 0: one more population (:45-46)
 __global__ __launch_bounds__(kThreads) void k_rs_population(BatchParams bp, int first, double* __restrict__ state_out,

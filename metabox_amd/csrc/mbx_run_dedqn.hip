@@ -8,8 +8,6 @@
 
 namespace mbx {
 
-int64_t dedqn_lds_doubles(int np, int dim) { return dd_lds_doubles(np, dim); }
-
 hipError_t dedqn_prepare(size_t lds_bytes)
 {
     hipError_t e = hipFuncSetAttribute((const void*)k_dedqn_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

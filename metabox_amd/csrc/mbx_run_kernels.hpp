@@ -28,7 +28,6 @@ extern template __global__ void k_lde_run<50, 30, 50, true>(LdeRunArgs);
 #endif
 // DEDQN (mbx_dedqn.hpp): kernels AND launch code live in mbx_run_dedqn.hip; mbx.hip reaches them through these host functions
 namespace mbx {
-int64_t dedqn_lds_doubles(int np, int dim);
 hipError_t dedqn_prepare(size_t lds_bytes);         // the kernels' dynamic-LDS limit, once per batch
 void dedqn_launch_reset(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, double* d_state_out);
 void dedqn_launch_step(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, const int32_t* d_actions, double* d_state_out, double* d_reward_out,
@@ -39,7 +38,6 @@ void dedqn_launch_run(const BatchParams& bp, size_t lds_bytes, hipStream_t strea
 // NRLPSO (mbx_nrlpso.hpp): likewise in mbx_run_nrlpso.hip
 namespace mbx {
 bool nrlpso_cached(int np, int dim, uint32_t flags, size_t max_lds_bytes);     // the distance matrix stays in LDS (flag clear and it fits)
-int64_t nrlpso_lds_doubles(int np, int dim, bool step, bool cached);
 hipError_t nrlpso_prepare(size_t lds_bytes);
 void nrlpso_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state_out);
 // d_actions: the caller's actions (mbx_step), or nullptr with the Q-table: the policy decides in the kernel
@@ -49,14 +47,12 @@ void nrlpso_launch_steps(const BatchParams& bp, bool cached, hipStream_t stream,
 }  // namespace mbx
 // SAHLPSO (mbx_sahlpso.hpp): likewise in mbx_run_sahlpso.hip
 namespace mbx {
-int64_t sahlpso_lds_doubles(int dim);
 hipError_t sahlpso_prepare(size_t lds_bytes);
 void sahlpso_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state_out);
 void sahlpso_launch_generation(const BatchParams& bp, hipStream_t stream, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
 }  // namespace mbx
 // LES (mbx_les.hpp): likewise in mbx_run_les.hip
 namespace mbx {
-int64_t les_lds_doubles_of(int dim);
 hipError_t les_prepare(size_t lds_bytes);
 void les_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state_out);
 // skip = 0: up to n_gens generations under the budget / early-stop end rule; skip = 1: steps step0 .. step0 + n_gens - 1 of a skip_step call of skip_total steps
@@ -65,7 +61,6 @@ void les_launch_run(const BatchParams& bp, hipStream_t stream, const float* d_pa
 }  // namespace mbx
 // RL-HPSDE (mbx_rlhpsde.hpp): likewise in mbx_run_rlhpsde.hip
 namespace mbx {
-int64_t rlhpsde_lds_doubles(int np, int dim);
 hipError_t rlhpsde_prepare(size_t lds_bytes);
 void rlhpsde_launch_reset(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, double* d_state_out);
 void rlhpsde_launch_step(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, const int32_t* d_actions, double* d_state_out, double* d_reward_out,
@@ -77,7 +72,6 @@ void rlhpsde_launch_run(const BatchParams& bp, size_t lds_bytes, hipStream_t str
 // NL_SHADE_LBC (mbx_nlshade.hpp): likewise in mbx_run_nlshade.hip
 #include <vector>
 namespace mbx {
-int64_t nlshade_lds_doubles(int np, int dim);
 std::vector<double> nlshade_schedule(int np, int max_fes);      // the batch's table bp.pci: the update count, then N after update 0 .. G
 hipError_t nlshade_prepare(size_t lds_bytes);
 void nlshade_launch_reset(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, double* d_state_out);

@@ -8,8 +8,6 @@
 
 namespace mbx {
 
-int64_t les_lds_doubles_of(int dim) { return les_lds_doubles(dim); }
-
 hipError_t les_prepare(size_t lds_bytes)
 {
     hipError_t e = hipFuncSetAttribute((const void*)k_les_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

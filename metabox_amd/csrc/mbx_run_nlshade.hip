@@ -9,8 +9,6 @@
 
 namespace mbx {
 
-int64_t nlshade_lds_doubles(int np, int dim) { return nl_lds_doubles(np, dim); }
-
 // The population schedule of an episode that runs to the budget (NLPSR, nl_shade_lbc.py:135-147): [0] = the number of updates G, [1 + g] = N after
 // update g (N0 for g = 0).  N = round-half-even(N0 + (4 - N0) x^(1 - x)), x = FEs / MaxFEs, the power in long double, rounded once; FEs advances by
 // the live population, which only ever shrinks.

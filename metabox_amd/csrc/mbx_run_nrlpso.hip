@@ -13,8 +13,6 @@ bool nrlpso_cached(int np, int dim, uint32_t flags, size_t max_lds_bytes)
     return !(flags & MBX_F_NRLPSO_RECOMPUTE) && (size_t)nr_lds_doubles(1, np, dim, true, true) * sizeof(double) <= max_lds_bytes;
 }
 
-int64_t nrlpso_lds_doubles(int np, int dim, bool step, bool cached) { return nr_lds_doubles(step ? 1 : np, np, dim, step, cached); }
-
 hipError_t nrlpso_prepare(size_t lds_bytes)
 {
     hipError_t e = hipFuncSetAttribute((const void*)k_nrlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

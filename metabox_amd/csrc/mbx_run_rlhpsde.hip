@@ -8,8 +8,6 @@
 
 namespace mbx {
 
-int64_t rlhpsde_lds_doubles(int np, int dim) { return hp_lds_doubles(np, dim); }
-
 hipError_t rlhpsde_prepare(size_t lds_bytes)
 {
     hipError_t e = hipFuncSetAttribute((const void*)k_rlhpsde_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

@@ -8,9 +8,6 @@
 
 namespace mbx {
 
-// the larger of the reset's carve-up (40 evaluation rows) and the generation's (one row and the resident arrays)
-int64_t sahlpso_lds_doubles(int dim) { return std::max(sh_lds_doubles(MBX_SAHL_NP, dim, false), sh_lds_doubles(1, dim, true)); }
-
 hipError_t sahlpso_prepare(size_t lds_bytes)
 {
     hipError_t e = hipFuncSetAttribute((const void*)k_sahlpso_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

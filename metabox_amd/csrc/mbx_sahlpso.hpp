@@ -40,13 +40,14 @@
 // Arithmetic follows numpy's expression order with no contraction (the build passes -ffp-contract=off).
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams
+#include "mbx_lds.hpp"
 #include "mbx_npsum.hpp"
 
 namespace mbx {
 
 constexpr double kShC1 = 1.49445, kShLb = -5., kShUb = 5., kShVmax = 1.;
-constexpr int kShNP = MBX_SAHL_NP, kShHcr = MBX_SAHL_HCR, kShHls = MBX_SAHL_HLS, kShNsel = MBX_SAHL_NSEL;
+constexpr int kShHcr = MBX_SAHL_HCR, kShHls = MBX_SAHL_HLS, kShNsel = MBX_SAHL_NSEL;
 
 // M_cr (:12) without an indexed table (a dynamic index into a local array is scratch memory)
 __device__ __forceinline__ double sh_mcr(int k)
@@ -54,49 +55,7 @@ __device__ __forceinline__ double sh_mcr(int k)
     return k == 0 ? 0.0001 : k == 1 ? 0.0005 : k == 2 ? 0.001 : k == 3 ? 0.005 : k == 4 ? 0.01 : k == 5 ? 0.05 : k == 6 ? 0.1 : 0.5;
 }
 
-struct ShLds {
-    double *XR, *T, *Z, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *X, *V, *PB, *FX, *PC0, *W, *PCR, *NFCR, *NSCR, *PLS, *NFLS, *NSLS, *CDFCR, *CDFLS, *MCAU;
-    int *RANK, *SELF, *MI, *MCR, *MLS, *MSUC;
-    uint32_t* KEY;
-    __device__ __forceinline__ EvalLds eval(const double* x, double* f) const { return EvalLds{x, Z, T, M1T, M2T, DSH, V0, V1, V2, f}; }
-};
-
-// rows = evaluation rows of the launch: 40 for the reset (XR is the population), 1 for a generation (step = true: the resident arrays as well)
-__host__ __device__ inline int64_t sh_lds_doubles(int rows, int D, bool step)
-{
-    const int64_t NE = align2((int64_t)rows * D), ZS = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D);
-    int64_t n = NE + eval_t_doubles(rows, D) + ZS + 2 * DD + 4 * align2(D) + align2(rows) + 32 + 7 * (int64_t)kShNP / 2;
-    if (step) n += 3 * align2((int64_t)kShNP * D) + 4 * kShNP + 6 * 16 + 2 * 16;
-    return align2(n);
-}
-
-__device__ __forceinline__ ShLds sh_carve(double* base, int rows, int D, bool step)
-{
-    const int64_t NE = align2((int64_t)rows * D), ZS = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D);
-    ShLds L{};
-    double* p = base;
-    L.XR = p; p += NE;  L.T = p; p += eval_t_doubles(rows, D);  L.Z = p; p += ZS;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);
-    L.NC = p; p += align2(rows);  L.RED = p; p += 32;
-    int* q = reinterpret_cast<int*>(p);
-    L.RANK = q; q += kShNP;  L.SELF = q; q += kShNP;  L.MI = q; q += kShNP;  L.MCR = q; q += kShNP;  L.MLS = q; q += kShNP;  L.MSUC = q; q += kShNP;
-    L.KEY = reinterpret_cast<uint32_t*>(q);
-    p += 7 * kShNP / 2;
-    if (step) {
-        const int64_t PE = align2((int64_t)kShNP * D);
-        L.X = p; p += PE;  L.V = p; p += PE;  L.PB = p; p += PE;
-        L.FX = p; p += kShNP;  L.PC0 = p; p += kShNP;  L.W = p; p += kShNP;  L.MCAU = p; p += kShNP;
-        L.PCR = p; p += 16;  L.NFCR = p; p += 16;  L.NSCR = p; p += 16;  L.PLS = p; p += 16;  L.NFLS = p; p += 16;  L.NSLS = p; p += 16;
-        L.CDFCR = p; p += 16;  L.CDFLS = p; p += 16;
-    }
-    return L;
-}
-
-// what lanes of one wave wrote to LDS is visible to the wave's other lanes afterwards
-__device__ __forceinline__ void sh_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// The LDS layout (ShLds, kShNP, sh_lds_doubles, sh_carve) lives in mbx_lds.hpp.
 
 // searchsorted(cdf, u, side='right') over H entries, never past the last one (a tape is caller data)
 __device__ __forceinline__ int sh_search(const double* cdf, int H, double u)
@@ -295,7 +254,7 @@ __global__ __launch_bounds__(kThreads) void k_sahlpso_generation(BatchParams bp,
                     L.MCAU[k] = ca;
                 }
             }
-            sh_wave_sync();                                           // the next move of this wave reads f_X, w and the pBest row
+            wave_lds_fence();                                           // the next move of this wave reads f_X, w and the pBest row
         }
         fes += 1;                                                     // :92
         if ((double)fes >= (double)log_index * bp.log_interval) {    // :110-112, once

@@ -31,7 +31,8 @@
 // normal(loc, s) = loc + s z, the median of eight values = (a + b) / 2 of the two middle order statistics.
 #pragma once
 #include "mbx_device.hpp"
-#include "mbx_rlepso.hpp"   // BatchParams, align2
+#include "mbx_rlepso.hpp"   // BatchParams
+#include "mbx_lds.hpp"
 
 namespace mbx {
 
@@ -46,34 +47,7 @@ __host__ __device__ inline int sd_local_generations(int max_fes)
     return g;
 }
 
-struct SdLds {
-    double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *GB, *NC, *PBC, *R1, *R2, *LBP, *LBC, *IWT, *SUC, *RED;
-    int *FLAG, *PERM, *LBI, *SWF;
-    uint32_t* KEY;
-    __device__ __forceinline__ EvalLds eval() const { return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
-};
-
-__host__ __device__ inline int64_t sd_lds_doubles(int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    const int64_t NSA = align2(MBX_SDMS_NS);
-    return NE + eval_t_doubles(NP, D) + SC + 2 * DD + 5 * align2(D) + 4 * P + align2((int64_t)MBX_SDMS_NS * D) + 3 * NSA + 16 + align2((3 * P + 2 * NSA + 1) / 2);
-}
-
-__device__ __forceinline__ SdLds sd_carve(double* base, int NP, int D)
-{
-    const int64_t NE = align2((int64_t)NP * D), SC = align2(NE > 2 * kThreads ? NE : 2 * kThreads), DD = align2((int64_t)D * D), P = align2(NP);
-    const int64_t NSA = align2(MBX_SDMS_NS);
-    SdLds L;
-    double* p = base;
-    L.X = p; p += NE;  L.T = p; p += eval_t_doubles(NP, D);  L.Z = p; p += SC;  L.M1T = p; p += DD;  L.M2T = p; p += DD;
-    L.DSH = p; p += align2(D);  L.V0 = p; p += align2(D);  L.V1 = p; p += align2(D);  L.V2 = p; p += align2(D);  L.GB = p; p += align2(D);
-    L.NC = p; p += P;  L.PBC = p; p += P;  L.R1 = p; p += P;  L.R2 = p; p += P;  L.LBP = p; p += align2((int64_t)MBX_SDMS_NS * D);
-    L.LBC = p; p += NSA;  L.IWT = p; p += NSA;  L.SUC = p; p += NSA;  L.RED = p; p += 16;
-    int* q = reinterpret_cast<int*>(p);
-    L.FLAG = q; q += P;  L.PERM = q; q += P;  L.KEY = reinterpret_cast<uint32_t*>(q); q += P;  L.LBI = q; q += NSA;  L.SWF = q;
-    return L;
-}
+// The LDS layout (SdLds, sd_lds_doubles, sd_carve) lives in mbx_lds.hpp.
 
 // __random_regroup's permutation (:88) into L.PERM: new row k = old row PERM[k].  tp: the tape's perm slots (nullptr: Philox -- the rank of NP
 // keys, the index breaking ties).  Ends with a barrier.

@@ -30,6 +30,13 @@ INT_ACTIONS = (3, 7, 16, 19)         # DE-DDQN, QLPSO, DEDQN, NRLPSO choose amon
 AGENTS = (1, 2, 3, 5, 6, 7, 16, 19)
 NEED_STATE_OUT = (2, 3)              # LDE, DE-DDQN
 MAX_FES, LOG_INTERVAL, N_LOGPOINT = 2000, 400, 5
+# id -> the entry of tests/golden/lds_sizes.json (doubles; recorded before the layouts became walks in metabox_amd/csrc/mbx_lds.hpp) that launch_info's lds_bytes reports at
+# this file's geometry (D = 10): the batch's figure, the larger of the reset's and the step's carve-up where both share it (SAHLPSO), or the step kernel's where
+# launch_info reports that one (DE-DDQN, NRLPSO with the distance matrix in LDS)
+LDS_ENTRY = {1: 'rl(16,10,1)', 2: 'lde(16,10,1)', 3: 'dq(1,16,10)', 4: 'rs(16,10)', 5: 'rp(16,10,0)', 6: 'gl(16,10)', 7: 'ql(16,16,10)', 8: 'cl(16,16,10,0,0)',
+             9: 'cl(16,16,10,0,0)', 10: 'cl(16,16,10,0,1)', 11: 'gp(16,10)', 13: 'jd(170,10)', 15: 'md(200,10)', 16: 'dd(16,10)', 18: 'sd(99,10)',
+             19: 'nr(1,16,10,1,1)', 20: 'sh(1,10,1)', 21: 'les(10)'}
+assert sorted(LDS_ENTRY) == sorted(ALGOS)
 
 
 @functools.lru_cache(maxsize=None)
@@ -70,12 +77,19 @@ def _want():
         return json.load(f)
 
 
+@functools.lru_cache(maxsize=None)
+def _lds_sizes():
+    with open(os.path.join(GOLDEN, 'lds_sizes.json')) as f:
+        return json.load(f)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('algo', sorted(ALGOS), ids=lambda a: ALGOS[a][0])
 def test_reset_and_one_step_as_recorded(algo):
     got, want = run(algo), _want()[ALGOS[algo][0]]
     assert len(want['public']) == 2 and len(want['public'][0]) == 16 + N_LOGPOINT + 1
     assert float.fromhex(want['public'][0][1]) >= ALGOS[algo][1], 'the record must hold a batch that has evaluated its population'
+    assert got['launch_info']['lds_bytes'] == 8 * _lds_sizes()[LDS_ENTRY[algo]]
     assert got == want
 
 
