@@ -204,19 +204,38 @@ __device__ __forceinline__ void wave_argmin(double& v, int& i)
     }
 }
 
+// minimum of two float64 that are known not to be NaN: v_min_f64 itself, without the canonicalisation the compiler puts in front of fmin() on values of unknown origin
+__device__ __forceinline__ double min_f64_no_nan(double x, double y)
+{
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+    return r;
+}
+
 // argmin over a[0..n) in LDS (first index on ties).  All threads call; result broadcast through red[0..1].
+// The wave exchanges VALUES only (two ds_bpermute and one v_min_f64 per round; wave_argmin's (value, index) pairs cost a third bpermute, two compares and three
+// selects per round); the index is found afterwards: the lowest lane of the first 64-entry step of `a` that holds an entry equal to the minimum, i.e. the first
+// index of the minimum, np.argmin's.  (Not the lowest LANE of the exchange: lane l has folded entries l, l + 64, ... and would answer l + 64 before l + 1.)
+// A NaN never enters the exchange (x < v is false for it), -0. == 0. holds as it did in wave_argmin's tie rule, and the value handed back is a[imin] itself.
 __device__ __forceinline__ void block_argmin(const double* a, int n, double* red, double& vmin, int& imin)
 {
     const int tid = opaque_tid();
     if (tid < 64) {
-        double v = INFINITY; int idx = 0x7fffffff;
+        double m = INFINITY;
         for (int j = tid; j < n; j += 64) {
             const double x = a[j];
-            if (x < v) { v = x; idx = j; }
+            if (x < m) m = x;
         }
-        wave_argmin(v, idx);
-        if (idx >= n) { idx = 0; v = a[0]; }          // every entry +inf (or NaN): np.argmin answers 0; never hand back an out-of-range index
-        if (tid == 0) { red[0] = v; red[1] = (double)idx; }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) m = min_f64_no_nan(m, __shfl_xor(m, off, 64));
+        int idx = 0;                                  // every entry +inf (or NaN): np.argmin answers 0; never hand back an out-of-range index
+        if (m < INFINITY) {                           // (wave-uniform)
+            for (int j0 = 0; j0 < n; j0 += 64) {
+                const unsigned long long eq = __builtin_amdgcn_ballot_w64(j0 + tid < n && a[j0 + tid] == m);
+                if (eq != 0ull) { idx = j0 + (int)__builtin_ctzll(eq); break; }
+            }
+        }
+        if (tid == 0) { red[0] = a[idx]; red[1] = (double)idx; }
     }
     __syncthreads();
     vmin = red[0]; imin = (int)red[1];

@@ -123,6 +123,7 @@ __device__ __forceinline__ void rl_commit(const RlLds& L, int NP, int D, bool st
 struct MoveCtx {
     const RlLds& L; const double* pci; const double* tape; const Rng& rng; double* gPos; double* gVel;
     const int* ORDER; const int* NLESS; const int* RANK; int NP, D, G; double lb, ub, vmax; const FastDiv& fg;
+    bool whole_groups;           // NP is a multiple of G and both are compile-time constants: fg.div(i) < G for every particle
 };
 
 // Two-headed Gaussian MLP policy (mbx_gauss_mlp in include/mbx.h): RLEPSO's Actor (src/agent/rlepso_agent.py:9-47) and RL-PSO's
@@ -379,8 +380,11 @@ __device__ __forceinline__ int fdr_settle(const RlLds& L, const int* __restrict_
 // UN: candidates per unrolled group (MBX_FDR_UNROLL = 4 everywhere but config 5's resident kernel: 1024 threads, D = 40: 2 / 4 / 8 -> 1.619 / 1.641 / 1.703 ms per
 // generation; the headline kernel: 2 / 3 / 4 / 6 / 8 -> 119.9 / 117.1 / 116.5 / 117.5 / 121.6 us; both with per-lane trip counts)
 // range: an upper bound of |p_jd - p_id| + 1e-5 (ub - lb + 1e-5), used by the near-tie flag only
+// The scan does not read the item's nless: the only thing it decided was `nless > 0` in the flag, and that is a_0 < 0 (NC is in ascending order: somebody is strictly
+// better than the item exactly when the best cost is below its own; a NaN cost answers false both ways) -- a compare on a register the scan holds anyway, where
+// NLESS[ORDER[rk]] was two dependent LDS reads and their address arithmetic per item.
 template <int W, int UN = MBX_FDR_UNROLL, bool TIE = true>
-__device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0, int nless, int bound, int kb[W], double range = 0.)
+__device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0, int bound, int kb[W], double range = 0.)
 {
 #ifdef MBX_ABLATE_FDR_SCAN
     bound = 1;                                                    // instruction-budget builds: the head and the tail of the scan without its loops
@@ -428,7 +432,7 @@ __device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0,
         step(L.NCS[k] - fi, x, k);
     }
     const double thr = fabs(a0) * range * 0x1p-49;               // |a* b_j| <= |a_0| x range for every pair of the item
-    return nless > 0 && !(tiem > f64_hi_as_f32(thr) * 1.0000005f);
+    return a0 < 0. && !(tiem > f64_hi_as_f32(thr) * 1.0000005f);
     } else {
     // unrolled by hand (the compiler does not unroll around the inline assembly of fdr_take); the LDS reads of a group are
     // issued before its first comparison
@@ -534,9 +538,15 @@ __device__ __forceinline__ void fdr_pass(const RlLds& L, const int* ORDER, const
             // the scan's trip count, one per wave: the highest rank among the wave's items (consecutive in ps; nless(rank) <= rank), scalar arithmetic from the pass
             // and the wave's place in it (fdr_exact: scanning past a lane's own nless changes nothing)
             const int top = (pass & 1) ? lim - 1 - w0 : (base + w0 + 63 < lim ? base + w0 + 63 : lim - 1);
-            const int bound = __builtin_amdgcn_readfirstlane(fw.div(top));
+            int bound = __builtin_amdgcn_readfirstlane(fw.div(top));
+#ifdef MBX_FDR_ROUND_BOUND
+            // experiment, measured and dropped (docs/EXPERIMENTS.md): the bound rounded up to whole unrolled groups where the table allows it, so that only the waves
+            // of the top ranks run the remainder loop.  Exact by the argument in fdr_exact's comment, but a remainder candidate costs 20 vector instructions and a
+            // group of UN = 4 costs 74: trading r remainder steps for a whole group ADDS instructions for r < 4.
+            { const int up = 1 + (bound - 1 + UN - 1) / UN * UN; bound = bound > 0 && up <= NP ? up : bound; }
+#endif
             int kb[W];
-            const bool tie = fdr_exact<W, UN, TIE>(L, D, rk, d0, NLESS[ORDER[rk]], bound, kb, range);
+            const bool tie = fdr_exact<W, UN, TIE>(L, D, rk, d0, bound, kb, range);
 #pragma unroll
             for (int q = 0; q < W; ++q) L.KB[rk * D + d0 + q] = (uint8_t)kb[q];
 #ifdef MBX_FDR_COUNT
@@ -572,6 +582,38 @@ __device__ __forceinline__ void fdr_pass(const RlLds& L, const int* ORDER, const
     }
 }
 
+// The arithmetic of the move (rlepso_optimizer.py:179-195) once an item's uniforms and exemplars are known: uf / ucs the FDR weight and the CLPSO uniform of each
+// coordinate, xrs the rank of its CLPSO exemplar (the particle's own rank where no tournament was consumed); FDR exemplars from KB.
+template <int W, bool RES>
+__device__ __forceinline__ void rl_move_apply(const MoveCtx& c, int i, int d0, int rk, const double uf[W], const double ucs[W], const int xrs[W], double cur[W], double vel[W])
+{
+    const RlLds& L = c.L;
+    const int D = c.D, e0 = i * D + d0, es0 = rk * D + d0;
+    const double r1 = L.R1[i], r2 = L.R2[i];
+    const int g = c.fg.div(i);
+    double cw = 0., c1 = 0., c2 = 0., c3 = 0., c4 = 0.;
+    // whole_groups (NP a multiple of the group count, known at compile time): every particle has a group, no select on the five coefficients
+    if (c.whole_groups || g < c.G) { const double* k = L.COEF + g * 6; cw = k[1]; c1 = k[2]; c2 = k[3]; c3 = k[4]; c4 = k[5]; }
+#pragma unroll
+    for (int q = 0; q < W; ++q) {
+        const int e = e0 + q, d = d0 + q;
+        const double pp = L.PB[es0 + q], uc = ucs[q];
+        const int xr = xrs[q], kb = L.KB[es0 + q];
+        const double ex = L.PB[xr * D + d];                        // CLPSO exemplar (own rank: the particle's own pbest)
+        const double v_fdr = uf[q] * (L.PB[kb * D + d] - pp);
+        const double v_pbest = r1 * (pp - cur[q]);
+        const double v_gbest = r2 * (L.GB[d] - cur[q]);
+        const double v_cl = uc * (ex - cur[q]);
+        double nv = cw * vel[q] + c1 * v_cl + c2 * v_fdr + c3 * v_gbest + c4 * v_pbest;
+        nv = fmin(fmax(nv, -c.vmax), c.vmax);
+        double np_ = cur[q] + nv;
+        np_ = fmin(fmax(np_, c.lb), c.ub);
+        L.X[e] = np_;
+        if (RES) { cur[q] = np_; vel[q] = nv; }
+        else { c.gPos[e] = np_; c.gVel[e] = nv; }
+    }
+}
+
 // Velocity / position update of W adjacent coordinates of particle i (rlepso_optimizer.py:179-195); FDR exemplars from KB.
 // CLPSO (:76-95): one Philox call carries the uniforms of an element PAIR (site ELEM_A, index e >> 1), another one (site TOURN, same
 // index) the two tournament pairs; the latter is only evaluated where a tournament is consumed, i.e. where !(u > pci_i).
@@ -581,8 +623,7 @@ __device__ __forceinline__ void rl_move(const MoveCtx& c, int i, int d0, double 
 {
     const RlLds& L = c.L;
     const int NP = c.NP, D = c.D;
-    const int rk = c.RANK[i], e0 = i * D + d0, es0 = rk * D + d0;
-    const double r1 = L.R1[i], r2 = L.R2[i];
+    const int rk = c.RANK[i], e0 = i * D + d0;
     // one Philox call carries the four element-wise uniforms of an element PAIR, 32 bits each (site ELEM_A, index e >> 1: words 0 / 2 = CLPSO
     // uniform / FDR weight of the even element, 1 / 3 of the odd one); a two-coordinate work item starts on an even element (D even, d0 even)
     double uf[W];
@@ -595,9 +636,6 @@ __device__ __forceinline__ void rl_move(const MoveCtx& c, int i, int d0, double 
         if (W == 2) { uf[0] = u32d(wa.z); uf[W - 1] = u32d(wa.w); }
         else uf[0] = u32d((e0 & 1) ? wa.w : wa.z);
     }
-    const int g = c.fg.div(i);
-    double cw = 0., c1 = 0., c2 = 0., c3 = 0., c4 = 0.;
-    if (g < c.G) { const double* k = L.COEF + g * 6; cw = k[1]; c1 = k[2]; c2 = k[3]; c3 = k[4]; c4 = k[5]; }
     double ucs[W]; int xrs[W];
     {
         const double pci = c.pci[i];
@@ -628,23 +666,75 @@ __device__ __forceinline__ void rl_move(const MoveCtx& c, int i, int d0, double 
             }
         }
     }
+    rl_move_apply<W, RES>(c, i, d0, rk, uf, ucs, xrs, cur, vel);
+}
+
+// ---- the move of the resident kernel with the tournaments COMPACTED per wave (k_rlepso_run, 256-thread geometries; no tape there)
+// rl_move runs the MBX_SITE_TOURN Philox call and the two tournament look-ups (about 35 + 30 vector instructions) in every wave-pass in which ONE lane consumes a
+// tournament; with pci between 0.05 and 0.5 about 18 % of the items do, so practically every wave-pass pays for them (8 per generation at NP 100 / D 10).  Here a
+// wave first draws MBX_SITE_ELEM_A for ALL its items (IT per lane; the four words stay in the lane's registers), the items that consume a tournament append their
+// number to the wave's own list (ballot + mbcnt: the position is the count of such lanes below, plus the wave's earlier passes), then the wave deals the listed items
+// 64 per step -- TOURN draw, both coordinates' tournaments, the two exemplar ranks written back OVER the list entry -- and every lane picks its entry up again: one
+// step per wave instead of IT (23 listed items per wave on average, 128 at most).  Same Philox counters (ELEM_A and TOURN at index it = e0 >> 1), same words, same
+// tie rule (the first candidate wins); a coordinate that consumes no tournament ignores the rank computed for it.
+//  * The list is the wave's slice of FL (64 IT entries), which the FDR pass has finished with behind its closing barrier and next touches behind the ranking barrier
+//    of the following generation: THREADS x IT < NI + THREADS <= 2 NI = NE entries, FL's size, wherever NI >= THREADS (rl_run_listed).
+//  * No barrier: writer and readers of an entry are lanes of ONE wave, whose LDS instructions execute in program order; the wavefront fences keep the compiler from
+//    reordering them.
+#ifndef MBX_RL_LISTED_TOURN
+#define MBX_RL_LISTED_TOURN 1       // 0: rl_move per item, as in k_rlepso_step (A/B and instruction-budget builds)
+#endif
+__host__ __device__ constexpr bool rl_run_listed(int threads, int ni) { return MBX_RL_LISTED_TOURN && threads == 256 && ni >= threads; }
+
+template <int THREADS, int NI, int HD, int IT>
+__device__ __forceinline__ void rl_move_listed(const MoveCtx& c, const FastDiv& fh, int tid, double (&vel)[IT][2])
+{
+    static_assert(NI >= THREADS && NI < 65536, "the wave lists fit FL, an item number fits an entry");
+    const RlLds& L = c.L;
+    uint16_t* WL = L.FL + (tid >> 6) * (64 * IT);
+    U4 wa[IT];
+    bool nd[IT][2];
+    int pos[IT];
+    int n = 0;                                                    // listed items of the wave so far (scalar)
 #pragma unroll
-    for (int q = 0; q < W; ++q) {
-        const int e = e0 + q, d = d0 + q;
-        const double pp = L.PB[es0 + q], uc = ucs[q];
-        const int xr = xrs[q], kb = L.KB[es0 + q];
-        const double ex = L.PB[xr * D + d];                        // CLPSO exemplar (own rank: the particle's own pbest)
-        const double v_fdr = uf[q] * (L.PB[kb * D + d] - pp);
-        const double v_pbest = r1 * (pp - cur[q]);
-        const double v_gbest = r2 * (L.GB[d] - cur[q]);
-        const double v_cl = uc * (ex - cur[q]);
-        double nv = cw * vel[q] + c1 * v_cl + c2 * v_fdr + c3 * v_gbest + c4 * v_pbest;
-        nv = fmin(fmax(nv, -c.vmax), c.vmax);
-        double np_ = cur[q] + nv;
-        np_ = fmin(fmax(np_, c.lb), c.ub);
-        L.X[e] = np_;
-        if (RES) { cur[q] = np_; vel[q] = nv; }
-        else { c.gPos[e] = np_; c.gVel[e] = nv; }
+    for (int j = 0; j < IT; ++j) {
+        // (a lane past the last item draws for the last item and lists nothing: a Philox call costs the wave the same with or without it, and without a branch the
+        // need bits stay compare masks on the scalar unit)
+        const int it = tid + j * THREADS, itc = it < NI ? it : NI - 1;
+        const double pci = c.pci[fh.div(itc)];
+        wa[j] = c.rng.draw((uint32_t)itc, MBX_SITE_ELEM_A);
+        nd[j][0] = it < NI && !(u32d(wa[j].x) > pci); nd[j][1] = it < NI && !(u32d(wa[j].y) > pci);
+        const bool any = nd[j][0] || nd[j][1];
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(any);
+        pos[j] = n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (any) WL[pos[j]] = (uint16_t)it;
+        n += __builtin_popcountll(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int s = tid & 63; s < n; s += 64) {
+        const U4 wt = c.rng.draw((uint32_t)WL[s], MBX_SITE_TOURN);
+        const int a1 = (int)__umulhi(wt.x, (uint32_t)c.NP), a2 = (int)__umulhi(wt.y, (uint32_t)c.NP);
+        const int b1 = (int)__umulhi(wt.z, (uint32_t)c.NP), b2 = (int)__umulhi(wt.w, (uint32_t)c.NP);
+        const int x0 = c.RANK[L.PBC[a2] < L.PBC[a1] ? a2 : a1], x1 = c.RANK[L.PBC[b2] < L.PBC[b1] ? b2 : b1];     // binary tournaments on pbest cost, first candidate wins ties
+        WL[s] = (uint16_t)(x0 | x1 << 8);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int j = 0; j < IT; ++j) {
+        const int it = tid + j * THREADS;
+        if (it < NI) {
+            const int i = fh.div(it), rk = c.RANK[i];
+            const uint32_t xw = nd[j][0] || nd[j][1] ? WL[pos[j]] : 0u;
+            const double2 c2 = *(const double2*)(L.X + 2 * it);
+            double cur[2] = {c2.x, c2.y};
+            const double uf[2] = {u32d(wa[j].z), u32d(wa[j].w)}, ucs[2] = {u32d(wa[j].x), u32d(wa[j].y)};
+            const int xrs[2] = {nd[j][0] ? (int)(xw & 255u) : rk, nd[j][1] ? (int)(xw >> 8) : rk};
+            rl_move_apply<2, true>(c, i, 2 * (it - i * HD), rk, uf, ucs, xrs, cur, vel[j]);
+        }
     }
 }
 
@@ -857,7 +947,7 @@ __global__ __launch_bounds__(THREADS) MBX_RL_WAVES void k_rlepso_step(BatchParam
 #endif
 
     // ---- velocity / position update (:179-195).  A work item is W adjacent dimensions of one particle (W = 2 when D is even).
-    const MoveCtx mc{L, bp.pci, tape, rng, gPos, gVel, ORDER, NLESS, RANK, NP, D, G, lb, ub, vmax, fg};
+    const MoveCtx mc{L, bp.pci, tape, rng, gPos, gVel, ORDER, NLESS, RANK, NP, D, G, lb, ub, vmax, fg, NPC > 0 && GC > 0 && NPC % (GC > 0 ? GC : 1) == 0};
     if ((D & 1) == 0) {
         const int HD = D >> 1, NI = NP * HD;
         const FastDiv fh(HD);
@@ -1146,7 +1236,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         __syncthreads();
         if (tid < NP) {
             const int i = tid, gi = fg.div(i);
-            L.CMUT[i] = gi < G ? L.COEF[gi * 6] * L.PNI[i] : 0.;
+            L.CMUT[i] = NP % G == 0 || gi < G ? L.COEF[gi * 6] * L.PNI[i] : 0.;      // (NP a multiple of G: every particle has a group)
             const U4 w = rng.draw((uint32_t)i, MBX_SITE_PART);
             L.R1[i] = u53(w.x, w.y); L.R2[i] = u53(w.z, w.w);
             const int rank = NLESS[i];
@@ -1195,21 +1285,24 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         // and the LDS reads per candidate, which costs more than the idle waves did.)
         // ---- velocity / position update (:179-195): new position -> X, new velocity -> register
         {
-            const MoveCtx mc{L, ar().bp.pci, nullptr, rng, nullptr, nullptr, ORDER, NLESS, RANK, NP, D, G, lb, ub, vmax, fg};
-#pragma unroll
-            for (int j = 0; j < IT; ++j) {
-                const int it = tid + j * THREADS;
-                if (it < NI) {
-                    const int i = fh.div(it);
-                    const double2 c2 = *(const double2*)(L.X + 2 * it);
-                    double cur[2] = {c2.x, c2.y};
+            const MoveCtx mc{L, ar().bp.pci, nullptr, rng, nullptr, nullptr, ORDER, NLESS, RANK, NP, D, G, lb, ub, vmax, fg, NP % G == 0};
 #ifndef MBX_ABLATE_MOVE
-                    rl_move<2, true>(mc, i, 2 * (it - i * HD), cur, vel[j]);
-#else
-                    (void)i; (void)cur;
-#endif
+            if constexpr (rl_run_listed(THREADS, NI)) rl_move_listed<THREADS, NI, HD, IT>(mc, fh, tid, vel);
+            else {
+#pragma unroll
+                for (int j = 0; j < IT; ++j) {
+                    const int it = tid + j * THREADS;
+                    if (it < NI) {
+                        const int i = fh.div(it);
+                        const double2 c2 = *(const double2*)(L.X + 2 * it);
+                        double cur[2] = {c2.x, c2.y};
+                        rl_move<2, true>(mc, i, 2 * (it - i * HD), cur, vel[j]);
+                    }
                 }
             }
+#else
+            (void)mc;
+#endif
         }
         __syncthreads();
         // ---- evaluate, update pbest / gbest and the stagnation counters (:198-233)

@@ -44,7 +44,11 @@ VARIANTS = {
     'no_commit': ['-DMBX_ABLATE_COMMIT'],
     'no_reinit_draw': ['-DMBX_ABLATE_REINIT_DRAW'],            # no draw, nobody re-initialised
     'no_log': ['-DMBX_ABLATE_LOG'],
+    # not ablations but A/B switches of the full kernel (same results): what one trim is worth, as full - variant (TRIMS)
+    'per_item_tourn': ['-DMBX_RL_LISTED_TOURN=0'],             # the move with one tournament draw per wave-pass, as k_rlepso_step has it
+    'round_bound': ['-DMBX_FDR_ROUND_BOUND'],                  # the scan's bound rounded up to whole unrolled groups (measured and dropped)
 }
+TRIMS = [('tournaments compacted per wave', 'full', 'per_item_tourn'), ('scan bound rounded up to whole groups (not shipped)', 'round_bound', 'full')]
 # phase -> (minuend variant, subtrahend variant): instructions of the phase = count(minuend) - count(subtrahend)
 PHASES = [
     ('policy draw', 'full', 'no_policy'),
@@ -61,7 +65,7 @@ PHASES = [
     ('logging, termination, reward', 'full', 'no_log'),
 ]
 KERNEL = '_ZN3mbx12k_rlepso_runILi256ELi100ELi10ELi5ELb1EE'
-CAVEATS = ('a row is only as good as its ablation: without the move or with the one-coordinate objective the swarms take another course (re-initialisation storms, early stops), so \'move: the rest\' and \'objective\' are NOT instruction counts of those phases; with zero-trip scan loops the compiler folds most of the scan\'s set-up, so \'FDR pass: scaffolding\' is a lower bound; rows within +-20 of zero are below the method\'s resolution')
+CAVEATS = ('a row is only as good as its ablation: without the move or with the one-coordinate objective the swarms take another course (re-initialisation storms, early stops), so \'move: the rest\' and \'objective\' are NOT instruction counts of those phases; with zero-trip scan loops the compiler folds most of the scan\'s set-up, so \'FDR pass: scaffolding\' is a lower bound; rows within +-20 of zero are below the method\'s resolution; with rank = index (no_rank) the cost column is not ascending, which the scan\'s near-tie flag (a_0 < 0) relies on: \'ranking\' is not a count of the ranking either')
 
 
 def build(a):
@@ -146,6 +150,7 @@ def write(a, counts, instances):
             ph['move: the rest'] = ph.pop('move: all') - ph['move: Philox']
         out['phases'] = {k: round(v, 1) for k, v in ph.items()}
         out['total'] = round(counts['full'], 1)
+        out['trims'] = {n: round(counts[p] - counts[m], 1) for n, p, m in TRIMS if p in counts and m in counts}
         valid = sum(v for k, v in ph.items() if k not in ('objective', 'move: the rest'))      # (see CAVEATS)
         out['not attributed by a valid ablation (objective, the move without its Philox calls, policy coefficients, block set-up, interactions)'] = round(counts['full'] - valid, 1)
     os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
