@@ -7,7 +7,7 @@
 // So a size and its pointers cannot disagree.  All extents are in doubles; the base is 16-byte aligned and every extent is even, so every array
 // starts 16-byte aligned.  Arrays that share storage (an area that is dead while another phase uses it) are walks too: a second cursor starts
 // at the same place, and the enclosing take asks for where it ends, or for the longest of the alternatives.  (Eight families keep a carve written out by
-// hand beside their walk -- dq, dd, jd, md, sd, nr, ql, rp: their kernels measured slower, or in md's case computed other bytes, through the walk.  Their
+// hand beside their walk -- dq, dd, jd, md, sd, nr, ql, rp: their kernels measured slower through the walk.  Their
 // sizes are the walks', and tests/lds_sizes_main.hip holds every hand-written pointer to the walk's.  k_rs_population and k_eval carve inline in their kernels, as
 // they always did; only their sizes come from rs_layout / ev_layout.)
 #pragma once
@@ -387,8 +387,15 @@ struct MdLds {
     uint8_t* MU;
     __device__ __forceinline__ EvalLds eval(int ch, int D, double* f) const
     {
+#ifdef MBX_MD_WALK_CARVE
+        LdsCarve c{EV};
+        double *X, *T, *Z;
+        lds_eval_rows(c, ch, D, X, T, Z);
+        return EvalLds{X, Z, T, M1T, M2T, DSH, V0, V1, V2, f};
+#else
         double* T = EV + align2((int64_t)ch * D);
         return EvalLds{EV, T + eval_t_doubles(ch, D), T, M1T, M2T, DSH, V0, V1, V2, f};
+#endif
     }
 };
 
@@ -419,9 +426,12 @@ MBX_LDS_WALK MdLds md_layout(C& c, int NP, int D)
     return L;
 }
 __host__ __device__ inline int64_t md_lds_doubles(int NP, int D) { LdsSize c; md_layout(c, NP, D); return c.n; }
-// The carve-up and MdLds::eval stay written out by hand, so that the sorted-DE kernels compile as before: carved through md_layout, k_nlshade_run computed other bytes
-// than the parent on the MI355X (a gbest with the bit pattern of two small ints; the int / double reuse of L.CNT as PMIN is suspected, not established:
-// docs/EXPERIMENTS.md "One walk per LDS layout").  The size above is the walk's, and tests/lds_sizes_main.hip holds these pointers to the walk's over its grid.
+// The carve-up and MdLds::eval stay written out by hand for time: through the walk k_nlshade_step measured 2.1 % slower (docs/EXPERIMENTS.md "One walk per LDS
+// layout").  -DMBX_MD_WALK_CARVE (the Makefile's EXTRA) builds both through md_layout / lds_eval_rows instead: same pointers, other register allocation.  That form
+// once made k_nlshade_run write a gbest with the bit pattern of two small ints from the second update of a launch on; the cause was the compiler's, not the layout's
+// (register copies placed ahead of the exec restore of a join block: docs/EXPERIMENTS.md "NL_SHADE_LBC: the multi-update garbage"), and the multi-update tests of
+// tests/test_nlshade.py are what holds either form to the one-update launches.  The size above is the walk's, and tests/lds_sizes_main.hip holds these pointers to
+// the walk's over its grid.
 __host__ __device__ inline int64_t md_ev_doubles(int ch, int D)
 {
     const int64_t ne = (int64_t)ch * D;
@@ -441,6 +451,10 @@ __host__ __device__ inline int64_t md_lds_hand_doubles(int NP, int D)
 }
 __host__ __device__ __forceinline__ MdLds md_carve(double* base, int NP, int D)
 {
+#ifdef MBX_MD_WALK_CARVE
+    LdsCarve c{base};
+    return md_layout(c, NP, D);
+#else
     const int64_t DD = align2((int64_t)D * D);
     MdLds L;
     double* p = base;
@@ -453,6 +467,7 @@ __host__ __device__ __forceinline__ MdLds md_carve(double* base, int NP, int D)
     L.LIST = reinterpret_cast<int*>(p); p += align2((NP + 1) / 2);
     L.MU = reinterpret_cast<uint8_t*>(p);
     return L;
+#endif
 }
 
 __host__ __device__ inline int64_t nl_lds_doubles(int N0, int D) { return md_lds_doubles(N0, D); }

@@ -66,6 +66,11 @@ __device__ __forceinline__ int nl_choice(const double* cdf, int n, double u)
     return min(lo, n - 1);
 }
 
+// np.min over two runs of costs, a standing before b: NaN if either is, else the first-seen minimum (which decides the sign of a zero).  One step of
+// `m = INFINITY; for v: if (isnan(v) || isnan(m)) m = NAN; else if (v < m) m = v;` is m = nl_min_seen(m, v).
+__device__ __forceinline__ double nl_min_seen(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (b < a ? b : a); }
+static_assert(kThreads == 4 * 64, "the update folds the minimum over four waves of 64 lanes");
+
 // ------------------------------------------------------------------------------------------------ reset (__init_population :149-160)
 __global__ __launch_bounds__(kThreads) void k_nlshade_reset(BatchParams bp, double* __restrict__ state_out)
 {
@@ -145,7 +150,6 @@ __device__ __forceinline__ void nl_updates(const BatchParams& bp, int n_updates,
     double* gCv = S + MBX_NLSHADE_ST_C(N0, D);
     double* gU2 = S + MBX_NLSHADE_ST_U2(N0, D);
     double* carry = S + MBX_NLSHADE_ST_CARRY(N0, D);
-    double* PMIN = reinterpret_cast<double*>(L.CNT);                 // per-thread minima of the trial costs (CNT is free between the scans)
     double* CDF = L.EV;
     const int episode = (int)sc[MBX_SC_EPISODE];
     stage_problem(P, L.eval(CH, D, L.TC));
@@ -284,16 +288,13 @@ __device__ __forceinline__ void nl_updates(const BatchParams& bp, int n_updates,
             ocnt[0] += nc < gC[i];
             if (isnan(nc) || isnan(tmin)) tmin = NAN; else if (nc < tmin) tmin = nc;
         }
+        // (nl_min_seen is associative, so the wave's lanes, and then the four waves, fold in any grouping that keeps thread order; a lane whose partner
+        // lies beyond the wave folds with itself; the barriers of the scan stand between RED[4 .. 7] and their reader)
+        for (int off = 1; off < 64; off <<= 1) tmin = nl_min_seen(tmin, __shfl_down(tmin, off));
+        if ((tid & 63) == 0) L.RED[4 + (tid >> 6)] = tmin;
         md_scan3(L.CNT, ocnt, obase, otot);
-        PMIN[tid] = tmin;
         const int n_opt = otot[0], n_app = min(max(NA - narc, 0), n_opt), alen = narc + n_app;
-        __syncthreads();
-        if (tid == 0) {
-            double m = INFINITY;
-            const int used = min((NP + per - 1) / per, kThreads);
-            for (int t = 0; t < used; ++t) { const double v = PMIN[t]; if (isnan(v) || isnan(m)) m = NAN; else if (v < m) m = v; }
-            L.RED[1] = m;
-        }
+        if (tid == 0) L.RED[1] = nl_min_seen(nl_min_seen(L.RED[4], L.RED[5]), nl_min_seen(L.RED[6], L.RED[7]));
         // ---- archive (:129-133, :244-245): the parent of rank k is population row k
         if (n_opt > 0 && alen > 0) {
             auto target = [&](int k) -> int {

@@ -949,6 +949,72 @@ def test_hip_nlshade_routes_are_bit_identical():
         x.close()
 
 
+def _sound_gbest(gbest, log, where):
+    """gbest and the curve are costs the kernel computed: 0 or a normal number (a denormal is what ints read as a double look like), the curve
+    never rises and never lies below gbest."""
+    assert np.all((log == 0.) | (np.abs(log) >= 1e-300)) and (gbest == 0. or abs(gbest) >= 1e-300), (*where, gbest, log)
+    assert np.all(np.diff(log) <= 0.) and gbest <= log.min(), (*where, gbest, log)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dim,max_fes,chunks,pers', [(12, 1500, (2, 1, 5), (2, 1, 1)), (40, 6000, (1, 2, 5), (4, 3, 2, 2, 2, 1, 1))])
+def test_hip_nlshade_routes_are_bit_identical_where_a_thread_owns_several_rows(dim, max_fes, chunks, pers):
+    """The comparison of test_hip_nlshade_routes_are_bit_identical at N0 > 256, where a thread owns `per` = ceil(NP / 256) > 1 rows: launches of
+    `chunks` updates and then the rest of the episode, so that `per` changes inside a launch and a launch starts inside the per > 1 stretch
+    (D = 12: 276, 131 rows; D = 40: 920, 516, 401, 318, 259, 214 rows).  After every launch gbest of every instance is a sound cost
+    (`_sound_gbest`) and equals the least cost of its population (the best row is never replaced by a worse one nor cut by the reduction).  After
+    every update of the mbx_step route gbest is the least entry of the curve whenever the update logged one, and never above it otherwise (the
+    curve holds gbest at the log points only, so between them gbest may lie below it)."""
+    import torch
+    from metabox_amd.suite import Batch, Suite
+    ps = {**problems('bbob', dim), **problems('bbob-noisy', dim)}
+    ids = [1, 5, 8, 15, 21, 24, 103, 117]
+    assert sum(ps[i].noise[0] != 0 for i in ids) >= 1
+    B, n0 = len(ids), geom(dim)[0]
+    total = NL_SHADE_LBC.n_updates(dim, max_fes)
+    live = np.minimum.accumulate(NL_SHADE_LBC.n_schedule(dim, max_fes))
+    assert n0 > 256 and tuple(-(-int(n) // 256) for n in live[:len(pers)]) == pers and live[-1] == 4
+    s = Suite([ps[i] for i in ids])
+    mk = lambda: Batch(s, ALGO_NLSHADE, np.arange(B, dtype=np.int32), np.arange(B, dtype=np.uint64) * 7919 + 3, n0, max_fes, max_fes // NLOG, NLOG)      # noqa: E731
+    a, s1, st = mk(), mk(), mk()
+    for x in (a, s1, st):
+        x.reset()
+    logged = 0
+    for n in (*chunks, total - sum(chunks)):
+        a.nlshade_run(n)
+        for _ in range(n):
+            s1.nlshade_run(1)
+            before = [(pub[SC_COST_LEN], pub[SC_DONE]) for pub in (st.read_public(k).copy() for k in range(B))]
+            st.step(None)
+            for k in range(B):
+                pub = st.read_public(k)
+                gbest, log = pub[SC_GBEST], pub[16:16 + int(pub[SC_COST_LEN])]
+                _sound_gbest(gbest, log, (ids[k], 'mbx_step'))
+                if pub[SC_COST_LEN] > before[k][0] and not before[k][1]:
+                    assert gbest == log.min() == log[-1], (ids[k], gbest, log)
+                    logged += 1
+        torch.cuda.synchronize()
+        for k in range(B):
+            blk = a.read_state(k)
+            assert np.array_equal(blk, s1.read_state(k), equal_nan=True) and np.array_equal(blk, st.read_state(k), equal_nan=True), (ids[k], n)
+            f = from_block(blk, dim)
+            _sound_gbest(f['gbest'], np.asarray(f['log']), (ids[k], n))
+            assert f['gbest'] == np.nanmin(f['cost']), (ids[k], n, f['gbest'], f['cost'][:4])
+    assert logged >= B * NLOG // 2
+    full = 0
+    for k in range(B):
+        f = from_block(a.read_state(k), dim)
+        assert f['done'], ids[k]
+        if f['fes'] >= max_fes:
+            assert f['scalars'][SC_GEN] == total and len(f['cost']) == 4, (ids[k], f['scalars'])
+            full += 1
+        else:
+            assert f['gbest'] <= 1e-8, (ids[k], f['gbest'])
+    assert full > 0
+    for x in (a, s1, st):
+        x.close()
+
+
 def _u53(w0, w1):
     return ((w0 >> 5) * 67108864.0 + (w1 >> 6)) / 9007199254740992.0
 
