@@ -412,6 +412,27 @@ int mbx_nrlpso_rollout(mbx_batch* b, const double* d_q_table, int n_steps, int32
  * op: 0 log, 1 exp, 2 sin, 3 cos, 4 pow(x, y), 5 T_osz(x) (bbob.py:51-67), 6 T_asy(x; beta_lin = y) (bbob.py:70-82). */
 int mbx_debug_math(int op, const double* d_x, const double* d_y, double* d_out, int n, void* stream);
 
+/* Test / diagnostics: the numpy-order sums and the order primitives the step kernels share, run on n_cases vectors by the routines the kernels call
+ * (csrc/mbx_npsum.hpp, mbx_depop.hpp, mbx_jde21.hpp, mbx_device.hpp).  Case c is d_x[d_off[c] .. d_off[c + 1]), d_off int32 [n_cases + 1].  By op:
+ *   NP_SUM_BLOCK (length <= 128), NP_SUM (<= 256), MD_PAIRWISE (<= 3200): one thread per case; d_out float64 [n_cases], np.add.reduce of the case.
+ *   NP_SUM_LANES8 (<= 128): one wave per case, every lane calls; d_out float64 [n_cases, 64], every lane's answer.
+ *   NP_SUM_LANES8_GROUPS (<= 128): one wave per eight cases, the eight lanes of group g sum case 8 w + g; d_out float64 [n_cases, 8].
+ *   JD_DIST4: a case is the four rows pa | pb | ua | ub of length D <= 128 each; d_out float64 [n_cases, 4] = the squared distances
+ *     |pa - ua|, |pb - ua|, |pa - ub|, |pb - ub|, each np.sum((p - u) ** 2).
+ *   BLOCK_ARGMIN (length >= 1, whatever fits in LDS): one workgroup per case, the vector in LDS; d_out float64 [n_cases, 2] = (value, index).
+ *   MD_SORT (1 <= length <= 3200): one workgroup per case, keys and rows padded to P = the next power of two >= max(length, 2) with +inf keys and the rows
+ *     length .. P - 1, as the sorted-DE kernels pad them; d_out int32, the P rows in sorted order, case after case (P differs from case to case).
+ * Reads d_off back (synchronises the stream) to check the lengths; MBX_E_ARG for a null pointer, a length outside the bounds above, or more LDS than a workgroup has. */
+#define MBX_DBG_NP_SUM_BLOCK         0
+#define MBX_DBG_NP_SUM               1
+#define MBX_DBG_MD_PAIRWISE          2
+#define MBX_DBG_NP_SUM_LANES8        3
+#define MBX_DBG_NP_SUM_LANES8_GROUPS 4
+#define MBX_DBG_JD_DIST4             5
+#define MBX_DBG_BLOCK_ARGMIN         6
+#define MBX_DBG_MD_SORT              7
+int mbx_debug_reduce(int op, const double* d_x, const int32_t* d_off, int n_cases, void* d_out, void* stream);
+
 /* Test / diagnostics: the element-wise Philox draws of RLEPSO's move phase (include/mbx_layout.h section 3: sites ELEM_A and TOURN) of the instance with
  * key `seed` at generation `gen` of episode `episode`, converted exactly as the generation kernel converts them: d_out [np * dim, 4] float64 =
  * {CLPSO uniform in [0, 1), FDR weight in [0, 1), tournament candidate 1, tournament candidate 2 (integers in [0, np))} per element

@@ -169,6 +169,7 @@ def load_lib():
         'mbx_nlshade_run': (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
         'mbx_gleet_policy': (C.c_int, [vp, C.POINTER(GleetActor), vp, vp, vp, vp]),
         'mbx_debug_math': (C.c_int, [C.c_int, vp, vp, vp, C.c_int, vp]),
+        'mbx_debug_reduce': (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp]),
         'mbx_debug_rlepso_draws': (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         'mbx_batch_launch_info': (C.c_int, [vp, C.POINTER(C.c_int32)]),
         'mbx_instance_state_doubles': (i64, [vp]),
@@ -194,11 +195,11 @@ EXPORTED_SYMBOLS = ('mbx_suite_create', 'mbx_suite_destroy', 'mbx_suite_size', '
                     'mbx_tape_stride', 'mbx_batch_create', 'mbx_batch_destroy', 'mbx_batch_flags', 'mbx_set_tape', 'mbx_reset', 'mbx_step', 'mbx_results',
                     'mbx_gauss_policy', 'mbx_lde_policy', 'mbx_ddqn_qnet', 'mbx_rlepso_policy_table_rows', 'mbx_rlepso_policy_table', 'mbx_rlepso_act_step',
                     'mbx_rlepso_rollout_resident', 'mbx_rlepso_rollout', 'mbx_lde_rollout_resident', 'mbx_lde_rollout', 'mbx_rlpso_rollout',
-                    'mbx_qlpso_rollout', 'mbx_dedqn_rollout', 'mbx_nrlpso_rollout', 'mbx_gleet_policy', 'mbx_debug_math', 'mbx_debug_rlepso_draws', 'mbx_batch_launch_info', 'mbx_instance_state_doubles',
+                    'mbx_qlpso_rollout', 'mbx_dedqn_rollout', 'mbx_nrlpso_rollout', 'mbx_gleet_policy', 'mbx_debug_math', 'mbx_debug_reduce', 'mbx_debug_rlepso_draws', 'mbx_batch_launch_info', 'mbx_instance_state_doubles',
                     'mbx_debug_read_state', 'mbx_debug_write_state', 'mbx_debug_clock_probe', 'mbx_debug_clock_mark', 'mbx_debug_clock_slots',
                     'mbx_batch_rebind', 'mbx_read_public', 'mbx_last_error', 'mbx_version')
 
-# the entry points of include/mbx_les.h (LES), beside the 44 of include/mbx.h
+# the entry points of include/mbx_les.h (LES), beside the 45 of include/mbx.h
 LES_SYMBOLS = ('mbx_les_set_params', 'mbx_les_rollout')
 
 # the entry point of include/mbx_rlhpsde.h (RL-HPSDE)

@@ -1590,6 +1590,105 @@ extern "C" int mbx_debug_math(int op, const double* d_x, const double* d_y, doub
     return MBX_OK;
 }
 
+// Test / diagnostics: the numpy-order sums and the order primitives the step kernels share, run as those kernels run them (mbx_npsum.hpp, mbx_depop.hpp,
+// mbx_jde21.hpp, mbx_device.hpp: the routines themselves, nothing restated here).  Case c is x[off[c] .. off[c + 1]).
+// The single-thread sums: one thread per case.
+__global__ void k_debug_sum(int op, const double* __restrict__ x, const int32_t* __restrict__ off, int n_cases, double* __restrict__ out)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_cases) return;
+    const double* a = x + off[c];
+    const int n = off[c + 1] - off[c];
+    if (op == MBX_DBG_NP_SUM_BLOCK) out[c] = np_sum_block([&](int k) { return a[k]; }, n);
+    else if (op == MBX_DBG_NP_SUM) out[c] = np_sum([&](int k) { return a[k]; }, n);
+    else if (op == MBX_DBG_MD_PAIRWISE) out[c] = md_pairwise(a, n);
+    else {                                                           // MBX_DBG_JD_DIST4: the rows pa | pb | ua | ub
+        const int D = n / 4;
+        double s[4];
+        jd_dist4(a, a + D, a + 2 * D, a + 3 * D, D, s);
+        for (int q = 0; q < 4; ++q) out[4 * c + q] = s[q];
+    }
+}
+
+// np_sum_lanes8: one wave per workgroup and every lane calls.  grouped = 0: the wave sums case blockIdx.x, every lane's answer is kept.  grouped = 1: the
+// eight lanes of group g sum case 8 blockIdx.x + g (a group without a case sums nothing), so the eight groups of a wave hold different data.
+__global__ __launch_bounds__(64) void k_debug_lanes8(int grouped, const double* __restrict__ x, const int32_t* __restrict__ off, int n_cases, double* __restrict__ out)
+{
+    const int lane = threadIdx.x, c = grouped ? blockIdx.x * 8 + (lane >> 3) : (int)blockIdx.x;
+    const bool live = c < n_cases;
+    const double* a = x + (live ? off[c] : 0);
+    const int n = live ? off[c + 1] - off[c] : 0;
+    const double s = np_sum_lanes8([&](int k) { return a[k]; }, n);
+    if (live) out[grouped ? c * 8 + (lane & 7) : c * 64 + lane] = s;
+}
+
+// block_argmin: one workgroup per case, the vector in LDS as the step kernels hold their costs.
+__global__ __launch_bounds__(kThreads) void k_debug_argmin(const double* __restrict__ x, const int32_t* __restrict__ off, double* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int c = blockIdx.x, tid = threadIdx.x, n = off[c + 1] - off[c];
+    double* A = smem;
+    double* RED = smem + align2(n);
+    for (int i = tid; i < n; i += kThreads) A[i] = x[off[c] + i];
+    __syncthreads();
+    double v; int i;
+    block_argmin(A, n, RED, v, i);
+    if (tid == 0) { out[2 * c] = v; out[2 * c + 1] = (double)i; }
+}
+
+// md_sort: one workgroup per case, KEY / IDX staged and padded as md_init_sorted stages them; the whole padded permutation goes out, case after case.
+__global__ __launch_bounds__(kThreads) void k_debug_sort(const double* __restrict__ x, const int32_t* __restrict__ off, int32_t* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int c = blockIdx.x, tid = threadIdx.x, n = off[c + 1] - off[c], npad = md_pad(n);
+    int64_t o = 0;
+    for (int k = 0; k < c; ++k) o += md_pad(off[k + 1] - off[k]);
+    double* KEY = smem;
+    int* IDX = reinterpret_cast<int*>(smem + npad);
+    for (int t = tid; t < npad; t += kThreads) { KEY[t] = t < n ? x[off[c] + t] : INFINITY; IDX[t] = t; }
+    __syncthreads();
+    md_sort(KEY, IDX, npad);
+    for (int t = tid; t < npad; t += kThreads) out[o + t] = IDX[t];
+}
+
+extern "C" int mbx_debug_reduce(int op, const double* d_x, const int32_t* d_off, int n_cases, void* d_out, void* stream)
+{
+    static const int kMaxLen[] = {128, 256, 3200, 128, 128, 4 * 128, 0, 3200};       // by op; block_argmin: what fits in LDS
+    if (op < 0 || op > MBX_DBG_MD_SORT || !d_x || !d_off || !d_out || n_cases < 0) return fail(MBX_E_ARG, "mbx_debug_reduce: bad arguments");
+    if (n_cases == 0) return MBX_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t> off((size_t)n_cases + 1);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(off.data(), d_off, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int longest = 0;
+    for (int c = 0; c < n_cases; ++c) {
+        const int n = off[c + 1] - off[c];
+        const bool sized = op == MBX_DBG_BLOCK_ARGMIN ? n >= 1 : op == MBX_DBG_MD_SORT ? n >= 1 && n <= kMaxLen[op]
+                         : op == MBX_DBG_JD_DIST4 ? n >= 4 && n % 4 == 0 && n <= kMaxLen[op] : n >= 0 && n <= kMaxLen[op];
+        if (off[c] < 0 || !sized) return fail(MBX_E_ARG, "mbx_debug_reduce: op %d does not take case %d of %d values at offset %d", op, c, n, off[c]);
+        longest = std::max(longest, n);
+    }
+    if (op <= MBX_DBG_MD_PAIRWISE || op == MBX_DBG_JD_DIST4)
+        hipLaunchKernelGGL(k_debug_sum, dim3((n_cases + 63) / 64), dim3(64), 0, st, op, d_x, d_off, n_cases, (double*)d_out);
+    else if (op == MBX_DBG_NP_SUM_LANES8 || op == MBX_DBG_NP_SUM_LANES8_GROUPS) {
+        const int grouped = op == MBX_DBG_NP_SUM_LANES8_GROUPS;
+        hipLaunchKernelGGL(k_debug_lanes8, dim3(grouped ? (n_cases + 7) / 8 : n_cases), dim3(64), 0, st, grouped, d_x, d_off, n_cases, (double*)d_out);
+    } else {
+        const bool sort = op == MBX_DBG_MD_SORT;
+        const size_t lds = sort ? (size_t)md_pad(longest) * (sizeof(double) + sizeof(int)) : (size_t)(align2(longest) + 2) * sizeof(double);
+        if (lds > (size_t)max_lds_bytes()) return fail(MBX_E_ARG, "mbx_debug_reduce: a case of %d values needs %zu B of LDS (> %d)", longest, lds, max_lds_bytes());
+        if (sort) {
+            HIP_TRY(hipFuncSetAttribute((const void*)k_debug_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_debug_sort, dim3(n_cases), dim3(kThreads), lds, st, d_x, d_off, (int32_t*)d_out);
+        } else {
+            HIP_TRY(hipFuncSetAttribute((const void*)k_debug_argmin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_debug_argmin, dim3(n_cases), dim3(kThreads), lds, st, d_x, d_off, (double*)d_out);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return MBX_OK;
+}
+
 extern "C" int64_t mbx_instance_state_doubles(const mbx_batch* b)
 {
     if (!b) return fail(MBX_E_ARG, "null batch");

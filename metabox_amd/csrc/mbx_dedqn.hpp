@@ -84,6 +84,7 @@ __device__ void dd_features(const PT& P, const DdLds& L, int NP, int D, const Rn
         for (int j = 0; j < NP; ++j) { const double dj = L.DIST[j]; rank += (dj < di) || (dj == di && j < tid); }
         L.SORTED[rank] = L.SCOST[tid];
     }
+    static_assert(MBX_DEDQN_NP_MAX <= 128, "np_sum_lanes8 is numpy's order for n <= 128: the NP sums below rest on dedqn_check's np <= MBX_DEDQN_NP_MAX");
     if (wave == 2) {
         const double m = np_sum_lanes8([&](int i) { return L.SCOST[i]; }, NP) / NP;
         if (lane == 0) L.RED[2] = m;

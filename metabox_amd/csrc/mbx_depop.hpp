@@ -12,6 +12,7 @@
 #pragma once
 #include "mbx_device.hpp"
 #include "mbx_lds.hpp"
+#include "mbx_npsum.hpp"    // np_sum_block, np_pairwise: numpy's pairwise summation order
 
 namespace mbx {
 
@@ -35,35 +36,16 @@ __device__ __forceinline__ void md_scan3(int* CNT, const int (&c)[3], int (&base
     __syncthreads();
 }
 
-// numpy's pairwise sum of a contiguous vector: a block of at most 128 elements ...
+// numpy's pairwise sum of a contiguous vector, mbx_npsum.hpp's block and halving: the block out of line (the recursion below names it 64 times) ...
 __device__ __noinline__ double md_pw_leaf(const double* a, int n)
 {
-    if (n < 8) {
-        double r = 0.;
-        for (int i = 0; i < n; ++i) r += a[i];
-        return r;
-    }
-    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-        r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3]; r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
-    }
-    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; i < n; ++i) res += a[i];
-    return res;
+    return np_sum_block([a](int i) { return a[i]; }, n);
 }
-// ... and the halving recursion above that, DEPTH levels of it: 128 << DEPTH elements at least (n2 is rounded down, so the right half may
-// be the longer one by up to 8 + 1: the depth is chosen with a level to spare)
+// ... and DEPTH levels of halving above it: 128 << DEPTH elements at least (the right half may be the longer one: the depth is chosen with a level to spare)
 template <int DEPTH>
 __device__ __forceinline__ double md_pw(const double* a, int n)
 {
-    if (n <= 128) return md_pw_leaf(a, n);
-    if constexpr (DEPTH == 0) return NAN;
-    else {
-        int n2 = n / 2;
-        n2 -= n2 % 8;
-        return md_pw<DEPTH - 1>(a, n2) + md_pw<DEPTH - 1>(a + n2, n - n2);
-    }
+    return np_pairwise<DEPTH>([a](int off, int m) { return md_pw_leaf(a + off, m); }, 0, n);
 }
 __device__ __forceinline__ double md_pairwise(const double* a, int n) { return md_pw<6>(a, n); }      // n <= 3200
 

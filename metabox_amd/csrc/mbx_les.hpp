@@ -222,6 +222,7 @@ __global__ __launch_bounds__(kThreads) void k_les_run(BatchParams bp, LesArgs ar
         const Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)(t + 1), episode};
         if (tid < 64) {                                              // ---- the two networks and the D-wide update (:130-143), wave 0
             if (tid < NP) {                                          // cal_attn_feature (:86-95), then Q, K, V of row tid
+                static_assert(NP <= 128, "np_sum_block is numpy's order for n <= 128");
                 const double mean = np_sum_block([&](int k) { return L.NC[k]; }, NP) / NP;
                 const double var = np_sum_block([&](int k) { const double x = L.NC[k] - mean; return x * x; }, NP) / NP;
                 const double c = L.NC[tid];

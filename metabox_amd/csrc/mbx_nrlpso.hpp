@@ -32,6 +32,7 @@ struct NrTraj { int32_t* actions; double* state; double* reward; int32_t* last_a
 // The LDS layout (NrLds, kNrK, nr_stride, nr_lds_doubles, nr_carve) lives in mbx_lds.hpp.
 
 // sqrt(np.sum((a - b) ** 2, -1)) of two rows
+static_assert(MBX_NRLPSO_DIM_MAX <= 128 && MBX_NRLPSO_NP_MAX <= 128, "np_sum_block is numpy's order for n <= 128: the D and NP sums of this file rest on nrlpso_check's limits");
 __device__ __forceinline__ double nr_dist(const double* a, const double* b, int D)
 {
     return sqrt(np_sum_block([&](int d) { const double t = a[d] - b[d]; return t * t; }, D));

@@ -19,6 +19,7 @@ namespace mbx {
 // The LDS layout (QlLds, ql_lds_doubles, ql_carve) and MBX_N4_WAVES live in mbx_lds.hpp.
 
 // __cal_diversity (:45-46) of the population in L.POP.  All threads call; the value is returned to every thread.
+static_assert(kThreads <= 256, "np_sum is numpy's order for n <= 256: NP by check_np (np <= kThreads), D by check_dim (dim <= 64)");
 __device__ __forceinline__ double ql_diversity(const QlLds& L, int NP, int D)
 {
     const int tid = threadIdx.x;

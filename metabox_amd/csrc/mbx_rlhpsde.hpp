@@ -110,6 +110,7 @@ __device__ void hp_walk_state(const PT& P, const MdLds& L, double* FT, double* S
                  MBX_SITE_HP_WNOISE_A, MBX_SITE_HP_WNOISE_B);
     if (tid < kHpWalk) gWC[tid] = WC[tid];
     // ---- distances to row 0 (np.linalg.norm(., axis=-1): sqrt of a pairwise row sum) and the first differences
+    static_assert(MBX_RLHPSDE_DIM_MAX <= 128 && kHpSteps <= 256, "np_sum_block / np_sum are numpy's order for n <= 128 / 256: D by rlhpsde_check, the walk by its constant");
     if (tid < kHpSteps) {
         const double* x = W + (int64_t)(tid + 1) * D;
         DIST[tid] = sqrt(np_sum_block([&](int d) { const double t = x[d] - best[d]; return t * t; }, D));

@@ -273,6 +273,7 @@ __global__ __launch_bounds__(kThreads) void k_sahlpso_generation(BatchParams bp,
                 for (int j = 0; j < kShHcr; ++j) { const double nf = L.NFCR[j]; const double v = nf != 0. ? L.NSCR[j] / nf : 0.; L.RED[j] = v; sum += v; }
                 for (int j = 0; j < kShHcr; ++j) L.PCR[j] = sum == 0. ? 1. / kShHcr : L.RED[j] / sum;      // (sum == 0: the departure, see the header)
                 for (int j = 0; j < kShHls; ++j) { const double nf = L.NFLS[j]; L.RED[j] = nf != 0. ? L.NSLS[j] / nf : 0.; }
+                static_assert(kShHls <= 128, "np_sum_block is numpy's order for n <= 128");
                 const double sl = np_sum_block([&](int j) { return L.RED[j]; }, kShHls);
                 for (int j = 0; j < kShHls; ++j) L.PLS[j] = sl == 0. ? 1. / kShHls : L.RED[j] / sl;
             }

@@ -413,7 +413,7 @@ def test_abi_geometry_of_nrlpso():
         bad = oracle.make_cfg(algo, 100, 10, 20000, 400, 50)
         assert lib.mbx_state_dim(C.byref(bad)) < 0 and lib.mbx_tape_stride(C.byref(bad)) < 0
     assert state_off(100, 10, 50)['end'] == 4 * 1000 + 4 * 100 + 500 + 8 + 10 + 8 + 16 + 51
-    assert 'mbx_nrlpso_rollout' in _abi.EXPORTED_SYMBOLS and len(_abi.EXPORTED_SYMBOLS) == 44 and hasattr(lib, 'mbx_nrlpso_rollout')
+    assert 'mbx_nrlpso_rollout' in _abi.EXPORTED_SYMBOLS and len(_abi.EXPORTED_SYMBOLS) == 45 and hasattr(lib, 'mbx_nrlpso_rollout')
 
 
 def test_registered_by_name():

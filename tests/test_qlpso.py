@@ -70,7 +70,8 @@ def test_oracle_replays_reference_qlpso_episode(case):
 def test_numpy_summation_order_of_the_diversity():
     """The oracle's diversity equals numpy's own evaluation of the reference expression bit for bit (pairwise summation)."""
     rs = np.random.RandomState(3)
-    for NPx, D in ((30, 10), (30, 7), (100, 30), (200, 40)):
+    # above 128 values numpy halves, and from 249 to 255 the right half (129 .. 135 values) halves again: the lengths 129, 248, 249, 255 and 256
+    for NPx, D in ((30, 10), (30, 7), (100, 30), (200, 40), (129, 2), (248, 13), (249, 2), (255, 13), (256, 10)):
         pop = rs.rand(NPx, D) * 10 - 5
         want = np.mean(np.sqrt(np.sum(np.square(pop - np.mean(pop, 0)), 1)))
         cfg = oracle.make_cfg(ALGO_QLPSO, NPx, D, 10 * NPx, NPx, 5)

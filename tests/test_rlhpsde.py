@@ -524,11 +524,11 @@ def test_abi_geometry_of_rlhpsde():
         assert ok(**bad) < 0 and b'RL-HPSDE' in lib.mbx_last_error(), bad
     for algo in (12, 14, 17, 22, 23):                                # stay unassigned
         assert lib.mbx_state_dim(C.byref(oracle.make_cfg(algo, 180, 10, 20000, 400, NLOG))) < 0
-    # the entry point lives in a header of its own: include/mbx_rlhpsde.h declares exactly it, the library exports it, include/mbx.h keeps its 44
+    # the entry point lives in a header of its own: include/mbx_rlhpsde.h declares exactly it, the library exports it, include/mbx.h keeps its 45
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     declared = set(re.findall(r'\b(mbx_rlhpsde_[a-z_]+)\s*\(', open(os.path.join(root, 'include', 'mbx_rlhpsde.h')).read()))
     assert declared == set(_abi.RLHPSDE_SYMBOLS) == {'mbx_rlhpsde_rollout'} and all(hasattr(lib, n) for n in declared)
-    assert not declared & set(_abi.EXPORTED_SYMBOLS) and len(_abi.EXPORTED_SYMBOLS) == 44
+    assert not declared & set(_abi.EXPORTED_SYMBOLS) and len(_abi.EXPORTED_SYMBOLS) == 45
     assert 'mbx_rlhpsde' not in open(os.path.join(root, 'include', 'mbx.h')).read().replace('include/mbx_rlhpsde.h', '')
     assert lib.mbx_rlhpsde_rollout(None, None, 1, None, None, None, None, None, None, None, None) < 0 and b'mbx_rlhpsde_rollout' in lib.mbx_last_error()
     assert state_off(10)['end'] == 3 * 180 * 10 + 9 * 180 + 10 + WALK * 11 + 64 + 16 + NLOG + 1

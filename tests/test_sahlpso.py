@@ -343,7 +343,7 @@ def test_abi_geometry_of_sahlpso():
     assert ok(max_fes=41) == 1
     for algo in (12, 14, 17):                                        # stay unassigned
         assert lib.mbx_state_dim(C.byref(oracle.make_cfg(algo, NP0, 10, 20000, 400, 50))) < 0
-    assert len(_abi.EXPORTED_SYMBOLS) == 44
+    assert len(_abi.EXPORTED_SYMBOLS) == 45
 
 
 def test_n_generations_equals_the_fixture():
