@@ -1039,6 +1039,49 @@
 #define MBX_SITE_NL_NOISE_A  82u
 #define MBX_SITE_NL_NOISE_B  83u
 
+/* ---------------------------------------------------------------- 21. L2L (l2l_optimizer.py, l2l_agent.py:92-135) layouts
+ * MBX_ALGO_L2L (26), np = 1, dim <= 40.  An episode is at most MBX_L2L_T = 100 strictly sequential steps (the reference's literal: max_fes plays no
+ * part); a step is one cell of nn.LSTM(input D + 2, hidden 32, proj D) in float64, the box map lb + (ub - lb) * (1 / (1 + exp(-x_raw))) and ONE
+ * evaluation y = problem.eval(x) [- optimum], noise included.  mbx_l2l_rollout runs n_steps of them in one launch with everything below in LDS;
+ * mbx_step (actions = x_raw [B, D] float64) is the box map, the evaluation and the bookkeeping alone: the host ran the cell.
+ * Weights are PER INSTANCE SET (mbx_l2l_set_params), one set = MBX_L2L_NPARAM(D) float64 in torch's order:
+ *   weight_ih_l0 [128][D + 2] | weight_hh_l0 [128][D] | bias_ih_l0 [128] | bias_hh_l0 [128] | weight_hr_l0 [D][32];  gate rows i | f | g | o, 32 each.
+ * state block: in[D + 2] h[D] c[32] x[D] scalars[16] cost_curve[MBX_L2L_CURVE_CAP].
+ *   in:  the cell's next input (x_raw, y, constant); all zeros after mbx_reset -- the constant slot is 0 at step 0 and 1 from step 1 on.
+ *   h:   the projected hidden state = the last x_raw;  c: the cell state;  x: the last evaluated position (diagnostic).
+ *   scalars: MBX_SC_GBEST = best y so far (strict <), MBX_SC_FES = MBX_SC_GEN = steps executed, MBX_SC_COST_LEN = ceil(steps / 2), MBX_SC_DONE,
+ *            MBX_SC_RETURN = sum y / y_0, and the three below.
+ *   cost_curve: the reference's cost[::2] -- slot k (0 <= k < 50) = best after step 2 k + 1; readers pad the later slots with the last real entry.
+ *   done = (optimum known and early_stop and y <= 1e-8) or steps >= 100; a finished instance stays frozen.
+ * Summation order (float64, no contraction: every product is rounded, then added):
+ *   s1 = sum_j W_ih[r][j] in[j], j ascending from 0.0;  s2 = sum_j W_hh[r][j] h[j] likewise;  gate_r = ((s1 + b_ih[r]) + s2) + b_hh[r];
+ *   sigmoid(v) = 1 / (1 + exp(-v));  c' = sigmoid(f) * c + sigmoid(i) * tanh(g);  x_raw[d] = sum_k W_hr[d][k] (sigmoid(o_k) * tanh(c'_k)), k ascending from 0.0.
+ * tape (per step): the evaluator's draws for one row, noise[3] (a | b | c as every other tape's noise rows).
+ * Philox: the single-row noise sites MBX_SITE_NOISE0_A/B, index 0, counter word 2 (generation) = the 1-based step.                              */
+#define MBX_L2L_DIM_MAX  40
+#define MBX_L2L_HID      32
+#define MBX_L2L_GATES    128
+#define MBX_L2L_T        100
+#define MBX_L2L_CURVE    50
+#define MBX_L2L_NPARAM(D)            (MBX_L2L_GATES * ((int64_t)(D) + 2) + MBX_L2L_GATES * (int64_t)(D) + 2 * MBX_L2L_GATES + (int64_t)(D) * MBX_L2L_HID)
+#define MBX_L2L_W_IH(D)              ((int64_t)0)
+#define MBX_L2L_W_HH(D)              (MBX_L2L_GATES * ((int64_t)(D) + 2))
+#define MBX_L2L_B_IH(D)              (MBX_L2L_W_HH(D) + MBX_L2L_GATES * (int64_t)(D))
+#define MBX_L2L_B_HH(D)              (MBX_L2L_B_IH(D) + MBX_L2L_GATES)
+#define MBX_L2L_W_HR(D)              (MBX_L2L_B_HH(D) + MBX_L2L_GATES)
+#define MBX_L2L_TAPE_NOISE(NP, D)    ((int64_t)0)
+#define MBX_L2L_TAPE_STRIDE(NP, D)   ((int64_t)3)
+#define MBX_L2L_ST_IN(NP, D)         ((int64_t)0)
+#define MBX_L2L_ST_H(NP, D)          ((int64_t)(D) + 2)
+#define MBX_L2L_ST_C(NP, D)          (2 * (int64_t)(D) + 2)
+#define MBX_L2L_ST_X(NP, D)          (2 * (int64_t)(D) + 2 + MBX_L2L_HID)
+#define MBX_L2L_ST_SCALARS(NP, D)    (3 * (int64_t)(D) + 2 + MBX_L2L_HID)
+#define MBX_L2L_CURVE_CAP(NLOG)      ((int64_t)(NLOG) + 1 > MBX_L2L_CURVE ? (int64_t)(NLOG) + 1 : (int64_t)MBX_L2L_CURVE)
+#define MBX_L2L_STATE_DOUBLES(NP, D, NLOG) (MBX_L2L_ST_SCALARS(NP, D) + MBX_NSCALAR + MBX_L2L_CURVE_CAP(NLOG))
+#define MBX_SC_L2L_YSUM  10   /* sum of y over the executed steps */
+#define MBX_SC_L2L_Y0    11   /* y of step 1 */
+#define MBX_SC_L2L_Y     12   /* y of the last step */
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

@@ -1,5 +1,5 @@
 // mbx.hip — libmbx.so: kernels' launch code and the C-ABI of include/mbx.h.
-// Build: make -C metabox_amd/csrc  (twelve translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip, mbx_run_rlhpsde.hip, mbx_run_nlshade.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
+// Build: make -C metabox_amd/csrc  (thirteen translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip, mbx_run_l2l.hip, mbx_run_rlhpsde.hip, mbx_run_nlshade.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -47,6 +47,7 @@
 #include "mbx_run_dedqn.hip"           // the DEDQN kernels and their launch code, in this file as well
 #include "mbx_run_nrlpso.hip"          // ... and the NRLPSO ones
 #include "mbx_run_les.hip"
+#include "mbx_run_l2l.hip"
 #include "mbx_run_rlhpsde.hip"
 #include "mbx_run_nlshade.hip"
 #endif
@@ -109,6 +110,9 @@ struct mbx_batch {
     int les_n_sets = 0;
     float* d_les_ts = nullptr;             // LES: [les_horizon + 1][13] float32 timestamp embedding tanh(t / timestamp - 1), one row per generation counter
     int les_horizon = 0;
+    double* d_l2l_params = nullptr;        // L2L: [l2l_n_sets][MBX_L2L_NPARAM(dim)] weight sets and the set of every instance (mbx_l2l_set_params; copies)
+    int32_t* d_l2l_set = nullptr;
+    int l2l_n_sets = 0;
     bool rollout_per_generation = false;   // MBX_F_ROLLOUT_PER_GENERATION: the mbx_*_rollout entry points take the host-loop route
     int64_t state_stride = 0;
     const double* d_tape = nullptr;
@@ -553,7 +557,7 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
 extern "C" int mbx_batch_destroy(mbx_batch* b)
 {
     if (!b) return MBX_OK;
-    (void)hipFree(b->d_problem_idx); (void)hipFree(b->d_seeds); (void)hipFree(b->d_state); (void)hipFree(b->d_order); (void)hipFree(b->d_pci); (void)hipFree(b->d_scratch); (void)hipFree(b->d_lstm_pack); (void)hipFree(b->d_les_params); (void)hipFree(b->d_les_set); (void)hipFree(b->d_les_ts);
+    (void)hipFree(b->d_problem_idx); (void)hipFree(b->d_seeds); (void)hipFree(b->d_state); (void)hipFree(b->d_order); (void)hipFree(b->d_pci); (void)hipFree(b->d_scratch); (void)hipFree(b->d_lstm_pack); (void)hipFree(b->d_les_params); (void)hipFree(b->d_les_set); (void)hipFree(b->d_les_ts); (void)hipFree(b->d_l2l_params); (void)hipFree(b->d_l2l_set);
     delete b;
     return MBX_OK;
 }
@@ -934,6 +938,20 @@ static int les_prepare_batch(mbx_batch* b, const AlgoGeom& g)
 MBX_RESET_FN(les_reset) { les_launch_reset(make_params(b), stream, d_state_out); }
 MBX_STEP_FN(les_step) { (void)d_actions; return mbx_les_rollout(b, 1, 0, MBX_OUT, stream); }   // one generation of the budget route
 
+// ---- L2L: mbx_run_l2l.hip
+static int l2l_check(const mbx_algo_cfg& c)
+{
+    // one point per step: a single evaluation row; one lane of wave 0 per dimension
+    if (c.np != 1) return fail(MBX_E_ARG, "L2L runs np = 1 (one point per step), not %d", c.np);
+    if (c.dim < 2 || c.dim > MBX_L2L_DIM_MAX) return fail(MBX_E_ARG, "L2L runs dim in [2, %d], not %d", MBX_L2L_DIM_MAX, c.dim);
+    return MBX_OK;
+}
+
+static AlgoGeom l2l_geom(const mbx_algo_cfg& c) { return MBX_GEOM(L2L, l2l_lds_doubles(c.dim), 1, c.dim); }
+static int l2l_prepare_batch(mbx_batch*, const AlgoGeom& g) { HIP_TRY(l2l_prepare(lds_of(g))); return MBX_OK; }
+MBX_RESET_FN(l2l_reset) { l2l_launch_reset(make_params(b), stream, d_state_out); }
+MBX_STEP_FN(l2l_step) { l2l_launch_step(make_params(b), stream, (const double*)d_actions, MBX_OUT); return MBX_OK; }   // the host ran the cell: actions = x_raw
+
 // ---- RL-HPSDE: mbx_run_rlhpsde.hip
 static int rlhpsde_check(const mbx_algo_cfg& c)
 {
@@ -1046,11 +1064,12 @@ static const AlgoOps kAlgoOps[] = {
     {MBX_ALGO_NRLPSO, "NRLPSO", true, false, nrlpso_check, nrlpso_geom, nrlpso_prepare_batch, nrlpso_reset, nrlpso_step, nrlpso_launch_info},
     {MBX_ALGO_SAHLPSO, "SAHLPSO", false, false, sahlpso_check, sahlpso_geom, sahlpso_prepare_batch, sahlpso_reset, sahlpso_step, nullptr},
     {MBX_ALGO_LES, "LES", false, false, les_check, les_geom, les_prepare_batch, les_reset, les_step, nullptr},
+    {MBX_ALGO_L2L, "L2L", true, false, l2l_check, l2l_geom, l2l_prepare_batch, l2l_reset, l2l_step, nullptr},
     {MBX_ALGO_RLHPSDE, "RL-HPSDE", true, false, rlhpsde_check, rlhpsde_geom, rlhpsde_prepare_batch, rlhpsde_reset, rlhpsde_step, nullptr},
     {MBX_ALGO_NLSHADE, "NL_SHADE_LBC", false, false, nlshade_check, nlshade_geom, nlshade_prepare_batch, nlshade_reset, nlshade_step, nullptr},
 };
 
-static const AlgoOps* ops_of(int algo)      // null for the ids that are not assigned (0, 12, 14, 17) and anything out of range
+static const AlgoOps* ops_of(int algo)      // null for the ids that are not assigned (0, 12, 14, 17, 22, 23) and anything out of range
 {
     for (const AlgoOps& o : kAlgoOps)
         if (o.id == algo) return &o;
@@ -1462,6 +1481,48 @@ extern "C" int mbx_les_rollout(mbx_batch* b, int n_gens, int skip, double* d_sta
     else
         les_launch_run(bp, (hipStream_t)stream, b->d_les_params, b->d_les_set, b->les_n_sets, b->d_les_ts, b->les_horizon, n_gens, skip, 0, n_gens, d_state_out,
                        d_reward_out, d_done_out);
+    HIP_TRY(hipGetLastError());
+    return MBX_OK;
+}
+
+extern "C" int mbx_l2l_set_params(mbx_batch* b, const double* d_params, int n_sets, const int32_t* d_set_of_instance)
+{
+    if (!b || !d_params || n_sets < 1) return fail(MBX_E_ARG, "mbx_l2l_set_params: bad arguments");
+    if (b->cfg.algo != MBX_ALGO_L2L) return fail(MBX_E_UNSUPPORTED, "mbx_l2l_set_params: the batch is not an L2L batch");
+    HIP_TRY(hipDeviceSynchronize());
+    if (d_set_of_instance) {                                        // an index outside the table would be read out of bounds on the device
+        std::vector<int32_t> h(b->B);
+        HIP_TRY(hipMemcpy(h.data(), d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < b->B; ++i)
+            if (h[i] < 0 || h[i] >= n_sets) return fail(MBX_E_ARG, "mbx_l2l_set_params: set_of_instance[%d] = %d outside [0, %d)", i, h[i], n_sets);
+    }
+    (void)hipFree(b->d_l2l_params); (void)hipFree(b->d_l2l_set);
+    b->d_l2l_params = nullptr; b->d_l2l_set = nullptr; b->l2l_n_sets = 0;
+    const size_t bytes = (size_t)n_sets * (size_t)MBX_L2L_NPARAM(b->cfg.dim) * sizeof(double);
+    HIP_TRY(hipMalloc(&b->d_l2l_params, bytes));
+    HIP_TRY(hipMemcpy(b->d_l2l_params, d_params, bytes, hipMemcpyDeviceToDevice));
+    if (d_set_of_instance) {
+        HIP_TRY(hipMalloc(&b->d_l2l_set, (size_t)b->B * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(b->d_l2l_set, d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToDevice));
+    }
+    b->l2l_n_sets = n_sets;
+    return MBX_OK;
+}
+
+extern "C" int mbx_l2l_rollout(mbx_batch* b, int n_steps, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
+{
+    if (!b) return fail(MBX_E_ARG, "mbx_l2l_rollout: null batch");
+    if (b->cfg.algo != MBX_ALGO_L2L) return fail(MBX_E_UNSUPPORTED, "mbx_l2l_rollout: the batch is not an L2L batch");
+    if (!b->d_l2l_params) return fail(MBX_E_ARG, "L2L: no weights yet, call mbx_l2l_set_params first");
+    if (n_steps < 1) return fail(MBX_E_ARG, "mbx_l2l_rollout: n_steps must be >= 1");
+    if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_l2l_rollout: a replay tape holds one step");
+    const BatchParams bp = make_params(b);
+    const bool generic = generic_geometry(b);
+    if (b->rollout_per_generation)
+        for (int g = 0; g < n_steps; ++g)
+            l2l_launch_run(bp, generic, (hipStream_t)stream, b->d_l2l_params, b->d_l2l_set, b->l2l_n_sets, 1, d_state_out, d_reward_out, d_done_out);
+    else
+        l2l_launch_run(bp, generic, (hipStream_t)stream, b->d_l2l_params, b->d_l2l_set, b->l2l_n_sets, n_steps, d_state_out, d_reward_out, d_done_out);
     HIP_TRY(hipGetLastError());
     return MBX_OK;
 }

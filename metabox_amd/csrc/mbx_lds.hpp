@@ -623,6 +623,24 @@ MBX_LDS_WALK LesLds les_layout(C& c, int D)
 __host__ __device__ inline int64_t les_lds_doubles(int D) { LdsSize c; les_layout(c, D); return align2(c.n); }
 __device__ __forceinline__ LesLds les_carve(double* base, int D) { LdsCarve c{base}; return les_layout(c, D); }
 
+// ------------------------------------------------------------------------------------------------ L2L (mbx_l2l.hpp)
+struct L2lLds {
+    double *XR, *T, *Z, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *ACT, *IN, *H, *C, *HO, *CURVE;
+    __device__ __forceinline__ EvalLds eval() const { return EvalLds{XR, Z, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
+};
+
+// one evaluation row; ACT: the 128 activated gates, HO: sigmoid(o) tanh(c'), CURVE: cost[::2]
+MBX_LDS_WALK L2lLds l2l_layout(C& c, int D)
+{
+    L2lLds L{};
+    lds_eval_prefix(c, 1, D, L.XR, L.T, L.Z, L.M1T, L.M2T, L.DSH, L.V0, L.V1, L.V2);
+    L.NC = c.take(2);  L.ACT = c.take(MBX_L2L_GATES);  L.IN = c.take(align2(D + 2));  L.H = c.take(align2(D));
+    L.C = c.take(MBX_L2L_HID);  L.HO = c.take(MBX_L2L_HID);  L.CURVE = c.take(MBX_L2L_CURVE);
+    return L;
+}
+__host__ __device__ inline int64_t l2l_lds_doubles(int D) { LdsSize c; l2l_layout(c, D); return align2(c.n); }
+__device__ __forceinline__ L2lLds l2l_carve(double* base, int D) { LdsCarve c{base}; return l2l_layout(c, D); }
+
 // ------------------------------------------------------------------------------------------------ QLPSO (mbx_qlpso.hpp)
 struct QlLds {
     double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *POP, *COST, *MEAN, *DIST, *SC;

@@ -59,6 +59,16 @@ void les_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state
 void les_launch_run(const BatchParams& bp, hipStream_t stream, const float* d_params, const int32_t* d_set_of, int n_sets, const float* d_ts, int horizon,
                     int n_gens, int skip, int step0, int skip_total, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
 }  // namespace mbx
+// L2L (mbx_l2l.hpp): likewise in mbx_run_l2l.hip
+namespace mbx {
+hipError_t l2l_prepare(size_t lds_bytes);
+void l2l_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state_out);
+// the host ran the cell: d_x_raw [B, D] is the action
+void l2l_launch_step(const BatchParams& bp, hipStream_t stream, const double* d_x_raw, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
+// generic: the run-time-D body at D = 10 as well (MBX_F_GENERIC_GEOMETRY)
+void l2l_launch_run(const BatchParams& bp, bool generic, hipStream_t stream, const double* d_params, const int32_t* d_set_of, int n_sets, int n_steps,
+                    double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
+}  // namespace mbx
 // RL-HPSDE (mbx_rlhpsde.hpp): likewise in mbx_run_rlhpsde.hip
 namespace mbx {
 hipError_t rlhpsde_prepare(size_t lds_bytes);

@@ -68,6 +68,8 @@ COST_NS = {
 # evaluation-dominated like RLEPSO's generation and the ratios between functions carry over; with early_stop, Sphere and linear slope end early here too.
 # NL_SHADE_LBC falls back on the table too, documented rather than measured: an update is NP trial evaluations, but more than half of an episode is updates of 4 to 8 rows
 # whose fixed phases (two sorts, the scan, the sums) cost the same for every function, so the table overstates the spread between functions.
+# L2L falls back on the table as well, documented rather than measured: an episode is 100 single-row evaluations behind 100 LSTM cells whose cost is the same for
+# every function, so the table overstates the spread between functions; L2L_COST_US below is what a whole L2L episode costs next to the others (100 FEs, not maxFEs).
 EPISODE_COST_US = {
     10: {1: 2.06, 2: 5.49, 3: 6.599, 4: 6.06, 5: 0.882, 6: 4.785, 7: 4.8, 8: 4.582, 9: 4.534, 10: 5.31, 11: 5.267, 12: 5.705, 13: 5.18, 14: 5.018, 15: 6.403,
          16: 6.37, 17: 6.179, 18: 6.174, 19: 4.902, 20: 5.029, 21: 6.566, 22: 6.418, 23: 6.187, 24: 4.828, 101: 2.084, 102: 2.589, 103: 4.86, 104: 4.928, 105:
@@ -85,6 +87,11 @@ EPISODE_COST_US = {
          106.204, 112: 105.789, 113: 120.459, 114: 121.348, 115: 149.978, 116: 122.797, 117: 123.647, 118: 124.065, 119: 115.076, 120: 115.811, 121: 115.873,
          122: 148.381, 123: 149.596, 124: 149.642, 125: 112.751, 126: 112.987, 127: 112.725, 128: 198.153, 129: 199.259, 130: 198.812},
 }
+
+
+# us per WHOLE L2L EPISODE (100 steps) of one instance in a full batch, by dimension: tools/kbench_algos.py l2l on one MI355X (docs/EXPERIMENTS.md).  One row: the
+# cell and the barriers dominate, the function does not.
+L2L_COST_US = {10: 1.33, 40: 4.03}       # 5.43 ms per 4096 instances; 4.12 ms per 1024
 
 
 def relative_cost(problem):

@@ -139,10 +139,12 @@ class Batch:
         return self.state
 
     def step(self, actions):
-        """actions: CUDA tensor [B, action_dim] (float32).  Returns (state, reward, done) device tensors that are
+        """actions: CUDA tensor [B, action_dim] (float32; int32 for the tabular agents, float64 for L2L).  Returns (state, reward, done) device tensors that are
         overwritten by the next call."""
         if self.action_dim > 0:
             want = torch.int32 if self.cfg.algo in (_abi.ALGO_DEDDQN, _abi.ALGO_QLPSO, _abi.ALGO_DEDQN, _abi.ALGO_NRLPSO, _abi.ALGO_RLHPSDE) else torch.float32
+            if self.cfg.algo == _abi.ALGO_L2L:
+                want = torch.float64           # x_raw, the LSTM's float64 output
             assert actions.is_cuda and actions.is_contiguous() and actions.dtype == want
             assert actions.numel() == self.B * self.action_dim
         else:
@@ -257,6 +259,30 @@ class Batch:
         (``mbx_les_rollout``).  skip=False: up to `n_gens` generations under the budget / early-stop end rule, finished instances frozen; skip=True:
         the reference's ``skip_step = n_gens`` call.  Returns (state = gbest [B, 1], reward = (init_y - gbest) / init_y, done)."""
         _abi.check(self.lib.mbx_les_rollout(self._h, int(n_gens), int(bool(skip)), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
+        return self.state, self.reward, self.done
+
+    def l2l_set_params(self, params, set_of_instance=None):
+        """L2L: the weight sets of the batch and the set of every instance (``mbx_l2l_set_params``).  params: [n_sets, n] (or [n]) float64 with
+        n = 128 (D + 2) + 128 D + 128 + 128 + 32 D in torch's order (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, weight_hr_l0, each
+        flattened row-major).  set_of_instance: [B] integers, or None = set 0 for every instance.  The library keeps copies."""
+        D = self.cfg.dim
+        n = 128 * (D + 2) + 128 * D + 256 + 32 * D
+        p = np.asarray(params.detach().cpu().numpy() if torch.is_tensor(params) else params, dtype=np.float64)
+        if p.size % n:
+            raise ValueError(f'an L2L weight set at dim {D} has {n} values; got {p.size}')
+        p = np.ascontiguousarray(p.reshape(-1, n))
+        pd = torch.from_numpy(p).to(self.device)
+        sd = None
+        if set_of_instance is not None:
+            si = np.ascontiguousarray(set_of_instance, dtype=np.int32)
+            assert si.shape == (self.B,)
+            sd = torch.from_numpy(si).to(self.device)
+        _abi.check(self.lib.mbx_l2l_set_params(self._h, _ptr(pd), int(p.shape[0]), _ptr(sd)))
+
+    def l2l_rollout(self, n_steps):
+        """Up to `n_steps` L2L steps -- LSTM cell, box map, one evaluation -- of every instance in ONE launch with the recurrent state on chip in
+        between (``mbx_l2l_rollout``); finished instances stay frozen.  Returns (state = the last y [B, 1], reward = sum y / y_0, done)."""
+        _abi.check(self.lib.mbx_l2l_rollout(self._h, int(n_steps), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
         return self.state, self.reward, self.done
 
     def dedqn_rollout(self, weights, n_steps, trajectory=False):

@@ -195,6 +195,9 @@ class Tester(object):
             _fill(self.test_results, problems, name, self.runs, cost, fes)
             self.test_results['T1'][name] = 0.
             self.test_results['T2'][name] = wall / len(cost)
+            if type(agent).__name__ == 'L2L_Agent':           # an L2L episode is 100 evaluations: scaled to the budget of the others (tester.py:223-225)
+                self.test_results['T1'][name] *= cfg.maxFEs / 100
+                self.test_results['T2'][name] *= cfg.maxFEs / 100
         for optimizer in self.t_optimizer_for_cp:
             name = type(optimizer).__name__
             cost, fes, _, wall = run_pairs(problems, _random_search_runner(optimizer, cache), self.runs, cap, n_logpoint=cfg.n_logpoint)

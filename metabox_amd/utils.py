@@ -15,8 +15,8 @@ def _protein(config):
 
 
 def _autograd_twin(config):
-    raise NotImplementedError(f'{config.problem}: the autograd problem twins are only needed by L2L / RNN-OI, which are '
-                              f'outside the accelerated path (SURVEY.md §2).')
+    raise NotImplementedError(f'{config.problem}: the autograd problem twins are only needed to TRAIN L2L / RNN-OI (the gradient of the objective), '
+                              f'which this build does not do; --test and --rollout of L2L_Agent run on the plain suite (DESIGN.md §7).')
 
 
 _BUILDERS = {'bbob': _bbob, 'bbob-noisy': _bbob, 'protein': _protein,

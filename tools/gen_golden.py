@@ -3117,7 +3117,131 @@ def gen_nlshade():
         assert os.path.getsize(path) < 1024 * 1024
 
 
-SECTIONS = {'nlshade': gen_nlshade, 'rlhpsde': gen_rlhpsde, 'les': gen_les, 'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+# ------------------------------------------------------------------------------------------------ L2L
+# l2l_policy.npz  : the five arrays of the shipped bbob_easy nn.LSTM (float64) and e_lstm_base, the largest difference on these fixtures between
+#                   torch's own cell output (x_raw, c') and a long-double restatement fed the same recorded (input, h, c).
+# l2l_traces*.npz : whole reference rollout_episode runs at D = 10 on the 24 noise-free functions and on one noisy function per noise model
+#                   (np.random.seed(seed); the draws are NOT stored, the tests regenerate them).  Per episode x_raw [steps, D], c [steps, 32],
+#                   y [steps], cost = cost[::2], fes, return; per noise-free episode the two gains G_y / G_x measured on the reference itself:
+#                   the episode re-run with every y handed back to the agent times 1 + eps s_t (G_y), or with eps s_t added to the x_raw the
+#                   environment is given (G_x), s_t = +-1 from a fixed stream, eps = 2^-40; the gain is the largest relative change of y (as the
+#                   agent sees it) over the episode, divided by eps.
+L2L_EPS = 2.0 ** -40
+
+
+def l2l_cell_ld(w, inp, h, c):
+    """One cell of nn.LSTM(proj_size) in numpy long double: gates = W_ih in + b_ih + W_hh h + b_hh (i, f, g, o), c' = s(f) c + s(i) tanh(g),
+    h' = W_hr (s(o) tanh(c')).  -> (h', c') as long double."""
+    LD = np.longdouble
+    wih, whh, bih, bhh, whr = (np.asarray(w[k], dtype=LD) for k in ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0', 'weight_hr_l0'))
+    g = wih @ np.asarray(inp, dtype=LD) + bih + whh @ np.asarray(h, dtype=LD) + bhh
+    H = whr.shape[1]
+    def sig(v):
+        with np.errstate(over='ignore'):
+            return 1 / (1 + np.exp(-v))
+    c2 = sig(g[H:2 * H]) * np.asarray(c, dtype=LD) + sig(g[:H]) * np.tanh(g[2 * H:3 * H])
+    return whr @ (sig(g[3 * H:]) * np.tanh(c2)), c2
+
+
+def run_l2l_episode(problem, seed, agent, config, perturb=None):
+    """The reference's own rollout_episode on a fresh L2L_Optimizer, env.step wrapped from here (its text is untouched): records x_raw and y of every
+    step and the cell state c' the net returns.  perturb = ('y', s) hands every y back to the agent times 1 + eps s_t, ('x', s) adds eps s_t to the x_raw
+    the environment is given (s: one sign per step)."""
+    from optimizer.l2l_optimizer import L2L_Optimizer
+    from environment import PBO_Env
+    import copy
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    opt = L2L_Optimizer(copy.deepcopy(config))
+    env = PBO_Env(problem, opt)
+    xs, ys, cs = [], [], []
+    real_step, real_fwd = env.step, agent.net.forward
+
+    def step(x):
+        t = len(xs)
+        xs.append(np.array(x, dtype=np.float64))
+        xe = x + L2L_EPS * perturb[1][t] if perturb and perturb[0] == 'x' else x
+        y, r, d = real_step(xe)
+        if perturb and perturb[0] == 'y':
+            y = y * (1 + L2L_EPS * perturb[1][t])
+        ys.append(float(y))                                          # y as the agent sees it: G_y holds the direct change as well as what it grows into
+        return y, r, d
+
+    def fwd(inp, hc):
+        out, (h, c) = real_fwd(inp, hc)
+        cs.append(c.detach().numpy().reshape(-1).copy())
+        return out, (h, c)
+    env.step, agent.net.forward = step, fwd
+    try:
+        res = agent.rollout_episode(env)
+    finally:
+        del agent.net.forward
+    return dict(x_raw=np.stack(xs), c=np.stack(cs), y=np.array(ys), cost=np.array(res['cost'], dtype=np.float64), fes=np.int64(res['fes']),
+                ret=np.float64(res['return']), cost_all=np.array(opt.cost, dtype=np.float64))
+
+
+def gen_l2l():
+    scratch = tempfile.mkdtemp()
+    agent = load_shipped(os.path.join(ref_import.REF_SRC, 'agent_model/test/bbob_easy/L2L_Agent.pkl'))
+    w = {k: v.detach().numpy().astype(np.float64) for k, v in agent.net.state_dict().items()}
+    assert w['weight_ih_l0'].shape == (128, 12) and w['weight_hh_l0'].shape == (128, 10) and w['weight_hr_l0'].shape == (10, 32)
+    assert all(v.dtype == torch.float64 for v in agent.net.state_dict().values())
+    signs = np.where(np.random.RandomState(20261020).rand(100) < 0.5, -1., 1.)
+    data, cases, e_base = {'signs': signs}, [], 0.
+    for suite, fids in (('bbob', range(1, 25)), ('bbob-noisy', (101, 102, 103))):
+        config = ref_import.ref_config(['--problem', suite, '--dim', '10'], scratch)
+        tr, te, _ = all_problems(suite, 10)
+        ps = {fid_of(p): p for p in tr + te}
+        for fid in fids:
+            p, seed = ps[fid], 900 + fid
+            p.reset()
+            rec = run_l2l_episode(p, seed, agent, config)
+            n = len(rec['y'])
+            assert n == int(rec['fes']) and len(rec['cost']) == (n + 1) // 2 and np.array_equal(rec['cost'], rec['cost_all'][::2])
+            # torch's cell against the long-double one, fed the recorded (input, h, c) of every step
+            inp, h, c = np.zeros(12), np.zeros(10), np.zeros(32)
+            for t in range(n):
+                h2, c2 = l2l_cell_ld(w, inp, h, c)
+                e_base = max(e_base, float(np.max(np.abs(h2 - rec['x_raw'][t]))), float(np.max(np.abs(c2 - rec['c'][t]))))
+                inp, h, c = np.concatenate([rec['x_raw'][t], [rec['y'][t], 1.]]), rec['x_raw'][t], rec['c'][t]
+            key = f'{suite}/{fid}/{seed}'
+            if suite == 'bbob':
+                for tag in ('y', 'x'):
+                    p.reset()
+                    alt = run_l2l_episode(p, seed, agent, config, (tag, signs))
+                    m = min(n, len(alt['y']))
+                    with np.errstate(divide='ignore', invalid='ignore'):
+                        rel = np.abs(alt['y'][:m] - rec['y'][:m]) / np.abs(rec['y'][:m])
+                    rec['G_' + tag] = np.float64(np.nanmax(rel) / L2L_EPS)
+            del rec['cost_all']
+            cases.append(key)
+            for k, v in rec.items():
+                data[f'{key}/{k}'] = v
+            print(key, 'steps', n, 'best', rec['cost'][-1], 'ret', float(rec['ret']), 'G_y', float(rec.get('G_y', np.nan)), 'G_x', float(rec.get('G_x', np.nan)))
+    print('e_lstm_base', e_base, 'e_lstm', 4 * e_base)
+    np.savez_compressed(os.path.join(OUT, 'l2l_policy.npz'), e_lstm_base=np.float64(e_base), e_lstm=np.float64(4 * e_base), **w)
+    data['cases'] = np.array(cases)
+    parts, sizes, owner = [], [], {}
+    for key in data:
+        prefix = '/'.join(key.split('/')[:3])
+        if prefix not in owner:
+            need = sum(data[k].nbytes for k in data if '/'.join(k.split('/')[:3]) == prefix)
+            for n in range(len(parts) + 1):
+                if n == len(parts):
+                    parts.append({}); sizes.append(0)
+                if sizes[n] + need <= 700 * 1024 or sizes[n] == 0:
+                    break
+            owner[prefix] = n
+            sizes[n] += need
+        parts[owner[prefix]][key] = data[key]
+    for n, d in enumerate(parts):
+        path = os.path.join(OUT, 'l2l_traces%s.npz' % ('' if n == 0 else '_' + 'abcdefgh'[n]))
+        np.savez_compressed(path, **d)
+        print(os.path.basename(path), os.path.getsize(path))
+        assert os.path.getsize(path) < 1000 * 1024
+
+
+SECTIONS = {'l2l': gen_l2l, 'nlshade': gen_nlshade, 'rlhpsde': gen_rlhpsde, 'les': gen_les, 'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

@@ -28,7 +28,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPFLAGS = '--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DMBX_NOINLINE_MATH -fPIC -fvisibility=default'.split()
 OBJS = ['mbx.o', 'mbx_run_rlepso_c5.o', 'mbx_run_rlepso_fast.o', 'mbx_run_rlepso_d40.o', 'mbx_run_lde.o', 'mbx_run_dedqn.o', 'mbx_run_nrlpso.o', 'mbx_run_sahlpso.o',
-        'mbx_run_les.o', 'mbx_run_rlhpsde.o', 'mbx_run_nlshade.o']                                        # every object of csrc/Makefile but mbx_run_rlepso.o
+        'mbx_run_les.o', 'mbx_run_l2l.o', 'mbx_run_rlhpsde.o', 'mbx_run_nlshade.o']                                        # every object of csrc/Makefile but mbx_run_rlepso.o
 SITE_PART, SITE_ELEM_A, SITE_TOURN = 2, 0, 17                 # include/mbx_layout.h
 VARIANTS = {
     'full': [],

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso|les|rlhpsde|nlshade] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso|les|rlhpsde|nlshade|l2l] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -454,3 +454,35 @@ if 'les' in which:
                               'generations_per_call': gens, 'windows_us_per_generation': [round(x, 1) for x in v],
                               'launch_info': (bs if 'sahlpso' in k else br).launch_info()}))
         for b in (br, bg, bs): b.close()
+if 'l2l' in which:
+    # L2L (one step = one LSTM cell + 1 FE, an episode = 100 steps): whole episodes in ONE launch beside one launch per step (MBX_F_ROLLOUT_PER_GENERATION: same call,
+    # same outputs), the paths alternating window by window: bbob round-robin, 4096 instances at D = 10 (the weights in registers) and 1024 at D = 40 (the run-time-D
+    # body), every instance with one of 21 weight sets -- the shape of the --rollout table, 21 checkpoints in one batch.  Median of 5 windows per path after a
+    # warm-up window, each window ended by a device synchronise (wall times, launch gaps included).
+    from metabox_amd._abi import ALGO_L2L, F_ROLLOUT_PER_GENERATION
+    from metabox_amd.suite import Batch, Suite
+    for dim, B in ((10, 4096), (40, 1024)):
+        cfg = get_config(['--problem', 'bbob', '--dim', str(dim)])
+        tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+        s = Suite(ps)
+        pidx, seeds = np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1
+        sets = np.random.RandomState(0).uniform(-0.5, 0.5, (21, 128 * (dim + 2) + 128 * dim + 256 + 32 * dim))
+        br = Batch(s, ALGO_L2L, pidx, seeds, 1, 20000, 400, 50, early_stop=False)
+        bg = Batch(s, ALGO_L2L, pidx, seeds, 1, 20000, 400, 50, early_stop=False, flags=F_ROLLOUT_PER_GENERATION)
+        for b in (br, bg): b.l2l_set_params(sets, (np.arange(B) // len(ps)) % 21)
+        def l2l(b):
+            def run(n):
+                for _ in range(n):
+                    b.reset(); b.l2l_rollout(100)
+            return run
+        paths = {'k_l2l_run resident, 100 steps per launch': (l2l(br), 4), 'k_l2l_run one launch per step': (l2l(bg), 4)}
+        times = {k: [] for k in paths}
+        for w in range(6):
+            for k, (fn, n) in paths.items():
+                dt = timed(fn, n)
+                if w: times[k].append(dt / n * 1e3)                  # window 0 warms up
+        assert torch.equal(br.state, bg.state) and torch.equal(br.results()['cost'], bg.results()['cost']) and bool(br.done.all())
+        for k, v in times.items():
+            print(json.dumps({'path': f'{k}, bbob d={dim}, {B} instances', 'ms_per_episode_batch_median': float(np.median(v)), 'us_per_step_median': float(np.median(v)) * 10,
+                              'windows_ms_per_episode_batch': [round(x, 3) for x in v], 'launch_info': br.launch_info()}))
+        for b in (br, bg): b.close()
