@@ -16,6 +16,18 @@
 //  * exemplar_stag lives on the optimizer object (:19) and init_population never resets it: mbx_reset leaves the counters alone;
 //  * gbest and the cost curve follow the particles only; exemplar costs never enter them (found_best is not observable).
 // Arithmetic follows numpy's expression order with no contraction (the build passes -ffp-contract=off); uniform(a, b) = a + (b - a) u.
+//
+// What is pinned, and by what (tests/glpso_exact.py restates :22-66 and :76-177 on this state block with NP and D at run time; tests/test_glpso_exact.py):
+//  * positions, velocities, candidate exemplars and the exemplar rows after selection and tournament: bit for bit, at (NP, D) from (4, 2) to (256, 10), the docking
+//    shape included.  No bit-level exception is needed: fmin(fmax(v, lo), hi) is np.clip on every finite input, signed zeros included.  (The two bounces below could
+//    be one test, `nx > ub || nx < lb`: a position is never beyond both bounds.)
+//  * every cost against the extended-precision evaluators, every `<` decided wherever exact +- allowance decides it;
+//  * the rules stated here, each by a planted state: strict `<` for pbest, gbest and the selection (exact ties, c < c); stag > 7 (counters at 6, 7, 8); first on
+//    ties in the tournament and in the gbest argmin; the tournament gathering the exemplars after selection and before any replacement of this launch; exemplar_cost
+//    and the counter left alone by the tournament; the counters carried over mbx_reset and mbx_batch_rebind; the log test after the first evaluation; mt < 0.01.
+// Not pinned: free-running Philox episodes against the reference in distribution, and the normal-noise draws on the Philox route (the host cannot rebuild the
+// device's log / cos).  The log-point append below is guarded by the curve's length where the reference's (:160-162) is not: the two part only for a budget with
+// log_interval (n_logpoint + 1) <= max_fes, which no test reaches.
 #pragma once
 #include "mbx_device.hpp"
 #include "mbx_rlepso.hpp"   // BatchParams

@@ -1,6 +1,12 @@
 """GL-PSO (src/optimizer/gl_pso.py), a classic baseline of the test harness: the batched HIP kernels (metabox_amd/csrc/mbx_glpso.hpp)
 replay the reference's episodes from tests/golden/glpso_traces.npz (tools/gen_golden.py glpso) through mbx_set_tape.  The numpy draws
-are not stored: GlpsoTapeFeeder regenerates them from the seed in the reference's draw order (include/mbx_layout.h §11)."""
+are not stored: GlpsoTapeFeeder regenerates them from the seed in the reference's draw order (include/mbx_layout.h §11).
+
+This module is the recorded episodes (NP = 100, D = 10 / 30 / 12; gbest, fes, pbest, exemplar_cost and the counters, within the parity tolerance), the Philox route
+against the rebuilt tape at D = 10, and batch invariance.  What the episodes do not reach is pinned by tests/test_glpso_exact.py against the exact restatement of
+tests/glpso_exact.py: positions, velocities and exemplar rows bit for bit, every cost against extended precision, NP from 4 to 256 and D from 2 to 40, the tie and
+threshold rules of the kernel header on planted states, and the route equality at edge shapes.  Still unpinned: free-running Philox episodes against the reference in
+distribution, and the normal-noise draws on the Philox route."""
 import copy
 import ctypes as C
 
@@ -18,11 +24,11 @@ SITE_ELEM_A, SITE_ELEM_R, SITE_NOISE0_A, SITE_NOISE0_B, SITE_NOISE1_A, SITE_NOIS
 SITE_GL_CROSS, SITE_GL_MUT, SITE_GL_NOISE_A, SITE_GL_NOISE_B, SITE_GL_TOUR = 18, 19, 20, 21, 22
 
 
-def tape_stride(D):
+def tape_stride(D, NP=NP):
     return 6 * NP * D + 16 * NP
 
 
-def split_state(st, D, nlog=50):
+def split_state(st, D, nlog=50, NP=NP):
     NE = NP * D
     o = 4 * NE + 3 * NP + D
     return {'X': st[:NE], 'V': st[NE:2 * NE], 'pbpos': st[2 * NE:3 * NE], 'pbest': st[3 * NE:3 * NE + NP],
@@ -228,10 +234,10 @@ def _mulhi(w, n):
     return (w * n) >> 32
 
 
-def philox_tape(seed, D, noise_kind, gen, episode=0):
+def philox_tape(seed, D, noise_kind, gen, episode=0, NP=NP):
     """The tape that reproduces the Philox stream of (seed, gen, episode) under the site map of include/mbx_layout.h §11."""
     NE = NP * D
-    t = np.zeros(tape_stride(D))
+    t = np.zeros(tape_stride(D, NP))
 
     def ph(idx, site):
         return oracle.philox(seed, idx, site, gen, episode)
