@@ -182,6 +182,19 @@ __device__ unsigned long long g_phase_cycles[8192 * 16];         // [block][phas
 #ifndef MBX_FDR_UNROLL_D40
 #define MBX_FDR_UNROLL_D40 2        // the D = 40 resident kernels (1024 threads; config 5)
 #endif
+// Unrolled groups per iteration of the scan's main loop in the resident 256-thread kernels (fdr_exact: GR).  The groups of an iteration are loaded and compared one after the
+// other -- the register footprint is the one of MBX_FDR_UNROLL candidates -- and read the two LDS streams at constant offsets from ONE pair of address registers, which
+// advance once per iteration instead of once per group.  1: one group per iteration and an indexed remainder loop, as every other kernel keeps them (the A/B switch).
+#ifndef MBX_FDR_GROUPS
+#define MBX_FDR_GROUPS 3
+#endif
+// The waves of the resident 256-thread kernels run at priority 1 outside the FDR pass and at 0 inside it: vector issue is arbitrated by priority, then age, and five
+// workgroups share a CU, so the short dependency-bound phases (policy, ranking, move, objective, commit) of one workgroup are served ahead of the other workgroups' scans,
+// which fill whatever is left (docs/EXPERIMENTS.md: -2.3 % / -2.5 % on the headline, no instruction saved).  s_setprio ignores EXEC: all three sit in straight-line code of
+// the generation loop that every wave of the workgroup runs.  0: no s_setprio at all (the A/B switch).  The 512- / 1024-thread kernels own their CU and were not measured.
+#ifndef MBX_RL_PRIO
+#define MBX_RL_PRIO 1
+#endif
 #ifndef MBX_FDR_OWN_AT
 #define MBX_FDR_OWN_AT 64           // flagged items per swarm and generation above which every lane settles its own items instead of one wave per coordinate (fdr_pass)
 #endif
@@ -383,7 +396,12 @@ __device__ __forceinline__ int fdr_settle(const RlLds& L, const int* __restrict_
 // The scan does not read the item's nless: the only thing it decided was `nless > 0` in the flag, and that is a_0 < 0 (NC is in ascending order: somebody is strictly
 // better than the item exactly when the best cost is below its own; a NaN cost answers false both ways) -- a compare on a register the scan holds anyway, where
 // NLESS[ORDER[rk]] was two dependent LDS reads and their address arithmetic per item.
-template <int W, int UN = MBX_FDR_UNROLL, bool TIE = true>
+// GR: groups per iteration of the main loop (MBX_FDR_GROUPS in the resident 256-thread kernels, 1 everywhere else).  With GR > 1 the scan walks two pointers, pc into the
+// cost column and pr into the position rows: the main loop covers GR x UN candidates per trip -- group g at pc + g UN and pr + g UN D, constant offsets in the LDS
+// instructions -- and advances both once; whole groups that are left (at most GR - 1) go one per trip; the remainder, at most UN - 1 candidates, is straight-line code at
+// constant offsets behind scalar tests, with no address arithmetic of its own.  The candidates are visited in the same order, k = 1 .. bound - 1 each exactly once, through
+// the same `step`: same exemplars, same flag, and nothing at or beyond `bound` is read (tests/test_gpu_rlepso_trims3.py restates the trip arithmetic).
+template <int W, int UN = MBX_FDR_UNROLL, bool TIE = true, int GR = 1>
 __device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0, int bound, int kb[W], double range = 0.)
 {
 #ifdef MBX_ABLATE_FDR_SCAN
@@ -413,6 +431,48 @@ __device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0,
         }
         tiem = fdr_min3_abs(tiem, f64_hi_as_f32(difv[0]), f64_hi_as_f32(difv[W - 1]));
     };
+    if constexpr (GR > 1) {
+    const double* pc = L.NCS + 1;                                 // candidate k's cost
+    const double* pr = col + D;                                   // and its row
+    // one unrolled group: the LDS reads of its UN candidates are issued before its first comparison
+    auto group = [&](const double* c, const double* r, int k) {
+        double a[UN], x[UN][W];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            a[u] = c[u];
+            // (W == 2: an even coordinate of a row of even D -- one 16-byte read per candidate, as with indices)
+            if constexpr (W == 2) { const double2 v = *(const double2*)(r + u * D); x[u][0] = v.x; x[u][1] = v.y; }
+            else {
+#pragma unroll
+                for (int q = 0; q < W; ++q) x[u][q] = r[u * D + q];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UN; ++u) step(a[u] - fi, x[u], k + u);
+    };
+    int k = 1;
+    for (; k + GR * UN <= bound; k += GR * UN) {
+        static_for<0, GR>([&](auto gc) {
+            constexpr int g = decltype(gc)::value;
+            group(pc + g * UN, pr + g * UN * D, k + g * UN);
+            __builtin_amdgcn_sched_barrier(0);                    // the next group's reads stay behind this group's comparisons: UN candidates in registers, not GR x UN
+        });
+        pc += GR * UN; pr += GR * UN * D;
+    }
+    for (; k + UN <= bound; k += UN) { group(pc, pr, k); pc += UN; pr += UN * D; }
+    static_for<0, UN - 1>([&](auto rc) {                          // the remainder: k + r < bound implies k + r - 1 < bound, the tests nest
+        constexpr int r = decltype(rc)::value;
+        if (k + r < bound) {
+            double x[W];
+            if constexpr (W == 2) { const double2 v = *(const double2*)(pr + r * D); x[0] = v.x; x[1] = v.y; }
+            else {
+#pragma unroll
+                for (int q = 0; q < W; ++q) x[q] = pr[r * D + q];
+            }
+            step(pc[r] - fi, x, k + r);
+        }
+    });
+    } else {
     int k = 1;
     for (; k + UN <= bound; k += UN) {
         double a[UN], x[UN][W];
@@ -430,6 +490,7 @@ __device__ __forceinline__ bool fdr_exact(const RlLds& L, int D, int rk, int d0,
 #pragma unroll
         for (int q = 0; q < W; ++q) x[q] = col[k * D + q];
         step(L.NCS[k] - fi, x, k);
+    }
     }
     const double thr = fabs(a0) * range * 0x1p-49;               // |a* b_j| <= |a_0| x range for every pair of the item
     return a0 < 0. && !(tiem > f64_hi_as_f32(thr) * 1.0000005f);
@@ -523,7 +584,7 @@ __device__ __noinline__ void fdr_settle_own(const double* __restrict__ NC, const
 // 6.7 % of the wave-passes for a second scan, +10.4 % per generation against +3.5 % of instructions; (b) the flagged lanes' items settled by their own wave right behind
 // the pass (readlane + fdr_settle): the serial ~250-instruction chain then sits inside the scan of a wave the other three wait for, +4.8 % in the driver window against
 // +3.9 % for the list, +10.6 % against +8.8 % over whole episodes.
-template <int W, int UN, bool TIE, int THREADS>
+template <int W, int UN, bool TIE, int THREADS, int GR = 1>
 __device__ __forceinline__ void fdr_pass(const RlLds& L, const int* ORDER, const int* NLESS, int NP, int D, int tid, double range, unsigned long long* cnt = nullptr)
 {
     const int DW = D / W, NI = NP * DW;
@@ -546,7 +607,7 @@ __device__ __forceinline__ void fdr_pass(const RlLds& L, const int* ORDER, const
             { const int up = 1 + (bound - 1 + UN - 1) / UN * UN; bound = bound > 0 && up <= NP ? up : bound; }
 #endif
             int kb[W];
-            const bool tie = fdr_exact<W, UN, TIE>(L, D, rk, d0, bound, kb, range);
+            const bool tie = fdr_exact<W, UN, TIE, GR>(L, D, rk, d0, bound, kb, range);
 #pragma unroll
             for (int q = 0; q < W; ++q) L.KB[rk * D + d0 + q] = (uint8_t)kb[q];
 #ifdef MBX_FDR_COUNT
@@ -1167,6 +1228,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
     bool done = false;
     int g = 0;
     __syncthreads();
+    if constexpr (MBX_RL_PRIO && THREADS == 256) __builtin_amdgcn_s_setprio(1);      // (straight-line code every wave of the workgroup runs, like the two calls around the FDR pass)
     for (; g < n_gens && !done; ++g) {
         // the thread index is re-materialised every generation: otherwise the compiler hoists all the index arithmetic of the body out of
         // the loop and spills it (528 B of scratch per thread), which the one-generation kernel never has to carry
@@ -1278,7 +1340,9 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         for (int e = tid; e < NP * D; e += THREADS) L.KB[e] = 0;
         __syncthreads();
 #else
-        fdr_pass<2, (DC == 40 ? MBX_FDR_UNROLL_D40 : MBX_FDR_UNROLL), TIE, THREADS>(L, ORDER, NLESS, NP, D, tid, ub - lb + 1e-5, ar().bp.clk);      // (ends with the barrier that publishes KB)
+        if constexpr (MBX_RL_PRIO && THREADS == 256) __builtin_amdgcn_s_setprio(0);
+        fdr_pass<2, (DC == 40 ? MBX_FDR_UNROLL_D40 : MBX_FDR_UNROLL), TIE, THREADS, (THREADS == 256 ? MBX_FDR_GROUPS : 1)>(L, ORDER, NLESS, NP, D, tid, ub - lb + 1e-5, ar().bp.clk);      // (ends with the barrier that publishes KB)
+        if constexpr (MBX_RL_PRIO && THREADS == 256) __builtin_amdgcn_s_setprio(1);
 #endif
         // (Measured and dropped, round 3: dealing config 5's half-empty last pass -- 512 items of the highest ranks on 1024 threads -- as single
         // coordinates, one per thread, so that every wave scans: 1.80 -> 1.94 ms per generation; the one-coordinate scan repeats the cost difference

@@ -27,8 +27,17 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPFLAGS = '--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DMBX_NOINLINE_MATH -fPIC -fvisibility=default'.split()
-OBJS = ['mbx.o', 'mbx_run_rlepso_c5.o', 'mbx_run_rlepso_fast.o', 'mbx_run_rlepso_d40.o', 'mbx_run_lde.o', 'mbx_run_dedqn.o', 'mbx_run_nrlpso.o', 'mbx_run_sahlpso.o',
-        'mbx_run_les.o', 'mbx_run_l2l.o', 'mbx_run_rlhpsde.o', 'mbx_run_nlshade.o']                                        # every object of csrc/Makefile but mbx_run_rlepso.o
+
+
+def makefile_objs():
+    """Every object of csrc/Makefile but mbx_run_rlepso.o (the translation unit the variants recompile): the list follows the Makefile."""
+    text = open(os.path.join(ROOT, 'metabox_amd', 'csrc', 'Makefile')).read()
+    objs = re.search(r'^OBJS\s*=\s*(.+)$', text, re.M).group(1).split()
+    assert 'mbx_run_rlepso.o' in objs and all(o.endswith('.o') for o in objs), objs
+    return [o for o in objs if o != 'mbx_run_rlepso.o']
+
+
+OBJS = makefile_objs()
 SITE_PART, SITE_ELEM_A, SITE_TOURN = 2, 0, 17                 # include/mbx_layout.h
 VARIANTS = {
     'full': [],
@@ -47,8 +56,13 @@ VARIANTS = {
     # not ablations but A/B switches of the full kernel (same results): what one trim is worth, as full - variant (TRIMS)
     'per_item_tourn': ['-DMBX_RL_LISTED_TOURN=0'],             # the move with one tournament draw per wave-pass, as k_rlepso_step has it
     'round_bound': ['-DMBX_FDR_ROUND_BOUND'],                  # the scan's bound rounded up to whole unrolled groups (measured and dropped)
+    'one_group': ['-DMBX_FDR_GROUPS=1'],                       # the scan's loops as before the third budget: one group per trip, indexed remainder
+    'two_groups': ['-DMBX_FDR_GROUPS=2'],                      # two groups (8 candidates) per trip instead of the shipped three
+    'no_prio': ['-DMBX_RL_PRIO=0'],                            # no s_setprio around the FDR pass (scalar instructions: the vector count is the same; the A/B is one of time)
 }
-TRIMS = [('tournaments compacted per wave', 'full', 'per_item_tourn'), ('scan bound rounded up to whole groups (not shipped)', 'round_bound', 'full')]
+TRIMS = [('tournaments compacted per wave', 'full', 'per_item_tourn'), ('scan bound rounded up to whole groups (not shipped)', 'round_bound', 'full'),
+         ('scan: three groups per trip from one pair of address registers, straight-line remainder', 'full', 'one_group'),
+         ('scan: two groups per trip instead of three (not shipped)', 'two_groups', 'full'), ('wave priority 1 outside the FDR pass, 0 inside (scalar instructions: no vector instruction is saved)', 'full', 'no_prio')]
 # phase -> (minuend variant, subtrahend variant): instructions of the phase = count(minuend) - count(subtrahend)
 PHASES = [
     ('policy draw', 'full', 'no_policy'),
