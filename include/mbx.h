@@ -116,6 +116,7 @@ int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, double* d_f,
 #define MBX_ALGO_RLHPSDE 24 /* src/optimizer/rl_hpsde_optimizer.py  one step = one update (NP FEs) + the landscape walk (201 FEs), np = 18 dim shrinking towards 4, dim <= 40, max_fes > np + 201; rollout entry point: include/mbx_rlhpsde.h (22 and 23 are not assigned and stay rejected) */
 #define MBX_ALGO_NLSHADE 25 /* src/optimizer/nl_shade_lbc.py       one step = one update (NP FEs), np = 23 dim shrinking non-linearly to 4, dim <= 40, max_fes > np -- classic baseline, no agent; n updates per launch: include/mbx_nlshade.h */
 #define MBX_ALGO_L2L    26  /* src/optimizer/l2l_optimizer.py      one step = one point proposed by an LSTM (1 FE, 100 steps at most); np = 1, dim <= 40; actions = x_raw [dim] float64; weights per instance set and the resident rollout: include/mbx_l2l.h */
+#define MBX_ALGO_SYMBOL 27  /* src/optimizer/symbol_optimizer.py   one step = one action of 5 sub-steps (5 NP FEs) under an update rule handed over as an expression tree; np in [4, 128] (the reference: 100), dim in [2, 40]; actions = [126] float64 (63 tokens, 63 constants); per-instance rules and the resident rollout: include/mbx_symbol.h */
 #define MBX_ALGO_SAHLPSO 20 /* src/optimizer/sahlpso.py            one step = one pass over the live particles (NP FEs, NP shrinking 40 -> 4; fewer when the episode ends inside the pass), np = 40, dim <= 40, max_fes > 40 -- classic baseline, no agent */
 
 typedef struct mbx_algo_cfg {

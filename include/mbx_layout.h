@@ -1082,6 +1082,75 @@
 #define MBX_SC_L2L_Y0    11   /* y of step 1 */
 #define MBX_SC_L2L_Y     12   /* y of the last step */
 
+/* ---------------------------------------------------------------- 22. SYMBOL (symbol_optimizer.py, symbol_related/population.py) layouts
+ * MBX_ALGO_SYMBOL (27), np in [4, 128], dim in [2, 40].  An action is an UPDATE RULE, a heap-ordered expression tree of MBX_SYM_SLOTS = 2^6 - 1 slots
+ * (children of p at 2p + 1 and 2p + 2, -1 = empty) over the tokens below with a float64 constant per slot, applied for n_substeps (the reference: 5)
+ * sub-steps: next = x + f(x, gb, gw, dx, randx.., pb), the periodic wrap lb + floored_mod(next - ub, ub - lb), one evaluation of the NP rows and
+ * Population.update.  The tree is evaluated as the reference's parenthesised infix string is: (left op right), -(child), float64, no contraction.
+ * tokens: 0 '+', 1 '*' (binary), 2 '-' (unary, left child only), 3 'C-1', 4 'C0' (constants: the value is consts[slot], already scaled by its
+ *         power of ten), 5 x, 6 gb, 7 gw, 8 dx (= delta_x), 9 randx, 10 pb.  The k-th randx leaf in post-order (= left to right in the string) gathers whole rows
+ *         of the PRE-MOVE x by the k-th index row of the sub-step.  mbx_step takes the program as [B, 126] float64: 63 tokens, then 63 constants.
+ * A malformed program (empty or leaf root, unknown token, operator with an empty child or below slot 31, a node under a leaf / an empty slot / on the
+ * right of a unary) leaves the instance untouched and sets d_n_bad.
+ * state block: x[NP*D] pbest_pos[NP*D] delta_x[NP*D] cost[NP] pbest[NP] gbest_pos[D] gworst_pos[D] cbest_pos[D] feat[10] scalars[16]
+ *              cost_curve[n_logpoint+1] idx[MBX_SYM_SUB_MAX][MBX_SYM_RANDX_MAX][NP] as BYTES (the index rows the last action drew, sub-step major).
+ *   feat: the nine features of feature_encoding (population.py:175-209) after the last completed action (or the reset); slot 9 is padding.
+ *   scalars beyond the common ones (MBX_SC_GEN counts the sub-steps of the episode; plus one it is the Philox generation word): the sub-steps done of
+ *   the action in progress, gworst_cost, cbest_cost, cbest_index, stag_count, pre_gbest, init_cost.
+ * tape: pos_u[NP*D] (x = -ub + (ub - -ub) u, Population.reset) noise_init[3*NP], then per sub-step s < MBX_SYM_SUB_MAX: idx[32][NP] (as doubles) noise[3*NP].
+ * Philox: reset (gen 0): MBX_SITE_ELEM_R(e): u53(w0,w1) = pos_u; noise MBX_SITE_NOISE1_A/B(i).
+ *         sub-step: MBX_SITE_SYM_IDX(k*NP + i): mulhi(w0, NP) = index i of randx occurrence k; noise MBX_SITE_NOISE0_A/B(i).
+ * Features, in the kernel's order (np_sum = numpy's pairwise block, mbx_npsum.hpp): den = gworst - gbest + 1e-8, maxd = sqrt((ub - lb)^2 D);
+ *   f1 = np_sum_i((c_i - gbest) / den) / NP;  f2 = (np_sum_i(np_sum_j |x_i - x_j|) / (NP NP)) / maxd, |.| = sqrt of the squares summed d ascending from 0.;
+ *   f3 = std(c) / (std(fit) + 1e-8), std(v) = sqrt(np_sum((v - np_sum(v) / NP)^2) / NP), fit = gworst for i < NP / 2, else gbest;
+ *   f4 = (max_fes - fes) / max_fes;  f5 = stag / (max_fes / NP, integers);  f6 / f8 = np_sum_i(sqrt(np_sum_d (x_id - p_d)^2) / maxd) / NP for p = cbest / gbest position;
+ *   f7 = np_sum_i((c_i - cbest) / den) / NP;  f9 = gbest < pre_gbest.                                                                                  */
+#define MBX_SYM_DIM_MAX    40
+#define MBX_SYM_NP_MAX     128
+#define MBX_SYM_SLOTS      63
+#define MBX_SYM_NTOK       11
+#define MBX_SYM_RANDX_MAX  32
+#define MBX_SYM_SUB_MAX    8
+#define MBX_SYM_SKIP       5     /* sub-steps of an mbx_step action: the reference's skip_step */
+#define MBX_SYM_NFEAT      9
+#define MBX_SYM_TOK_ADD    0
+#define MBX_SYM_TOK_MUL    1
+#define MBX_SYM_TOK_NEG    2
+#define MBX_SYM_TOK_CM1    3
+#define MBX_SYM_TOK_C0     4
+#define MBX_SYM_TOK_X      5
+#define MBX_SYM_TOK_GB     6
+#define MBX_SYM_TOK_GW     7
+#define MBX_SYM_TOK_DX     8
+#define MBX_SYM_TOK_RANDX  9
+#define MBX_SYM_TOK_PB     10
+#define MBX_SYMBOL_TAPE_POS(NP, D)        ((int64_t)0)
+#define MBX_SYMBOL_TAPE_NOISE_INIT(NP, D) ((int64_t)(NP) * (D))
+#define MBX_SYMBOL_TAPE_SUB(NP, D, S)     ((int64_t)(NP) * (D) + 3 * (int64_t)(NP) + (int64_t)(S) * (MBX_SYM_RANDX_MAX + 3) * (int64_t)(NP))
+#define MBX_SYMBOL_SUB_IDX(NP, D)         ((int64_t)0)
+#define MBX_SYMBOL_SUB_NOISE(NP, D)       ((int64_t)MBX_SYM_RANDX_MAX * (NP))
+#define MBX_SYMBOL_TAPE_STRIDE(NP, D)     MBX_SYMBOL_TAPE_SUB(NP, D, MBX_SYM_SUB_MAX)
+#define MBX_SYMBOL_ST_X(NP, D)            ((int64_t)0)
+#define MBX_SYMBOL_ST_PBPOS(NP, D)        ((int64_t)(NP) * (D))
+#define MBX_SYMBOL_ST_DX(NP, D)           (2 * (int64_t)(NP) * (D))
+#define MBX_SYMBOL_ST_COST(NP, D)         (3 * (int64_t)(NP) * (D))
+#define MBX_SYMBOL_ST_PBEST(NP, D)        (3 * (int64_t)(NP) * (D) + (NP))
+#define MBX_SYMBOL_ST_GBPOS(NP, D)        (3 * (int64_t)(NP) * (D) + 2 * (int64_t)(NP))
+#define MBX_SYMBOL_ST_GWPOS(NP, D)        (3 * (int64_t)(NP) * (D) + 2 * (int64_t)(NP) + (D))
+#define MBX_SYMBOL_ST_CBPOS(NP, D)        (3 * (int64_t)(NP) * (D) + 2 * (int64_t)(NP) + 2 * (int64_t)(D))
+#define MBX_SYMBOL_ST_FEAT(NP, D)         (3 * (int64_t)(NP) * (D) + 2 * (int64_t)(NP) + 3 * (int64_t)(D))
+#define MBX_SYMBOL_ST_SCALARS(NP, D)      (MBX_SYMBOL_ST_FEAT(NP, D) + 10)
+#define MBX_SYMBOL_ST_IDX(NP, D, NLOG)    (MBX_SYMBOL_ST_SCALARS(NP, D) + MBX_NSCALAR + (int64_t)(NLOG) + 1)      /* in doubles; the region holds bytes */
+#define MBX_SYMBOL_STATE_DOUBLES(NP, D, NLOG) (MBX_SYMBOL_ST_IDX(NP, D, NLOG) + (int64_t)MBX_SYM_SUB_MAX * MBX_SYM_RANDX_MAX * (NP) / 8 + 1)
+#define MBX_SC_SYM_SUB       9    /* sub-steps done of the action in progress (0 between actions) */
+#define MBX_SC_SYM_GWORST    10   /* gworst_cost: the worst cost ever seen (strict >) */
+#define MBX_SC_SYM_CBEST     11   /* cbest_cost: the best of the last evaluated generation */
+#define MBX_SC_SYM_CBEST_IDX 12
+#define MBX_SC_SYM_STAG      13   /* stag_count */
+#define MBX_SC_SYM_PRE_GBEST 14   /* gbest at the start of the last action */
+#define MBX_SC_SYM_INIT_COST 15   /* the best cost of the initial population */
+#define MBX_SITE_SYM_IDX     84u
+
 #define MBX_PHILOX_M0 0xD2511F53u
 #define MBX_PHILOX_M1 0xCD9E8D57u
 #define MBX_PHILOX_W0 0x9E3779B9u

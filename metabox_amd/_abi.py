@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/mbx.h, include/mbx_les.h, include/mbx_l2l.h, include/mbx_rlhpsde.h and include/mbx_nlshade.h (libmbx.so).
+"""ctypes binding of the C-ABI in include/mbx.h, include/mbx_les.h, include/mbx_l2l.h, include/mbx_symbol.h, include/mbx_rlhpsde.h and include/mbx_nlshade.h (libmbx.so).
 
 This is the stub a maintainer of the reference would add to reach the HIP path (INTEGRATION.md shows it
 in isolation).  The library is built in-tree by ``__graft_entry__.build()`` / ``make -C metabox_amd/csrc``;
@@ -74,6 +74,7 @@ ALGO_LES = 21
 ALGO_RLHPSDE = 24    # (22 and 23 are not assigned)
 ALGO_NLSHADE = 25
 ALGO_L2L = 26
+ALGO_SYMBOL = 27
 POLICY_RLEPSO, POLICY_RLPSO = 0, 1
 _ARRAY_FIELDS = ('dshift', 'm1', 'm2', 'v0', 'v1', 'v2', 'py', 'pc', 'pw')
 
@@ -117,7 +118,7 @@ class MbxError(RuntimeError):
 
 
 def load_lib():
-    """Load libmbx.so and declare the prototypes of every symbol in include/mbx.h, include/mbx_les.h, include/mbx_l2l.h, include/mbx_rlhpsde.h and include/mbx_nlshade.h."""
+    """Load libmbx.so and declare the prototypes of every symbol in include/mbx.h, include/mbx_les.h, include/mbx_l2l.h, include/mbx_symbol.h, include/mbx_rlhpsde.h and include/mbx_nlshade.h."""
     global _lib
     if _lib is not None:
         return _lib
@@ -168,6 +169,7 @@ def load_lib():
         'mbx_les_rollout': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         'mbx_l2l_set_params': (C.c_int, [vp, vp, C.c_int, vp]),
         'mbx_l2l_rollout': (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+        'mbx_symbol_rollout': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
         'mbx_rlhpsde_rollout': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
         'mbx_nlshade_run': (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
         'mbx_gleet_policy': (C.c_int, [vp, C.POINTER(GleetActor), vp, vp, vp, vp]),
@@ -207,6 +209,9 @@ LES_SYMBOLS = ('mbx_les_set_params', 'mbx_les_rollout')
 
 # the entry points of include/mbx_l2l.h (L2L)
 L2L_SYMBOLS = ('mbx_l2l_set_params', 'mbx_l2l_rollout')
+
+# the entry point of include/mbx_symbol.h (SYMBOL)
+SYMBOL_SYMBOLS = ('mbx_symbol_rollout',)
 
 # the entry point of include/mbx_rlhpsde.h (RL-HPSDE)
 RLHPSDE_SYMBOLS = ('mbx_rlhpsde_rollout',)

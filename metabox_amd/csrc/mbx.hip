@@ -1,5 +1,5 @@
 // mbx.hip — libmbx.so: kernels' launch code and the C-ABI of include/mbx.h.
-// Build: make -C metabox_amd/csrc  (thirteen translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip, mbx_run_l2l.hip, mbx_run_rlhpsde.hip, mbx_run_nlshade.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
+// Build: make -C metabox_amd/csrc  (fourteen translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip, mbx_run_l2l.hip, mbx_run_symbol.hip, mbx_run_rlhpsde.hip, mbx_run_nlshade.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -48,6 +48,7 @@
 #include "mbx_run_nrlpso.hip"          // ... and the NRLPSO ones
 #include "mbx_run_les.hip"
 #include "mbx_run_l2l.hip"
+#include "mbx_run_symbol.hip"
 #include "mbx_run_rlhpsde.hip"
 #include "mbx_run_nlshade.hip"
 #endif
@@ -952,6 +953,35 @@ static int l2l_prepare_batch(mbx_batch*, const AlgoGeom& g) { HIP_TRY(l2l_prepar
 MBX_RESET_FN(l2l_reset) { l2l_launch_reset(make_params(b), stream, d_state_out); }
 MBX_STEP_FN(l2l_step) { l2l_launch_step(make_params(b), stream, (const double*)d_actions, MBX_OUT); return MBX_OK; }   // the host ran the cell: actions = x_raw
 
+// ---- SYMBOL: mbx_run_symbol.hip
+static int symbol_check(const mbx_algo_cfg& c)
+{
+    // the index rows are bytes and one lane owns a row in the bookkeeping; the rule's operand gathers and the evaluator share two position buffers.
+    // dim >= 2 is the library's common lower bound (check_dim: the evaluator's 2-wide tiles and FastDiv are built for D >= 2), stated here so that SYMBOL's own message names it
+    // (a geometry outside these limits is a valid request this build does not implement, like a protein batch: MBX_E_UNSUPPORTED, the code every SYMBOL refusal carries)
+    if (c.np < 4 || c.np > MBX_SYM_NP_MAX) return fail(MBX_E_UNSUPPORTED, "SYMBOL runs np in [4, %d], not %d", MBX_SYM_NP_MAX, c.np);
+    if (c.dim < 2 || c.dim > MBX_SYM_DIM_MAX) return fail(MBX_E_UNSUPPORTED, "SYMBOL runs dim in [2, %d], not %d", MBX_SYM_DIM_MAX, c.dim);
+    return MBX_OK;
+}
+
+static AlgoGeom symbol_geom(const mbx_algo_cfg& c) { return MBX_GEOM(SYMBOL, sym_lds_doubles(c.np, c.dim, sym_resident(c.np, c.dim)), MBX_SYM_NFEAT, 2 * MBX_SYM_SLOTS); }
+static int symbol_prepare_batch(mbx_batch* b, const AlgoGeom& g)
+{
+    for (int i = 0; i < b->B; ++i)
+        if (b->suite->h_problems[b->h_problem_idx[i]].kind == MBX_KIND_PROTEIN) return fail(MBX_E_UNSUPPORTED, "SYMBOL: protein docking problems are not supported");
+    HIP_TRY(symbol_prepare(lds_of(g)));
+    return MBX_OK;
+}
+MBX_RESET_FN(symbol_reset) { symbol_launch_reset(make_params(b), stream, d_state_out); }
+MBX_STEP_FN(symbol_step)      // the program as actions: MBX_SYM_SKIP sub-steps
+{
+    const BatchParams bp = make_params(b);
+    if (b->rollout_per_generation)
+        for (int g = 0; g < MBX_SYM_SKIP; ++g) symbol_launch_run(bp, stream, nullptr, nullptr, (const double*)d_actions, 1, MBX_SYM_SKIP, MBX_OUT, nullptr);
+    else symbol_launch_run(bp, stream, nullptr, nullptr, (const double*)d_actions, MBX_SYM_SKIP, MBX_SYM_SKIP, MBX_OUT, nullptr);
+    return MBX_OK;
+}
+
 // ---- RL-HPSDE: mbx_run_rlhpsde.hip
 static int rlhpsde_check(const mbx_algo_cfg& c)
 {
@@ -1065,6 +1095,7 @@ static const AlgoOps kAlgoOps[] = {
     {MBX_ALGO_SAHLPSO, "SAHLPSO", false, false, sahlpso_check, sahlpso_geom, sahlpso_prepare_batch, sahlpso_reset, sahlpso_step, nullptr},
     {MBX_ALGO_LES, "LES", false, false, les_check, les_geom, les_prepare_batch, les_reset, les_step, nullptr},
     {MBX_ALGO_L2L, "L2L", true, false, l2l_check, l2l_geom, l2l_prepare_batch, l2l_reset, l2l_step, nullptr},
+    {MBX_ALGO_SYMBOL, "SYMBOL", true, false, symbol_check, symbol_geom, symbol_prepare_batch, symbol_reset, symbol_step, nullptr},
     {MBX_ALGO_RLHPSDE, "RL-HPSDE", true, false, rlhpsde_check, rlhpsde_geom, rlhpsde_prepare_batch, rlhpsde_reset, rlhpsde_step, nullptr},
     {MBX_ALGO_NLSHADE, "NL_SHADE_LBC", false, false, nlshade_check, nlshade_geom, nlshade_prepare_batch, nlshade_reset, nlshade_step, nullptr},
 };
@@ -1523,6 +1554,22 @@ extern "C" int mbx_l2l_rollout(mbx_batch* b, int n_steps, double* d_state_out, d
             l2l_launch_run(bp, generic, (hipStream_t)stream, b->d_l2l_params, b->d_l2l_set, b->l2l_n_sets, 1, d_state_out, d_reward_out, d_done_out);
     else
         l2l_launch_run(bp, generic, (hipStream_t)stream, b->d_l2l_params, b->d_l2l_set, b->l2l_n_sets, n_steps, d_state_out, d_reward_out, d_done_out);
+    HIP_TRY(hipGetLastError());
+    return MBX_OK;
+}
+
+extern "C" int mbx_symbol_rollout(mbx_batch* b, const int32_t* d_tokens, const double* d_consts, int n_substeps, double* d_state_out, double* d_reward_out,
+                                  uint8_t* d_done_out, int32_t* d_n_bad, void* stream)
+{
+    if (!b || !d_tokens || !d_consts) return fail(MBX_E_ARG, "mbx_symbol_rollout: bad arguments");
+    if (b->cfg.algo != MBX_ALGO_SYMBOL) return fail(MBX_E_UNSUPPORTED, "mbx_symbol_rollout: the batch is not a SYMBOL batch");
+    if (n_substeps < 1 || n_substeps > MBX_SYM_SUB_MAX) return fail(MBX_E_ARG, "mbx_symbol_rollout: n_substeps must be in [1, %d]", MBX_SYM_SUB_MAX);
+    const BatchParams bp = make_params(b);
+    if (b->rollout_per_generation)
+        for (int g = 0; g < n_substeps; ++g)
+            symbol_launch_run(bp, (hipStream_t)stream, d_tokens, d_consts, nullptr, 1, n_substeps, d_state_out, d_reward_out, d_done_out, d_n_bad);
+    else
+        symbol_launch_run(bp, (hipStream_t)stream, d_tokens, d_consts, nullptr, n_substeps, n_substeps, d_state_out, d_reward_out, d_done_out, d_n_bad);
     HIP_TRY(hipGetLastError());
     return MBX_OK;
 }

@@ -641,6 +641,39 @@ MBX_LDS_WALK L2lLds l2l_layout(C& c, int D)
 __host__ __device__ inline int64_t l2l_lds_doubles(int D) { LdsSize c; l2l_layout(c, D); return align2(c.n); }
 __device__ __forceinline__ L2lLds l2l_carve(double* base, int D) { LdsCarve c{base}; return l2l_layout(c, D); }
 
+// ------------------------------------------------------------------------------------------------ SYMBOL (mbx_symbol.hpp)
+struct SymLds {
+    double *A, *Bf, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *PBC, *GB, *GW, *CB, *RED, *PB, *DX, *PCST, *CST;
+    int *FLAG, *TOK, *PROG;
+    uint8_t* IDX;
+    // the evaluator's rows are the candidates (`cand`); the buffer of the positions they were moved from is its scratch Z
+    __device__ __forceinline__ EvalLds eval(double* cand, double* scratch) const { return EvalLds{cand, scratch, T, M1T, M2T, DSH, V0, V1, V2, NC}; }
+};
+
+// A | Bf: the two position buffers, x and the candidates by turns (each as long as the evaluator's scratch Z, whose part the other one plays during an
+// evaluation); PB | DX: pbest_pos and delta_x where they fit (`resident`), else they stay in the state block: the move reads only its own element of
+// them.  TOK / CST: the rule by slot; PCST / PROG: the same in post-order; IDX: the index rows of a sub-step, bytes.
+MBX_LDS_WALK SymLds sym_layout(C& c, int NP, int D, bool resident)
+{
+    const int64_t P = align2(NP), NE = align2((int64_t)NP * D), DV = align2(D);
+    SymLds L{};
+    L.A = c.take(eval_z_doubles(NP, D));  L.Bf = c.take(eval_z_doubles(NP, D));  L.T = c.take(eval_t_doubles(NP, D));
+    lds_eval_consts(c, D, true, L.M1T, L.M2T, L.DSH, L.V0, L.V1, L.V2);
+    L.NC = c.take(P);  L.PBC = c.take(P);  L.GB = c.take(DV);  L.GW = c.take(DV);  L.CB = c.take(DV);  L.RED = c.take(16);
+    L.PB = c.take(resident ? NE : 0);  L.DX = c.take(resident ? NE : 0);
+    L.PCST = c.take(64);  L.CST = c.take(64);
+    L.FLAG = c.template take<int>(align2((P + 1) / 2));  L.TOK = c.template take<int>(32);  L.PROG = c.template take<int>(32);
+    L.IDX = c.template take<uint8_t>(align2(((int64_t)MBX_SYM_RANDX_MAX * NP + 7) / 8));
+    return L;
+}
+__host__ __device__ inline int64_t sym_lds_doubles(int NP, int D, bool resident) { LdsSize c; sym_layout(c, NP, D, resident); return c.n; }
+// pbest_pos and delta_x on chip wherever the whole set fits the 160 KB of a gfx950 workgroup NEXT TO the kernels' static LDS: the block votes of sym_check
+// (__syncthreads_count / __syncthreads_or) take 256 B of it in k_symbol_step and k_symbol_run.  kSymStaticLdsMax is the room left for that; symbol_prepare
+// holds every kernel's static size against it.  (The largest geometry, NP 128 / D 40, is 159040 B without the two arrays: it fits with the room to spare.)
+constexpr int64_t kSymStaticLdsMax = 1024, kSymLdsLimit = 160 * 1024;
+__host__ __device__ inline bool sym_resident(int NP, int D) { return sym_lds_doubles(NP, D, true) * 8 + kSymStaticLdsMax <= kSymLdsLimit; }
+__device__ __forceinline__ SymLds sym_carve(double* base, int NP, int D, bool resident) { LdsCarve c{base}; return sym_layout(c, NP, D, resident); }
+
 // ------------------------------------------------------------------------------------------------ QLPSO (mbx_qlpso.hpp)
 struct QlLds {
     double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *RED, *POP, *COST, *MEAN, *DIST, *SC;

@@ -69,6 +69,14 @@ void l2l_launch_step(const BatchParams& bp, hipStream_t stream, const double* d_
 void l2l_launch_run(const BatchParams& bp, bool generic, hipStream_t stream, const double* d_params, const int32_t* d_set_of, int n_sets, int n_steps,
                     double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
 }  // namespace mbx
+// SYMBOL (mbx_symbol.hpp): likewise in mbx_run_symbol.hip
+namespace mbx {
+hipError_t symbol_prepare(size_t lds_bytes);
+void symbol_launch_reset(const BatchParams& bp, hipStream_t stream, double* d_state_out);
+// n_sub sub-steps of an action of n_action; the program as (d_tokens, d_consts) or as d_actions [B, 126] float64
+void symbol_launch_run(const BatchParams& bp, hipStream_t stream, const int32_t* d_tokens, const double* d_consts, const double* d_actions, int n_sub,
+                       int n_action, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, int32_t* d_n_bad);
+}  // namespace mbx
 // RL-HPSDE (mbx_rlhpsde.hpp): likewise in mbx_run_rlhpsde.hip
 namespace mbx {
 hipError_t rlhpsde_prepare(size_t lds_bytes);

@@ -139,12 +139,12 @@ class Batch:
         return self.state
 
     def step(self, actions):
-        """actions: CUDA tensor [B, action_dim] (float32; int32 for the tabular agents, float64 for L2L).  Returns (state, reward, done) device tensors that are
+        """actions: CUDA tensor [B, action_dim] (float32; int32 for the tabular agents, float64 for L2L and SYMBOL).  Returns (state, reward, done) device tensors that are
         overwritten by the next call."""
         if self.action_dim > 0:
             want = torch.int32 if self.cfg.algo in (_abi.ALGO_DEDDQN, _abi.ALGO_QLPSO, _abi.ALGO_DEDQN, _abi.ALGO_NRLPSO, _abi.ALGO_RLHPSDE) else torch.float32
-            if self.cfg.algo == _abi.ALGO_L2L:
-                want = torch.float64           # x_raw, the LSTM's float64 output
+            if self.cfg.algo in (_abi.ALGO_L2L, _abi.ALGO_SYMBOL):
+                want = torch.float64           # L2L: x_raw, the LSTM's float64 output; SYMBOL: 63 tokens and 63 constants
             assert actions.is_cuda and actions.is_contiguous() and actions.dtype == want
             assert actions.numel() == self.B * self.action_dim
         else:
@@ -284,6 +284,20 @@ class Batch:
         between (``mbx_l2l_rollout``); finished instances stay frozen.  Returns (state = the last y [B, 1], reward = sum y / y_0, done)."""
         _abi.check(self.lib.mbx_l2l_rollout(self._h, int(n_steps), _ptr(self.state), _ptr(self.reward), _ptr(self.done), _stream()))
         return self.state, self.reward, self.done
+
+    def symbol_rollout(self, tokens, consts, n_substeps=5):
+        """One SYMBOL action of every instance under ITS OWN update rule in ONE launch (``mbx_symbol_rollout``): tokens [B, 63] integers (the heap-ordered
+        expression tree, -1 = empty), consts [B, 63] float64 (the value of every constant leaf).  Returns (state = the nine features [B, 9], reward, done,
+        n_bad int32 [B]: 1 where the program was malformed and the instance was left untouched)."""
+        tk = torch.as_tensor(np.ascontiguousarray(tokens, dtype=np.int32)).to(self.device) if not torch.is_tensor(tokens) else tokens
+        cs = torch.as_tensor(np.ascontiguousarray(consts, dtype=np.float64)).to(self.device) if not torch.is_tensor(consts) else consts
+        assert tk.is_cuda and tk.dtype == torch.int32 and tk.is_contiguous() and tuple(tk.shape) == (self.B, 63)
+        assert cs.is_cuda and cs.dtype == torch.float64 and cs.is_contiguous() and tuple(cs.shape) == (self.B, 63)
+        if getattr(self, '_n_bad', None) is None:
+            self._n_bad = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        _abi.check(self.lib.mbx_symbol_rollout(self._h, _ptr(tk), _ptr(cs), int(n_substeps), _ptr(self.state), _ptr(self.reward), _ptr(self.done),
+                                               _ptr(self._n_bad), _stream()))
+        return self.state, self.reward, self.done, self._n_bad
 
     def dedqn_rollout(self, weights, n_steps, trajectory=False):
         """`n_steps` DEDQN env steps of every instance in ONE launch, the 4 -> 10 -> 10 -> 3 Q-network evaluated in the kernel and the population

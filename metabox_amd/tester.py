@@ -247,6 +247,29 @@ def rollout(config):
     cache = {}
     for agent_name, opt_name in zip(config.agent_for_rollout, config.optimizer_for_rollout):
         optimizer = _lookup(_optimizers, opt_name)(copy.deepcopy(config))
+        if hasattr(_agents, agent_name) and hasattr(getattr(_agents, agent_name), 'rollout_checkpoints') and _world()[1] == 1:
+            # the policy runs on the host (SYMBOL): all checkpoints in ONE batch, checkpoint-major, every block with the seeds the loop below would give it
+            agents = []
+            for cp in range(n_cp + 1):
+                with open(config.agent_load_dir + agent_name + '/checkpoint' + str(cp) + '.pkl', 'rb') as f:
+                    agents.append(pickle.load(f))
+            pidx, run = instance_table(len(problems), runs)
+            n = len(pidx)
+            from .suite import Suite
+            if id(problems) not in cache:
+                cache[id(problems)] = Suite(problems)
+            seeds = np.concatenate([philox_seed(run, np.arange(n), cp) for cp in range(n_cp + 1)])
+            env = BatchedPBO_Env(problems, optimizer, np.tile(pidx, n_cp + 1), seeds, suite=cache[id(problems)])
+            out = type(agents[0]).rollout_checkpoints(agents, env)
+            cost, fes, ret = (out[k].cpu().numpy().reshape(n_cp + 1, n, -1) for k in ('cost', 'fes', 'return'))
+            env.close()
+            for cp in range(n_cp + 1):
+                for k, p in enumerate(problems):
+                    rows = slice(k * runs, (k + 1) * runs)
+                    results['cost'][str(p)][agent_name][cp] = [_pad51(r) for r in cost[cp, rows]]
+                    results['fes'][str(p)][agent_name][cp] = [float(v) for v in fes[cp, rows, 0]]
+                    results['return'][str(p)][agent_name][cp] = [float(v) for v in ret[cp, rows, 0]]
+            continue
         for cp in range(n_cp + 1):
             with open(config.agent_load_dir + agent_name + '/checkpoint' + str(cp) + '.pkl', 'rb') as f:
                 agent = pickle.load(f)

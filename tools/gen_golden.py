@@ -3240,8 +3240,307 @@ def gen_l2l():
         print(os.path.basename(path), os.path.getsize(path))
         assert os.path.getsize(path) < 1000 * 1024
 
+# ------------------------------------------------------------------------------------------------ SYMBOL
+# symbol_policy.npz : the actor weights of checkpoints 0 and 20 of bbob_easy (nn.LSTM 252 -> 16, output_net 16 -> 11, constval_net 16 -> 4, x_to_c 9 -> 16);
+#                     per generated token of every recorded tree (both checkpoints, plus get_random_seq): the partial tree, the position, the mask, the float32
+#                     logits before masking, the choice and the constant; per tree the state it was generated from, the final tree and the infix string;
+#                     e_logit_base, the largest difference between the reference's LSTM run on one tree and on all trees of a checkpoint at once.
+# symbol_traces*.npz: whole reference episodes (Symbol_Optimizer, is_train = False, np.random.seed(seed); Population.reset's own seed() call is made a no-op in
+#                     memory) at D = 10 on bbob and bbob-noisy, the actions from the shipped policy or hand-built.  Per episode the initial uniforms and
+#                     positions, every index row (uint8; max(1, number of randx) rows per sub-step, flattened action after action) and noise draw, per action the tree, its constants, the string, features, reward, fes, done and the
+#                     curve; for the first, the middle and the last action the whole population state before the action and after each of its sub-steps.
+SYM_TOK = ('+', '*', '-', 'C-1', 'C0', 'x', 'gb', 'gw', 'dx', 'randx', 'pb')
 
-SECTIONS = {'l2l': gen_l2l, 'nlshade': gen_nlshade, 'rlhpsde': gen_rlhpsde, 'les': gen_les, 'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
+
+def symbol_hand_trees():
+    """name -> (tokens [63] int, constants [63] float32 as the actor would leave them)."""
+    T = {t: i for i, t in enumerate(SYM_TOK)}
+    out = {}
+
+    def tree(spec):
+        tok, c = -np.ones(63, dtype=np.int64), np.zeros(63, dtype=np.float32)
+        for slot, v in spec.items():
+            if isinstance(v, tuple):
+                tok[slot], c[slot] = T[v[0]], np.float32(v[1])
+            else:
+                tok[slot] = T[v]
+        return tok, c
+    k = [np.float32(-1. + np.float32(j) * np.float32(0.4)) for j in range(4)]          # the actor's four constants (min_c + choice * interval in float32)
+    out['three'] = tree({0: '*', 1: 'gb', 2: ('C0', k[1])})
+    full = {p: ('+' if p < 15 else '*') for p in range(31)}
+    full.update({p: 'randx' for p in range(31, 63)})
+    out['full'] = tree(full)
+    out['chain'] = tree({0: '-', 1: '-', 3: '-', 7: '-', 15: '-', 31: 'pb'})
+    out['consts'] = tree({0: '+', 1: '*', 2: '*', 3: ('C0', k[3]), 4: 'dx', 5: 'gb', 6: ('C-1', k[1])})
+    out['de'] = tree({0: '+', 1: '*', 2: '*', 3: ('C0', k[3]), 4: '+', 9: 'gb', 10: '-', 21: 'x', 5: '+', 11: 'randx', 12: '-', 25: 'randx', 6: ('C0', k[3])})
+    return out
+
+
+def run_symbol_episode(problem, seed, config, next_action, full_actions=None, max_actions=None):
+    """One reference episode through Symbol_Optimizer.update.  next_action(state float64 [9], t) -> (tokens [63], constants [63] float32)."""
+    from optimizer.symbol_optimizer import Symbol_Optimizer
+    from optimizer.symbol_related.population import Population
+    from agent.symbol_agent import construct_action
+    from agent.symbol_related.tokenizer import MyTokenizer
+    import copy
+    tokenizer = MyTokenizer()
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    opt = Symbol_Optimizer(copy.deepcopy(config))
+    opt.is_train = False
+    draws = {'uniform': [], 'randint': [], 'noise': []}
+    real = {k: getattr(np.random, k) for k in ('seed', 'uniform', 'randint', 'rand', 'randn')}
+
+    def uniform(low=0., high=1., size=None):
+        u = np.random.random_sample(size)
+        draws['uniform'].append(u)
+        return low + (high - low) * u
+
+    def randint(*a, **k):
+        r = real['randint'](*a, **k)
+        draws['randint'].append(np.asarray(r))
+        return r
+
+    def rand(*a):
+        r = real['rand'](*a)
+        draws['noise'].append(np.asarray(r, dtype=np.float64))
+        return r
+
+    def randn(*a):
+        r = real['randn'](*a)
+        draws['noise'].append(np.asarray(r, dtype=np.float64))
+        return r
+    subs = []
+    real_update = Population.update
+
+    def update(self, next_position, filter_survive=False):
+        real_update(self, next_position, filter_survive)
+        subs.append(dict(pos=np.array(self.before_select_pos), cost=np.array(self.c_cost), dx=np.array(self.delta_x), pb=np.array(self.pbest_position),
+                         pbc=np.array(self.pbest_cost), gb=np.array(self.gbest_position), gw=np.array(self.gworst_position), cb=np.array(self.cbest_position),
+                         sc=np.array([self.gbest_cost, self.gworst_cost, self.cbest_cost, self.cbest_index, self.stag_count, self.cur_fes], dtype=np.float64)))
+
+    def noise_rows(lst, NP):
+        a = np.zeros((3, NP))
+        for j, r in enumerate(lst):
+            a[j] = r
+        return a
+    np.random.seed = lambda *a: real['seed'](*a) if a else None
+    np.random.uniform, np.random.randint, np.random.rand, np.random.randn, Population.update = uniform, randint, rand, randn, update
+    try:
+        problem.reset()
+        state = opt.init_population(problem)
+        pop = opt.population
+        NP = pop.pop_size
+        rec = dict(pos_u=draws['uniform'][0], x0=np.array(pop.current_position), cost0=np.array(pop.c_cost), noise0=noise_rows(draws['noise'], NP), state0=np.array(state))
+        assert len(draws['uniform']) == 1 and np.array_equal(rec['x0'], -pop.max_x + (pop.max_x - -pop.max_x) * rec['pos_u'])
+        acts = dict(tok=[], cst=[], cval=[], expr=[], feat=[], reward=[], fes=[], done=[], nrx=[], idx=[], noise=[], cost_len=[], gbest=[])
+        full = {}
+        done, t = False, 0
+        while not done and (max_actions is None or t < max_actions):
+            tok, c32 = next_action(np.array(state), t)
+            expr = construct_action(np.asarray(tok)[None, :], np.asarray(c32, dtype=np.float32)[None, :], tokenizer)
+            cval = np.zeros(63)
+            for slot in range(63):
+                if tok[slot] in (3, 4):
+                    cval[slot] = float(str(np.float32(c32[slot]) * 10 ** (-1 if tok[slot] == 3 else 0)))
+            del subs[:]; del draws['randint'][:]; del draws['noise'][:]
+            pre = dict(pos=np.array(pop.current_position), cost=np.array(pop.c_cost), dx=np.array(pop.delta_x), pb=np.array(pop.pbest_position), pbc=np.array(pop.pbest_cost),
+                       gb=np.array(pop.gbest_position), gw=np.array(pop.gworst_position), cb=np.array(pop.cbest_position),
+                       sc=np.array([pop.gbest_cost, pop.gworst_cost, pop.cbest_cost, pop.cbest_index, pop.stag_count, pop.cur_fes], dtype=np.float64))
+            state, reward, done = opt.update({'expr': expr, 'skip_step': 5}, problem)
+            nrx = expr.count('randx')
+            ndraw = max(1, nrx)                                      # one row is drawn even where the rule has no randx (:149)
+            assert len(subs) == 5 and len(draws['randint']) == 5 * ndraw
+            per = len(draws['noise']) // 5
+            acts['tok'].append(np.asarray(tok, dtype=np.int8)); acts['cst'].append(np.asarray(c32, dtype=np.float32)); acts['cval'].append(cval); acts['expr'].append(expr)
+            acts['feat'].append(np.array(state)); acts['reward'].append(reward); acts['fes'].append(pop.cur_fes); acts['done'].append(done); acts['nrx'].append(nrx)
+            acts['idx'].append(np.array(draws['randint'], dtype=np.uint8).reshape(5, ndraw, NP))
+            acts['noise'].append(np.stack([noise_rows(draws['noise'][s * per:(s + 1) * per], NP) for s in range(5)]))
+            acts['cost_len'].append(len(opt.cost)); acts['gbest'].append(pop.gbest_cost)
+            full[t] = (pre, [dict(d) for d in subs])
+            t += 1
+    finally:
+        for k, v in real.items():
+            setattr(np.random, k, v)
+        Population.update = real_update
+    n = t
+    keep = sorted({0, n // 2, n - 1}) if full_actions is None else full_actions
+    rec.update(tok=np.stack(acts['tok']), cst=np.stack(acts['cst']), cval=np.stack(acts['cval']), expr=np.array(acts['expr']), feat=np.stack(acts['feat']),
+               reward=np.array(acts['reward'], dtype=np.float64), fes=np.array(acts['fes'], dtype=np.int64), done=np.array(acts['done'], dtype=np.uint8),
+               nrx=np.array(acts['nrx'], dtype=np.int16), idx=np.concatenate([a.reshape(-1) for a in acts['idx']]) if n else np.zeros(0, np.uint8),
+               cost_len=np.array(acts['cost_len'], dtype=np.int16), gbest=np.array(acts['gbest'], dtype=np.float64), curve=np.array(opt.cost, dtype=np.float64),
+               full_actions=np.array(keep, dtype=np.int16), max_fes=np.int64(config.maxFEs), log_interval=np.int64(config.log_interval), n_logpoint=np.int64(config.n_logpoint))
+    if any(a.any() for a in acts['noise']):
+        rec['noise'] = np.stack(acts['noise'])
+    # every sub-step's costs (what the restatement is fed) and scalars, the whole state for the kept actions
+    rec['sub_cost'] = np.stack([np.stack([d['cost'] for d in full[a][1]]) for a in range(n)])
+    rec['sub_sc'] = np.stack([np.stack([d['sc'] for d in full[a][1]]) for a in range(n)])
+    for a in keep:
+        pre, ss = full[a]
+        for k, v in pre.items():
+            rec[f'full{a}/pre/{k}'] = v
+        prev = pre['pos']
+        for d in ss:                                                 # delta_x is not stored: it is exactly the difference of two stored position blocks
+            assert np.array_equal(d['dx'], d['pos'] - prev)
+            prev = d['pos']
+        for k in ('pos', 'pb', 'pbc', 'gb', 'gw', 'cb'):
+            rec[f'full{a}/sub/{k}'] = np.stack([d[k] for d in ss])
+    return rec
+
+
+def gen_symbol():
+    import agent.symbol_related.lstm as lstm_mod
+    scratch = tempfile.mkdtemp()
+    root = os.path.join(ref_import.REF_SRC, 'agent_model', 'rollout', 'bbob_easy', 'Symbol_Agent')
+    agents = {k: load_shipped(os.path.join(root, f'checkpoint{k}.pkl')) for k in (0, 20)}
+    pol = {}
+    for k, a in agents.items():
+        for name, v in a.actor.state_dict().items():
+            pol[f'w{k}/{name}'] = v.detach().cpu().numpy().copy()
+    # ---- per-token records: hooks on the names lstm.py calls
+    tokens = dict(seq=[], pos=[], mask=[], logits=[], choice=[], cval=[], tree=[])
+    trees = dict(state=[], ckpt=[], tok=[], cst=[], expr=[], first=[])
+    cur = {'on': False}
+    real_mask, real_choice, real_c = lstm_mod.get_mask, lstm_mod.get_choice, lstm_mod.get_c
+
+    def get_mask(pre_seq, tokenizer, position, max_layer):
+        m = real_mask(pre_seq, tokenizer, position, max_layer)
+        if cur['on']:
+            cur['seq'], cur['pos'], cur['mask'] = pre_seq[0].numpy().copy(), int(position[0]), m[0].numpy().copy()
+        return m
+
+    def get_choice(output, mask, fix_choice=None):
+        logits = output.detach().clone().reshape(-1).numpy().astype(np.float32) if cur['on'] else None
+        r = real_choice(output, mask, fix_choice)
+        if cur['on']:
+            tokens['seq'].append(cur['seq'].astype(np.int8)); tokens['pos'].append(cur['pos']); tokens['mask'].append(cur['mask'].astype(np.uint8))
+            tokens['logits'].append(logits); tokens['choice'].append(int(r[1][0])); tokens['cval'].append(np.float32(0)); tokens['tree'].append(len(trees['tok']))
+        return r
+
+    def get_c(output, min_c, interval, fix_c=None):
+        r = real_c(output, min_c, interval, fix_c)
+        if cur['on']:
+            tokens['cval'][-1] = np.float32(r[1][0])
+        return r
+    lstm_mod.get_mask, lstm_mod.get_choice, lstm_mod.get_c = get_mask, get_choice, get_c
+    from agent.symbol_agent import construct_action
+    from agent.symbol_related.tokenizer import MyTokenizer
+    tokenizer = MyTokenizer()
+
+    def policy(k):
+        def act(state, t):
+            st = torch.FloatTensor(state[None, :])
+            cur['on'] = True
+            first = len(tokens['pos'])
+            with torch.no_grad():
+                seq, cst, _ = agents[k].actor(st, save_data=False)
+            cur['on'] = False
+            trees['first'].append(first)
+            trees['state'].append(st[0].numpy().copy()); trees['ckpt'].append(k); trees['tok'].append(seq[0].astype(np.int8)); trees['cst'].append(cst[0].astype(np.float32))
+            trees['expr'].append(construct_action(seq, cst, tokenizer))
+            return seq[0], cst[0]
+        return act
+    hand = symbol_hand_trees()
+    names = list(hand)
+
+    def hand_cycle(order):
+        return lambda state, t: hand[order[t % len(order)]]
+    try:
+        data, cases = {}, []
+        jobs = [('bbob', 1, 2701, policy(20), None), ('bbob', 10, 2710, policy(20), None), ('bbob', 15, 2715, policy(0), None),
+                ('bbob', 16, 2716, hand_cycle(['de', 'three', 'full', 'chain', 'consts']), None), ('bbob', 1, 2731, hand_cycle(['full', 'de', 'consts', 'chain', 'three']), 12),
+                ('bbob-noisy', 101, 2801, policy(20), None), ('bbob-noisy', 102, 2802, hand_cycle(['de', 'consts', 'full']), None),
+                ('bbob-noisy', 103, 2803, policy(0), None)]
+        for suite, fid, seed, nxt, cap in jobs:
+            config = ref_import.ref_config(['--problem', suite, '--dim', '10'], scratch)
+            tr, te, _ = all_problems(suite, 10)
+            p = {fid_of(q): q for q in tr + te}[fid]
+            rec = run_symbol_episode(p, seed, config, nxt, full_actions=[0, 39] if fid == 103 else None, max_actions=cap)     # (Cauchy: three noise rows per evaluation)
+            key = f'{suite}/{fid}/{seed}'
+            cases.append(key)
+            for k, v in rec.items():
+                data[f'{key}/{k}'] = v
+            print(key, 'actions', len(rec['fes']), 'fes', rec['fes'][-1], 'curve', len(rec['curve']), 'gbest', rec['gbest'][-1], 'done', rec['done'][-1])
+        # ---- more trees from both checkpoints on recorded states, and the random baseline's trees
+        states = np.stack(trees['state'])
+        rs = np.random.RandomState(20261021)
+        torch.manual_seed(271)
+        for j in range(120):
+            policy((0, 20)[j % 2])(states[rs.randint(len(states))].astype(np.float64), 0)
+        n_policy_tokens = len(tokens['pos'])
+        # get_random_seq: masks of trees the trained policy may never reach (no logits: the scores are uniform noise)
+        torch.manual_seed(272)
+        rnd_tok = dict(seq=[], pos=[], mask=[])
+
+        def get_mask_rnd(pre_seq, tk, position, max_layer):
+            m = real_mask(pre_seq, tk, position, max_layer)
+            for r in range(pre_seq.shape[0]):
+                rnd_tok['seq'].append(pre_seq[r].numpy().astype(np.int8)); rnd_tok['pos'].append(int(position[r])); rnd_tok['mask'].append(m[r].numpy().astype(np.uint8))
+            return m
+        lstm_mod.get_mask = get_mask_rnd
+        rseq, rcst = agents[20].actor.get_random_seq(60)
+        lstm_mod.get_mask = get_mask
+        # ---- the reference's LSTM on one tree against all trees of a checkpoint at once (teacher-forced on the recorded choices)
+        e_base = 0.
+        first = trees['first'] + [n_policy_tokens]
+        for k, a in agents.items():
+            ids = [i for i in range(len(trees['tok'])) if trees['ckpt'][i] == k]
+            st = torch.FloatTensor(np.stack([trees['state'][i] for i in ids]))
+            L = max(first[i + 1] - first[i] for i in ids)
+            act = a.actor
+            with torch.no_grad():
+                h = torch.zeros(1, len(ids), 16); c = act.x_to_c(st)[None]
+                x_in = torch.zeros(len(ids), 1, 252)
+                for s in range(L):
+                    out, (h, c) = act.lstm(x_in, (h, c))
+                    lg = act.output_net(out)[:, 0].numpy()
+                    x_in = x_in.clone()
+                    for r, i in enumerate(ids):
+                        if first[i] + s < first[i + 1]:
+                            e_base = max(e_base, float(np.max(np.abs(lg[r] - tokens['logits'][first[i] + s]))))
+                            ch, ps = tokens['choice'][first[i] + s], tokens['pos'][first[i] + s]
+                            code = [int(b) for b in bin(ch + 1)[2:].zfill(4)]
+                            for q in range(4):
+                                x_in[r, 0, ps * 4 + q] = code[q]
+        print('trees', len(trees['tok']), 'tokens', n_policy_tokens, 'random-tree masks', len(rnd_tok['pos']), 'e_logit_base', e_base)
+        pol.update(tok_seq=np.stack(tokens['seq']), tok_pos=np.array(tokens['pos'], dtype=np.int8), tok_mask=np.stack(tokens['mask']), tok_logits=np.stack(tokens['logits']),
+                   tok_choice=np.array(tokens['choice'], dtype=np.int8), tok_cval=np.array(tokens['cval'], dtype=np.float32), tok_tree=np.array(tokens['tree'], dtype=np.int16),
+                   tree_first=np.array(trees['first'], dtype=np.int32), tree_state=np.stack(trees['state']), tree_ckpt=np.array(trees['ckpt'], dtype=np.int8),
+                   tree_tok=np.stack(trees['tok']), tree_cst=np.stack(trees['cst']), tree_expr=np.array(trees['expr']),
+                   rnd_seq=np.stack(rnd_tok['seq']), rnd_pos=np.array(rnd_tok['pos'], dtype=np.int8), rnd_mask=np.stack(rnd_tok['mask']),
+                   rnd_tree_tok=rseq.astype(np.int8), rnd_tree_cst=rcst.astype(np.float32),
+                   e_logit_base=np.float64(e_base), e_logit=np.float64(4 * e_base))
+        for name, (tok, c) in hand.items():
+            pol[f'hand/{name}/tok'] = tok.astype(np.int8); pol[f'hand/{name}/cst'] = c
+            pol[f'hand/{name}/expr'] = np.array(construct_action(tok[None, :], c[None, :], tokenizer))
+    finally:
+        lstm_mod.get_mask, lstm_mod.get_choice, lstm_mod.get_c = real_mask, real_choice, real_c
+    path = os.path.join(OUT, 'symbol_policy.npz')
+    np.savez_compressed(path, **pol)
+    print(os.path.basename(path), os.path.getsize(path))
+    data_cases = np.array(cases)
+    parts, sizes, owner = [], [], {}
+    for key in data:
+        prefix = '/'.join(key.split('/')[:3])
+        if prefix not in owner:
+            need = sum(data[k].nbytes for k in data if '/'.join(k.split('/')[:3]) == prefix)
+            for n in range(len(parts) + 1):
+                if n == len(parts):
+                    parts.append({}); sizes.append(0)
+                if sizes[n] + need <= 960 * 1024 or sizes[n] == 0:
+                    break
+            owner[prefix] = n
+            sizes[n] += need
+        parts[owner[prefix]][key] = data[key]
+    parts[0]['cases'] = data_cases
+    for n, d in enumerate(parts):
+        path = os.path.join(OUT, 'symbol_traces%s.npz' % ('' if n == 0 else '_' + 'abcdefghijklmnop'[n]))
+        np.savez_compressed(path, **d)
+        print(os.path.basename(path), os.path.getsize(path))
+        assert os.path.getsize(path) < 1000 * 1024
+
+
+SECTIONS = {'symbol': gen_symbol, 'l2l': gen_l2l, 'nlshade': gen_nlshade, 'rlhpsde': gen_rlhpsde, 'les': gen_les, 'sahlpso': gen_sahlpso, 'nrlpso': gen_nrlpso, 'sdmspso': gen_sdmspso, 'dedqn': gen_dedqn,'madde': gen_madde, 'jde21': gen_jde21, 'glpso': gen_glpso, 'train': gen_train, 'lde_hd': gen_lde_hd, 'rlepso_hd': gen_rlepso_hd, 'rlepso_ties': gen_rlepso_ties, 'qlpso': gen_qlpso, 'gleet_policy': gen_gleet_policy, 'gleet': gen_gleet, 'rlpso': gen_rlpso, 'mte': gen_mte, 'lde_stats': gen_lde_stats, 'stats': gen_stats, 'harness': gen_harness, 'ddqn': gen_ddqn, 'protein': gen_protein, 'lde': gen_lde, 'instances': gen_instances, 'kat': gen_kat, 'noise': gen_noise, 'policy': gen_policy,
             'rlepso': gen_rlepso}
 
 if __name__ == '__main__':

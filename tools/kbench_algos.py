@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Throughput of the other batched paths (BASELINE.json configs 3 and 4, one GPU's share), policy included.
-   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso|les|rlhpsde|nlshade|l2l] """
+   python tools/kbench_algos.py [lde|ddqn|rs|rlpso|gleet|qlpso|glpso|jde21|madde|dedqn|sdmspso|nrlpso|sahlpso|les|rlhpsde|nlshade|l2l|symbol] """
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -486,3 +486,47 @@ if 'l2l' in which:
             print(json.dumps({'path': f'{k}, bbob d={dim}, {B} instances', 'ms_per_episode_batch_median': float(np.median(v)), 'us_per_step_median': float(np.median(v)) * 10,
                               'windows_ms_per_episode_batch': [round(x, 3) for x in v], 'launch_info': br.launch_info()}))
         for b in (br, bg): b.close()
+if 'symbol' in which:
+    # SYMBOL (one action = 5 sub-steps under a per-instance expression tree): 4096 instances at D = 10, bbob round-robin, the trees of the shipped policy (checkpoint
+    # 20, generated once per window from the batch's own features).  Three figures per action: the resident route (5 sub-steps in ONE launch), the per-sub-step route
+    # (MBX_F_ROLLOUT_PER_GENERATION: same call, same outputs) and the host policy (LSTM + grammar mask + constants for 4096 trees).  Median of 5 windows of 8 actions per
+    # path after a warm-up window, each window ended by a device synchronise.
+    from metabox_amd._abi import ALGO_SYMBOL, F_ROLLOUT_PER_GENERATION
+    from metabox_amd.agent import Symbol_Agent
+    from metabox_amd.suite import Batch, Suite
+    dim, B = 10, 4096
+    cfg = get_config(['--problem', 'bbob', '--dim', str(dim)]); cfg.agent_save_dir = None
+    agent = Symbol_Agent(cfg).load_exported_weights(np.load(os.path.join(os.path.dirname(__file__), '..', 'tests', 'golden', 'symbol_policy.npz')), prefix='w20/')
+    tr, te = construct_problem_set(cfg); ps = sorted(tr.data + te.data, key=lambda p: p.func_id)
+    s = Suite(ps)
+    pidx, seeds = np.arange(B) % len(ps), np.arange(B, dtype=np.uint64) + 1
+    br = Batch(s, ALGO_SYMBOL, pidx, seeds, 100, 20000, 400, 50, early_stop=False)
+    bg = Batch(s, ALGO_SYMBOL, pidx, seeds, 100, 20000, 400, 50, early_stop=False, flags=F_ROLLOUT_PER_GENERATION)
+    torch.manual_seed(1)
+    feats = br.reset().cpu().numpy().astype(np.float32); bg.reset()
+    host = []
+    def trees():
+        t0 = time.perf_counter(); tk, cs = agent.act(feats); host.append((time.perf_counter() - t0) * 1e3)
+        return torch.from_numpy(tk).cuda(), torch.from_numpy(cs).cuda()
+    tk, cs = trees()
+    def sym(b):
+        def run(n):
+            for _ in range(n):
+                b.symbol_rollout(tk, cs, 5)
+        return run
+    paths = {'k_symbol_run resident, 5 sub-steps per launch': (sym(br), 8), 'k_symbol_step one launch per sub-step': (sym(bg), 8)}
+    times = {k: [] for k in paths}
+    for w in range(6):
+        if w == 1:                                                   # both batches restart side by side so that the windows that count see the same populations
+            br.reset(); bg.reset()
+        for k, (fn, n) in paths.items():
+            dt = timed(fn, n)
+            if w: times[k].append(dt / n * 1e3)
+        if w < 4: feats = br.state.cpu().numpy().astype(np.float32); tk, cs = trees()
+    assert torch.equal(br.state, bg.state) and torch.equal(br.results()['cost'], bg.results()['cost'])
+    for k, v in times.items():
+        print(json.dumps({'path': f'{k}, bbob d={dim}, {B} instances', 'ms_per_action_median': float(np.median(v)), 'windows_ms_per_action': [round(x, 3) for x in v],
+                          'launch_info': br.launch_info()}))
+    print(json.dumps({'path': f'Symbol_Agent.act on the host (LSTM, mask, constants), {B} trees', 'ms_per_action_median': float(np.median(host)),
+                      'calls_ms': [round(x, 1) for x in host], 'distinct_mask_prefixes': agent.mask_cache_size()}))
+    for b in (br, bg): b.close()
