@@ -1,5 +1,8 @@
-// mbx.hip — libmbx.so: kernels' launch code and the C-ABI of include/mbx.h.
-// Build: make -C metabox_amd/csrc  (fourteen translation units: this file, mbx_run_rlepso*.hip, mbx_run_lde.hip, mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip, mbx_run_l2l.hip, mbx_run_symbol.hip, mbx_run_rlhpsde.hip, mbx_run_nlshade.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
+// mbx.hip — libmbx.so: the C-ABI of include/mbx.h, and kernels with their launch code for the twelve algorithms compiled in this file.
+// Build: make -C metabox_amd/csrc  (fourteen translation units.  This file; mbx_run_rlepso.hip, mbx_run_rlepso_c5.hip, mbx_run_rlepso_fast.hip, mbx_run_rlepso_d40.hip
+// and mbx_run_lde.hip, which instantiate the resident kernels this file launches; and one unit per own-unit algorithm, kernels, host code and entry points, known
+// here by its row of kAlgoOps alone (mbx_host.hpp): mbx_run_dedqn.hip, mbx_run_nrlpso.hip, mbx_run_sahlpso.hip, mbx_run_les.hip, mbx_run_l2l.hip,
+// mbx_run_symbol.hip, mbx_run_rlhpsde.hip, mbx_run_nlshade.hip); one file: hipcc ... -DMBX_SINGLE_TU -shared mbx.hip -o libmbx.so
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -43,9 +46,11 @@
 #define MBX_RUN_KERNELS_EXTERN
 #endif
 #include "mbx_run_kernels.hpp"
+#include "mbx_host.hpp"
 #ifdef MBX_SINGLE_TU
-#include "mbx_run_dedqn.hip"           // the DEDQN kernels and their launch code, in this file as well
+#include "mbx_run_dedqn.hip"           // the DEDQN kernels, host code and row, in this file as well
 #include "mbx_run_nrlpso.hip"          // ... and the NRLPSO ones
+#include "mbx_run_sahlpso.hip"         // (its row is data: left out, the library would not load)
 #include "mbx_run_les.hip"
 #include "mbx_run_l2l.hip"
 #include "mbx_run_symbol.hip"
@@ -58,7 +63,7 @@ using namespace mbx;
 // ------------------------------------------------------------------------------------------------ errors
 static thread_local std::string g_err;
 
-static int fail(int code, const char* fmt, ...)
+int mbx::fail(int code, const char* fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -69,84 +74,7 @@ static int fail(int code, const char* fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                             \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) return fail(MBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
-// ------------------------------------------------------------------------------------------------ handles
-struct mbx_suite {
-    int n = 0, dim = 0;
-    double* d_pool = nullptr;
-    DevProblem* d_problems = nullptr;
-    std::vector<DevProblem> h_problems;       // device pointers inside
-    std::vector<double> optimum;
-};
-
-struct AlgoOps;
-
-struct mbx_batch {
-    mbx_suite* suite = nullptr;
-    mbx_algo_cfg cfg{};
-    const AlgoOps* ops = nullptr;          // the row of kAlgoOps for cfg.algo
-    int B = 0;
-    int32_t* d_problem_idx = nullptr;
-    std::vector<int32_t> h_problem_idx;    // host copy (mbx_debug_write_state validates an injected block against its problem's box)
-    uint64_t* d_seeds = nullptr;
-    double* d_state = nullptr;
-    int32_t* d_order = nullptr;
-    double* d_pci = nullptr;               // RLEPSO: learning-probability curve [np]; DEDQN: correctly rounded log(n / np), n = 0 .. np
-    unsigned long long* d_clk = nullptr;   // mbx_debug_clock_slots: the caller's slot block for the NEXT resident RLEPSO launches (not owned)
-    double* d_scratch = nullptr; // [B] per-generation rewards of mbx_rlepso_rollout's host-loop route (RLEPSO batches; allocated by mbx_batch_create)
-    float* d_lstm_pack = nullptr;          // k-blocked copy of the PolicyNet weights for k_lde_run (k_lde_repack at every mbx_lde_rollout call)
-    bool fdr_fast = false;                 // RLEPSO, MBX_F_FDR_FAST honoured: the kernels without the near-tie flag / second pass of the FDR scan (include/mbx.h); cfg.flags holds
-                                           // the EFFECTIVE flags (environment overrides OR-ed in, MBX_F_FDR_FAST cleared where no fast instantiation exists)
-    bool rl_run_kinds_ok = false;          // RLEPSO: every problem of the batch is one of the 24 BBOB kinds the per-kind k_rlepso_run geometries have a body for (rl_run_kind_ok)
-    bool lde_run_kinds_ok = false;         // LDE: every problem of the batch has an objective kind the LEAN instantiations of k_lde_run build (one tile array: lde_run_kind_ok(.., two = false))
-    bool lde_run_kinds_two = false;        // ... a kind the instantiations with the second tile array build (F1-F24)
-    bool nrlpso_cached = false;            // NRLPSO: the step kernels keep the NP x NP distance matrix in LDS (MBX_F_NRLPSO_RECOMPUTE clear and the matrix fits)
-    float* d_les_params = nullptr;         // LES: [les_n_sets][246] parameter sets and the set of every instance (mbx_les_set_params; copies)
-    int32_t* d_les_set = nullptr;
-    int les_n_sets = 0;
-    float* d_les_ts = nullptr;             // LES: [les_horizon + 1][13] float32 timestamp embedding tanh(t / timestamp - 1), one row per generation counter
-    int les_horizon = 0;
-    double* d_l2l_params = nullptr;        // L2L: [l2l_n_sets][MBX_L2L_NPARAM(dim)] weight sets and the set of every instance (mbx_l2l_set_params; copies)
-    int32_t* d_l2l_set = nullptr;
-    int l2l_n_sets = 0;
-    bool rollout_per_generation = false;   // MBX_F_ROLLOUT_PER_GENERATION: the mbx_*_rollout entry points take the host-loop route
-    int64_t state_stride = 0;
-    const double* d_tape = nullptr;
-    size_t lds_bytes = 0;
-    int64_t sc_off = 0;          // offset of the scalar block inside an instance's state
-    int64_t tape_stride = 0;
-    int state_dim = 0, action_dim = 0;
-    int threads = kThreads;      // workgroup size of the RLEPSO generation kernels (512 for LDS-bound geometries)
-    // compile-time-geometry instantiation of the generation / rollout kernels (0 = geometry read from the batch):
-    //   1 = RLEPSO NP 100 / D 10 / 5 groups (BASELINE configs 1-2)      2 = RLEPSO NP 128 / D 40 / 5 groups (config 5)      7 = RLEPSO NP 100 / D 30 (bbob --dim 30)
-    //   8 / 10 = RLEPSO NP 100 at D 12 (protein docking) / D 40 (bbob --dim 40): resident kernel only, mbx_step stays on the run-time-geometry kernel
-    //   3 / 6 = LDE NP 50 / NP 100 at D 30 (config 3)      9 = LDE NP 50 / D 10 (resident kernel only)      4 = DE-DDQN NP 100 / D 12 (config 4)      5 = GLEET NP 100 / D 10
-    int fixed_geometry = 0;
-};
-
-// per-algorithm geometry
-struct AlgoGeom { int64_t state_doubles, sc_off, tape_stride, lds_doubles; int state_dim, action_dim; };
-
-// Everything the host code knows about one algorithm id: the blocks and the table kAlgoOps further down
-struct AlgoOps {
-    int id; const char* name;
-    bool takes_actions;      // mbx_step refuses a null d_actions
-    bool needs_state_out;    // mbx_reset / mbx_step refuse a null d_state_out: the kernels write the features without asking
-    int (*check)(const mbx_algo_cfg&);                  // the algorithm's own limits; null = the common np in [4, kThreads]
-    AlgoGeom (*geom)(const mbx_algo_cfg&);
-    int (*prepare)(mbx_batch*, const AlgoGeom&);        // once per batch, at the end of mbx_batch_create
-    void (*reset)(mbx_batch*, hipStream_t, double* d_state_out);
-    int (*step)(mbx_batch*, hipStream_t, const void* d_actions, double* d_state_out, double* d_reward_out, uint8_t* d_done_out);
-    void (*launch_info)(const mbx_batch*, int32_t out[4]);   // where the step kernel's figures differ from the batch's; null = they do not
-};
-
 static const AlgoOps* ops_of(int algo);
-static int max_lds_bytes();
 static AlgoGeom geom_of(const mbx_algo_cfg& c) { return ops_of(c.algo)->geom(c); }      // c has passed check_cfg
 
 extern "C" int mbx_suite_destroy(mbx_suite* s);
@@ -224,7 +152,7 @@ __global__ void k_results(const double* state, int64_t stride, int64_t sc_off, i
 }
 
 // ------------------------------------------------------------------------------------------------ suite
-static int max_lds_bytes()
+int mbx::max_lds_bytes()
 {
     int v = 0, dev = 0;
     (void)hipGetDevice(&dev);
@@ -428,9 +356,6 @@ extern "C" int mbx_eval(mbx_suite* s, int problem, const double* d_x, int n, dou
 }
 
 // ------------------------------------------------------------------------------------------------ batch
-static int check_np(const mbx_algo_cfg& c) { return c.np < 4 || c.np > kThreads ? fail(MBX_E_ARG, "np %d outside [4, %d]", c.np, kThreads) : MBX_OK; }
-static int check_dim(const mbx_algo_cfg& c) { return c.dim < 2 || c.dim > 64 ? fail(MBX_E_ARG, "dim %d outside [2, 64]", c.dim) : MBX_OK; }
-
 // unknown id, then the algorithm's own limits, then the common ones: the order decides which message a doubly-wrong cfg gets
 static int check_cfg(const mbx_algo_cfg* c)
 {
@@ -485,14 +410,7 @@ static int upload_launch_order(mbx_batch* b, const int32_t* problem_idx)
         default: return 276;
         }
     };
-    b->lde_run_kinds_ok = true;
-    b->rl_run_kinds_ok = true;
-    for (int i = 0; i < n_instances; ++i) b->rl_run_kinds_ok = b->rl_run_kinds_ok && rl_run_kind_ok(s->h_problems[problem_idx[i]].kind, s->h_problems[problem_idx[i]].noise_kind);
-    b->lde_run_kinds_two = true;
-    for (int i = 0; i < n_instances; ++i) {
-        b->lde_run_kinds_ok = b->lde_run_kinds_ok && lde_run_kind_ok(s->h_problems[problem_idx[i]].kind, s->dim, false);
-        b->lde_run_kinds_two = b->lde_run_kinds_two && lde_run_kind_ok(s->h_problems[problem_idx[i]].kind, s->dim, true);
-    }
+    if (b->ops->bind) b->ops->bind(b);       // reads b->h_problem_idx, which both callers have set
     std::vector<int32_t> order(n_instances);
     for (int i = 0; i < n_instances; ++i) order[i] = i;
     // equal weights: by kind, so that neighbours in the launch order -- the workgroups that share a CU -- run the same per-kind body (k_rlepso_run, k_lde_run)
@@ -558,8 +476,29 @@ extern "C" int mbx_batch_create(mbx_suite* s, const mbx_algo_cfg* cfg_in, const 
 extern "C" int mbx_batch_destroy(mbx_batch* b)
 {
     if (!b) return MBX_OK;
-    (void)hipFree(b->d_problem_idx); (void)hipFree(b->d_seeds); (void)hipFree(b->d_state); (void)hipFree(b->d_order); (void)hipFree(b->d_pci); (void)hipFree(b->d_scratch); (void)hipFree(b->d_lstm_pack); (void)hipFree(b->d_les_params); (void)hipFree(b->d_les_set); (void)hipFree(b->d_les_ts); (void)hipFree(b->d_l2l_params); (void)hipFree(b->d_l2l_set);
+    (void)hipFree(b->d_problem_idx); (void)hipFree(b->d_seeds); (void)hipFree(b->d_state); (void)hipFree(b->d_order); (void)hipFree(b->d_pci); (void)hipFree(b->d_scratch); (void)hipFree(b->d_lstm_pack); (void)hipFree(b->sets.d_params); (void)hipFree(b->sets.d_set); (void)hipFree(b->d_les_ts);
     delete b;
+    return MBX_OK;
+}
+
+int mbx::set_param_sets(mbx_batch* b, const char* who, const void* d_params, size_t bytes_per_set, int n_sets, const int32_t* d_set_of_instance)
+{
+    HIP_TRY(hipDeviceSynchronize());
+    if (d_set_of_instance) {                                        // an index outside the table would be read out of bounds on the device
+        std::vector<int32_t> h(b->B);
+        HIP_TRY(hipMemcpy(h.data(), d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < b->B; ++i)
+            if (h[i] < 0 || h[i] >= n_sets) return fail(MBX_E_ARG, "%s: set_of_instance[%d] = %d outside [0, %d)", who, i, h[i], n_sets);
+    }
+    (void)hipFree(b->sets.d_params); (void)hipFree(b->sets.d_set);
+    b->sets = ParamSets{};
+    HIP_TRY(hipMalloc(&b->sets.d_params, (size_t)n_sets * bytes_per_set));
+    HIP_TRY(hipMemcpy(b->sets.d_params, d_params, (size_t)n_sets * bytes_per_set, hipMemcpyDeviceToDevice));
+    if (d_set_of_instance) {
+        HIP_TRY(hipMalloc(&b->sets.d_set, (size_t)b->B * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(b->sets.d_set, d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToDevice));
+    }
+    b->sets.n_sets = n_sets;
     return MBX_OK;
 }
 
@@ -594,41 +533,10 @@ extern "C" int mbx_set_tape(mbx_batch* b, const double* d_tape)
     return MBX_OK;
 }
 
-static BatchParams make_params(const mbx_batch* b)
-{
-    BatchParams p;
-    p.problems = b->suite->d_problems; p.problem_idx = b->d_problem_idx; p.seeds = b->d_seeds;
-    p.state = b->d_state; p.state_stride = b->state_stride;
-    p.tape = b->d_tape; p.tape_stride = b->tape_stride; p.order = b->d_order; p.pci = b->d_pci;
-    p.NP = b->cfg.np; p.D = b->cfg.dim; p.max_fes = b->cfg.max_fes; p.log_interval = b->cfg.log_interval;
-    p.n_logpoint = b->cfg.n_logpoint; p.early_stop = b->cfg.early_stop; p.n_group = b->cfg.n_group; p.B = b->B;
-    p.sc_off = b->sc_off;
-    p.clk = b->d_clk;
-    return p;
-}
-
 // ------------------------------------------------------------------------------------------------ algorithms
-// One block per algorithm id: its limits (check), geometry (geom), per-batch setup (prepare: workgroup size / compile-time geometry, tables, and the
-// kernels' dynamic-LDS limits), the reset launch and the one-step launch; then one row of kAlgoOps at the end of the section.  The entry points
-// above and below look the row up and call through.  Templates are instantiated in the order this file first names them: keep the lists' order.
-template <class... K>
-static int allow_lds(size_t lds, K... kernels)
-{
-    for (const void* k : {(const void*)kernels...}) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return MBX_OK;
-}
-
-static size_t lds_of(const AlgoGeom& g) { return (size_t)g.lds_doubles * sizeof(double); }
-static bool generic_geometry(const mbx_batch* b) { return (b->cfg.flags & MBX_F_GENERIC_GEOMETRY) != 0; }   // keeps the run-time-geometry kernels (the tests compare the two instantiations bit for bit)
-
-#define MBX_GEOM(P, lds, sdim, adim) \
-    AlgoGeom{MBX_##P##_STATE_DOUBLES(c.np, c.dim, c.n_logpoint), MBX_##P##_ST_SCALARS(c.np, c.dim), MBX_##P##_TAPE_STRIDE(c.np, c.dim), (lds), (sdim), (adim)}
-#define MBX_RESET_FN(name) static void name(mbx_batch* b, hipStream_t stream, double* d_state_out)
-#define MBX_STEP_FN(name) static int name(mbx_batch* b, hipStream_t stream, const void* d_actions, double* d_state_out, double* d_reward_out, uint8_t* d_done_out)
-#define MBX_OUT d_state_out, d_reward_out, d_done_out
-// one workgroup per instance; a template-id with commas goes in parentheses
-#define MBX_LAUNCH(kernel, threads, lds, ...) hipLaunchKernelGGL(kernel, dim3(b->B), dim3(threads), (lds), stream, make_params(b), __VA_ARGS__)
-
+// One block per algorithm compiled in this file (mbx_host.hpp says what a block holds and defines what it is written with), then the table kAlgoOps: these
+// blocks' rows and the rows the own-unit algorithms export.  The entry points above and below look the row up and call through.  Templates are instantiated in
+// the order this file first names them: keep the lists' order.
 // ---- RLEPSO
 static int rlepso_check(const mbx_algo_cfg& c)
 {
@@ -755,6 +663,17 @@ MBX_STEP_FN(lde_step)
 
 static void lde_launch_info(const mbx_batch* b, int32_t out[4]) { if (b->fixed_geometry == 3) out[0] = MBX_LDE50_STEP_THREADS; }   // k_lde_step's own workgroup size (k_lde_reset keeps b->threads)
 
+// which instantiations of k_lde_run build a body for every objective kind of the batch (mbx_lde_rollout_resident, mbx_lde_rollout)
+static void lde_bind(mbx_batch* b)
+{
+    b->lde_run_kinds_ok = b->lde_run_kinds_two = true;
+    for (const int32_t pi : b->h_problem_idx) {
+        const int kind = b->suite->h_problems[pi].kind;
+        b->lde_run_kinds_ok = b->lde_run_kinds_ok && lde_run_kind_ok(kind, b->suite->dim, false);
+        b->lde_run_kinds_two = b->lde_run_kinds_two && lde_run_kind_ok(kind, b->suite->dim, true);
+    }
+}
+
 // ---- DE-DDQN
 static AlgoGeom deddqn_geom(const mbx_algo_cfg& c) { return MBX_GEOM(DQ, dq_lds_doubles(c.np, c.np, c.dim), MBX_DQ_NFEAT, 1); }   // k_dq_reset's LDS; k_dq_step launches with the one-row layout
 static size_t deddqn_step_lds(const mbx_batch* b) { return (size_t)dq_lds_doubles(1, b->cfg.np, b->cfg.dim) * sizeof(double); }
@@ -836,202 +755,6 @@ static int sdmspso_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds
 MBX_RESET_FN(sdmspso_reset) { MBX_LAUNCH(k_sdmspso_reset, kThreads, b->lds_bytes, d_state_out); }
 MBX_STEP_FN(sdmspso_step) { MBX_LAUNCH(k_sdmspso_update, kThreads, b->lds_bytes, MBX_OUT); return MBX_OK; }
 
-// ---- DEDQN: kernels and launch code in mbx_run_dedqn.hip
-static int dedqn_check(const mbx_algo_cfg& c)
-{
-    // the landscape analysis deals one row per lane of two waves, and LDS holds the population three times over
-    if (c.np < 4 || c.np > MBX_DEDQN_NP_MAX) return fail(MBX_E_ARG, "DEDQN runs np in [4, %d], not %d", MBX_DEDQN_NP_MAX, c.np);
-    if (c.dim < 2 || c.dim > MBX_DEDQN_DIM_MAX) return fail(MBX_E_ARG, "DEDQN runs dim in [2, %d], not %d", MBX_DEDQN_DIM_MAX, c.dim);
-    return MBX_OK;
-}
-
-static AlgoGeom dedqn_geom(const mbx_algo_cfg& c) { return MBX_GEOM(DEDQN, dd_lds_doubles(c.np, c.dim), MBX_DEDQN_NFEAT, 1); }
-static int dedqn_prepare_batch(mbx_batch* b, const AlgoGeom& g)
-{
-    HIP_TRY(dedqn_prepare(lds_of(g)));
-    // cal_rie's frequencies are n / NP: their logarithms, correctly rounded (extended precision, then one rounding to double), so that the kernel's
-    // entropies do not depend on the device's log (mbx_dedqn.hpp: dd_features); the batch's table pointer `pci` carries them
-    std::vector<double> lt(b->cfg.np + 1, 0.);
-    for (int n = 1; n < b->cfg.np; ++n) lt[n] = (double)std::log((long double)((double)n / (double)b->cfg.np));
-    HIP_TRY(hipMalloc(&b->d_pci, lt.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(b->d_pci, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
-    return MBX_OK;
-}
-
-MBX_RESET_FN(dedqn_reset) { dedqn_launch_reset(make_params(b), b->lds_bytes, stream, d_state_out); }
-MBX_STEP_FN(dedqn_step) { dedqn_launch_step(make_params(b), b->lds_bytes, stream, (const int32_t*)d_actions, MBX_OUT); return MBX_OK; }
-
-// ---- NRLPSO: mbx_run_nrlpso.hip
-static int nrlpso_check(const mbx_algo_cfg& c)
-{
-    // one lane per row of the distance matrix (two waves), k = 5 neighbours out of np - 1, and LDS holds population and pbest positions
-    if (c.np < MBX_NRLPSO_NP_MIN || c.np > MBX_NRLPSO_NP_MAX) return fail(MBX_E_ARG, "NRLPSO runs np in [%d, %d], not %d", MBX_NRLPSO_NP_MIN, MBX_NRLPSO_NP_MAX, c.np);
-    if (c.dim < 2 || c.dim > MBX_NRLPSO_DIM_MAX) return fail(MBX_E_ARG, "NRLPSO runs dim in [2, %d], not %d", MBX_NRLPSO_DIM_MAX, c.dim);
-    return MBX_OK;
-}
-
-static AlgoGeom nrlpso_geom(const mbx_algo_cfg& c)
-{
-    // the larger of the reset's carve-up (NP evaluation rows) and the step's (one row, the resident arrays, the distance matrix where it is kept)
-    return MBX_GEOM(NRLPSO, std::max(nr_lds_doubles(c.np, c.np, c.dim, false, false),
-                                     nr_lds_doubles(1, c.np, c.dim, true, nrlpso_cached(c.np, c.dim, c.flags, (size_t)max_lds_bytes()))), 1, 1);
-}
-
-static int nrlpso_prepare_batch(mbx_batch* b, const AlgoGeom& g)
-{
-    b->nrlpso_cached = nrlpso_cached(b->cfg.np, b->cfg.dim, b->cfg.flags, (size_t)max_lds_bytes());
-    HIP_TRY(nrlpso_prepare(lds_of(g)));
-    return MBX_OK;
-}
-
-MBX_RESET_FN(nrlpso_reset) { nrlpso_launch_reset(make_params(b), stream, d_state_out); }
-MBX_STEP_FN(nrlpso_step) { nrlpso_launch_steps(make_params(b), b->nrlpso_cached, stream, (const int32_t*)d_actions, nullptr, 1, nullptr, nullptr, nullptr, nullptr, MBX_OUT); return MBX_OK; }
-
-// the step kernels' LDS (the reset's carve-up is smaller at np = 100)
-static void nrlpso_launch_info(const mbx_batch* b, int32_t out[4]) { out[1] = (int32_t)(nr_lds_doubles(1, b->cfg.np, b->cfg.dim, true, b->nrlpso_cached) * sizeof(double)); }
-
-// ---- SAHLPSO: mbx_run_sahlpso.hip
-static int sahlpso_check(const mbx_algo_cfg& c)
-{
-    // 40 particles shrinking to 4 (8 of them exploration particles), one lane per dimension in the move; the 40 initial evaluations are spent by mbx_reset
-    if (c.np != MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO runs np = %d (shrinking to 4), not %d", MBX_SAHL_NP, c.np);
-    if (c.dim < 2 || c.dim > MBX_SAHL_DIM_MAX) return fail(MBX_E_ARG, "SAHLPSO runs dim in [2, %d], not %d", MBX_SAHL_DIM_MAX, c.dim);
-    if (c.max_fes <= MBX_SAHL_NP) return fail(MBX_E_ARG, "SAHLPSO needs max_fes > %d (the initial evaluation), not %d", MBX_SAHL_NP, c.max_fes);
-    return MBX_OK;
-}
-
-static AlgoGeom sahlpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(SAHL, std::max(sh_lds_doubles(MBX_SAHL_NP, c.dim, false), sh_lds_doubles(1, c.dim, true)), 1, 0); }
-static int sahlpso_prepare_batch(mbx_batch*, const AlgoGeom& g) { HIP_TRY(sahlpso_prepare(lds_of(g))); return MBX_OK; }
-MBX_RESET_FN(sahlpso_reset) { sahlpso_launch_reset(make_params(b), stream, d_state_out); }
-MBX_STEP_FN(sahlpso_step) { sahlpso_launch_generation(make_params(b), stream, MBX_OUT); return MBX_OK; }
-
-// ---- LES: mbx_run_les.hip
-static int les_check(const mbx_algo_cfg& c)
-{
-    // 16 samples per generation, one lane of wave 0 per row and per dimension; the 16 initial evaluations are spent by mbx_reset
-    if (c.np != MBX_LES_NP) return fail(MBX_E_ARG, "LES runs np = %d, not %d", MBX_LES_NP, c.np);
-    if (c.dim < 2 || c.dim > MBX_LES_DIM_MAX) return fail(MBX_E_ARG, "LES runs dim in [2, %d], not %d", MBX_LES_DIM_MAX, c.dim);
-    if (c.max_fes <= MBX_LES_NP) return fail(MBX_E_ARG, "LES needs max_fes > %d (the initial evaluation), not %d", MBX_LES_NP, c.max_fes);
-    return MBX_OK;
-}
-
-static AlgoGeom les_geom(const mbx_algo_cfg& c)
-{
-    return AlgoGeom{MBX_LES_STATE_DOUBLES(c.np, c.dim, MBX_LES_CURVE_CAP(c.max_fes, c.log_interval, c.n_logpoint)), MBX_LES_ST_SCALARS(c.np, c.dim),
-                    MBX_LES_TAPE_STRIDE(c.np, c.dim), les_lds_doubles(c.dim), 1, 0};
-}
-
-static int les_prepare_batch(mbx_batch* b, const AlgoGeom& g)
-{
-    HIP_TRY(les_prepare(lds_of(g)));
-    // the timestamp embedding (les_optimizer.py:110): tanh(t / timestamp - 1) rounded to float32, as the reference's float64 numpy row is when it
-    // enters the MLP; made in extended precision and rounded once to double, then to float, so that it does not depend on the device's tanh
-    static const int stamps[MBX_LES_NTS] = {1, 3, 10, 30, 50, 100, 250, 500, 750, 1000, 1250, 1500, 2000};
-    b->les_horizon = b->cfg.max_fes / MBX_LES_NP + MBX_LES_TS_MARGIN;
-    std::vector<float> ts((size_t)(b->les_horizon + 1) * MBX_LES_NTS);
-    for (int t = 0; t <= b->les_horizon; ++t)
-        for (int k = 0; k < MBX_LES_NTS; ++k) ts[(size_t)t * MBX_LES_NTS + k] = (float)(double)std::tanh((long double)((double)t / (double)stamps[k] - 1.));
-    HIP_TRY(hipMalloc(&b->d_les_ts, ts.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(b->d_les_ts, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice));
-    return MBX_OK;
-}
-
-MBX_RESET_FN(les_reset) { les_launch_reset(make_params(b), stream, d_state_out); }
-MBX_STEP_FN(les_step) { (void)d_actions; return mbx_les_rollout(b, 1, 0, MBX_OUT, stream); }   // one generation of the budget route
-
-// ---- L2L: mbx_run_l2l.hip
-static int l2l_check(const mbx_algo_cfg& c)
-{
-    // one point per step: a single evaluation row; one lane of wave 0 per dimension
-    if (c.np != 1) return fail(MBX_E_ARG, "L2L runs np = 1 (one point per step), not %d", c.np);
-    if (c.dim < 2 || c.dim > MBX_L2L_DIM_MAX) return fail(MBX_E_ARG, "L2L runs dim in [2, %d], not %d", MBX_L2L_DIM_MAX, c.dim);
-    return MBX_OK;
-}
-
-static AlgoGeom l2l_geom(const mbx_algo_cfg& c) { return MBX_GEOM(L2L, l2l_lds_doubles(c.dim), 1, c.dim); }
-static int l2l_prepare_batch(mbx_batch*, const AlgoGeom& g) { HIP_TRY(l2l_prepare(lds_of(g))); return MBX_OK; }
-MBX_RESET_FN(l2l_reset) { l2l_launch_reset(make_params(b), stream, d_state_out); }
-MBX_STEP_FN(l2l_step) { l2l_launch_step(make_params(b), stream, (const double*)d_actions, MBX_OUT); return MBX_OK; }   // the host ran the cell: actions = x_raw
-
-// ---- SYMBOL: mbx_run_symbol.hip
-static int symbol_check(const mbx_algo_cfg& c)
-{
-    // the index rows are bytes and one lane owns a row in the bookkeeping; the rule's operand gathers and the evaluator share two position buffers.
-    // dim >= 2 is the library's common lower bound (check_dim: the evaluator's 2-wide tiles and FastDiv are built for D >= 2), stated here so that SYMBOL's own message names it
-    // (a geometry outside these limits is a valid request this build does not implement, like a protein batch: MBX_E_UNSUPPORTED, the code every SYMBOL refusal carries)
-    if (c.np < 4 || c.np > MBX_SYM_NP_MAX) return fail(MBX_E_UNSUPPORTED, "SYMBOL runs np in [4, %d], not %d", MBX_SYM_NP_MAX, c.np);
-    if (c.dim < 2 || c.dim > MBX_SYM_DIM_MAX) return fail(MBX_E_UNSUPPORTED, "SYMBOL runs dim in [2, %d], not %d", MBX_SYM_DIM_MAX, c.dim);
-    return MBX_OK;
-}
-
-static AlgoGeom symbol_geom(const mbx_algo_cfg& c) { return MBX_GEOM(SYMBOL, sym_lds_doubles(c.np, c.dim, sym_resident(c.np, c.dim)), MBX_SYM_NFEAT, 2 * MBX_SYM_SLOTS); }
-static int symbol_prepare_batch(mbx_batch* b, const AlgoGeom& g)
-{
-    for (int i = 0; i < b->B; ++i)
-        if (b->suite->h_problems[b->h_problem_idx[i]].kind == MBX_KIND_PROTEIN) return fail(MBX_E_UNSUPPORTED, "SYMBOL: protein docking problems are not supported");
-    HIP_TRY(symbol_prepare(lds_of(g)));
-    return MBX_OK;
-}
-MBX_RESET_FN(symbol_reset) { symbol_launch_reset(make_params(b), stream, d_state_out); }
-MBX_STEP_FN(symbol_step)      // the program as actions: MBX_SYM_SKIP sub-steps
-{
-    const BatchParams bp = make_params(b);
-    if (b->rollout_per_generation)
-        for (int g = 0; g < MBX_SYM_SKIP; ++g) symbol_launch_run(bp, stream, nullptr, nullptr, (const double*)d_actions, 1, MBX_SYM_SKIP, MBX_OUT, nullptr);
-    else symbol_launch_run(bp, stream, nullptr, nullptr, (const double*)d_actions, MBX_SYM_SKIP, MBX_SYM_SKIP, MBX_OUT, nullptr);
-    return MBX_OK;
-}
-
-// ---- RL-HPSDE: mbx_run_rlhpsde.hip
-static int rlhpsde_check(const mbx_algo_cfg& c)
-{
-    // 18 dim rows shrinking towards 4, a thread owns a block of rows; the initial evaluation and the first walk (201 points) are spent by mbx_reset
-    if (c.dim < 2 || c.dim > MBX_RLHPSDE_DIM_MAX) return fail(MBX_E_ARG, "RL-HPSDE runs dim in [2, %d], not %d", MBX_RLHPSDE_DIM_MAX, c.dim);
-    if (c.np != MBX_RLHPSDE_NP(c.dim)) return fail(MBX_E_ARG, "RL-HPSDE runs np = 18 dim = %d, not %d", MBX_RLHPSDE_NP(c.dim), c.np);
-    if (c.max_fes <= c.np + MBX_RLHPSDE_WALK)
-        return fail(MBX_E_ARG, "RL-HPSDE needs max_fes > %d (the initial evaluation and the first walk), not %d", c.np + MBX_RLHPSDE_WALK, c.max_fes);
-    return MBX_OK;
-}
-
-static AlgoGeom rlhpsde_geom(const mbx_algo_cfg& c) { return MBX_GEOM(RLHPSDE, hp_lds_doubles(c.np, c.dim), 1, 1); }
-static int rlhpsde_prepare_batch(mbx_batch* b, const AlgoGeom& g)
-{
-    HIP_TRY(rlhpsde_prepare(lds_of(g)));
-    // DRIE's frequencies are n / 200 (and 1e-15 for an empty class): their logarithms, correctly rounded (extended precision, then one rounding to double), so that
-    // the kernel's entropies do not depend on the device's log (mbx_rlhpsde.hpp: hp_walk_state); the batch's table pointer `pci` carries them
-    std::vector<double> lt(MBX_RLHPSDE_WALK, 0.);
-    lt[0] = (double)std::log((long double)1e-15);
-    for (int n = 1; n < MBX_RLHPSDE_WALK - 1; ++n) lt[n] = (double)std::log((long double)((double)n / (double)(MBX_RLHPSDE_WALK - 1)));
-    HIP_TRY(hipMalloc(&b->d_pci, lt.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(b->d_pci, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
-    return MBX_OK;
-}
-
-MBX_RESET_FN(rlhpsde_reset) { rlhpsde_launch_reset(make_params(b), b->lds_bytes, stream, d_state_out); }
-MBX_STEP_FN(rlhpsde_step) { rlhpsde_launch_step(make_params(b), b->lds_bytes, stream, (const int32_t*)d_actions, MBX_OUT); return MBX_OK; }
-
-// ---- NL_SHADE_LBC: mbx_run_nlshade.hip
-static int nlshade_check(const mbx_algo_cfg& c)
-{
-    if (c.dim < 2 || c.dim > MBX_NLSHADE_DIM_MAX) return fail(MBX_E_ARG, "NL_SHADE_LBC runs dim in [2, %d], not %d", MBX_NLSHADE_DIM_MAX, c.dim);
-    if (c.np != MBX_NLSHADE_NP(c.dim)) return fail(MBX_E_ARG, "NL_SHADE_LBC runs np = 23 dim = %d, not %d", MBX_NLSHADE_NP(c.dim), c.np);
-    if (c.max_fes <= c.np) return fail(MBX_E_ARG, "NL_SHADE_LBC needs max_fes > %d (the initial evaluation), not %d", c.np, c.max_fes);
-    return MBX_OK;
-}
-
-static AlgoGeom nlshade_geom(const mbx_algo_cfg& c) { return MBX_GEOM(NLSHADE, nl_lds_doubles(c.np, c.dim), 1, 0); }
-static int nlshade_prepare_batch(mbx_batch* b, const AlgoGeom& g)
-{
-    HIP_TRY(nlshade_prepare(lds_of(g)));
-    // the population schedule is a function of (dim, max_fes) alone (mbx_nlshade.hpp, quirk 11); the batch's table pointer `pci` carries it
-    const std::vector<double> t = nlshade_schedule(b->cfg.np, b->cfg.max_fes);
-    HIP_TRY(hipMalloc(&b->d_pci, t.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(b->d_pci, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
-    return MBX_OK;
-}
-MBX_RESET_FN(nlshade_reset) { nlshade_launch_reset(make_params(b), b->lds_bytes, stream, d_state_out); }
-MBX_STEP_FN(nlshade_step) { nlshade_launch_step(make_params(b), b->lds_bytes, stream, MBX_OUT); return MBX_OK; }
-
 // ---- QLPSO
 static AlgoGeom qlpso_geom(const mbx_algo_cfg& c) { return MBX_GEOM(QLPSO, ql_lds_doubles(c.np, c.np, c.dim), 1, 1); }
 static int qlpso_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g), k_qlpso_reset, k_qlpso_step<false>, k_qlpso_step<true>); }
@@ -1068,42 +791,32 @@ static int rs_prepare(mbx_batch*, const AlgoGeom& g) { return allow_lds(lds_of(g
 MBX_RESET_FN(rs_reset) { MBX_LAUNCH(k_rs_population, kThreads, b->lds_bytes, 1, d_state_out, (double*)nullptr, (uint8_t*)nullptr); }
 MBX_STEP_FN(rs_step) { MBX_LAUNCH(k_rs_population, kThreads, b->lds_bytes, 0, MBX_OUT); return MBX_OK; }
 
-#undef MBX_GEOM
-#undef MBX_RESET_FN
-#undef MBX_STEP_FN
-#undef MBX_OUT
-#undef MBX_LAUNCH
+// id, name, takes_actions, needs_state_out, check, geom, prepare, reset, step, launch_info, bind.  A new algorithm in this file: its block above, its row here.
+static const AlgoOps kRlepsoOps = {MBX_ALGO_RLEPSO, "RLEPSO", true, false, rlepso_check, rlepso_geom, rlepso_prepare, rlepso_reset, rlepso_step, nullptr};
+static const AlgoOps kLdeOps = {MBX_ALGO_LDE, "LDE", true, true, nullptr, lde_geom, lde_prepare, lde_reset, lde_step, lde_launch_info, lde_bind};
+static const AlgoOps kDeddqnOps = {MBX_ALGO_DEDDQN, "DE-DDQN", true, true, nullptr, deddqn_geom, deddqn_prepare, deddqn_reset, deddqn_step, deddqn_launch_info};
+static const AlgoOps kRsOps = {MBX_ALGO_RANDOM_SEARCH, "Random_search", false, false, nullptr, rs_geom, rs_prepare, rs_reset, rs_step, nullptr};
+static const AlgoOps kRlpsoOps = {MBX_ALGO_RLPSO, "RL-PSO", true, false, nullptr, rlpso_geom, rlpso_prepare, rlpso_reset, rlpso_step, nullptr};
+static const AlgoOps kGleetOps = {MBX_ALGO_GLEET, "GLEET", true, false, nullptr, gleet_geom, gleet_prepare, gleet_reset, gleet_step, nullptr};
+static const AlgoOps kQlpsoOps = {MBX_ALGO_QLPSO, "QLPSO", true, false, nullptr, qlpso_geom, qlpso_prepare, qlpso_reset, qlpso_step, nullptr};
+static const AlgoOps kDeOps = {MBX_ALGO_DE, "DE", false, false, nullptr, de_geom, classic_prepare, classic_reset, de_step, nullptr};
+static const AlgoOps kPsoOps = {MBX_ALGO_PSO, "PSO", false, false, nullptr, pso_geom, classic_prepare, classic_reset, pso_step, nullptr};
+static const AlgoOps kCmaesOps = {MBX_ALGO_CMAES, "CMA-ES", false, false, nullptr, cmaes_geom, classic_prepare, classic_reset, cmaes_step, nullptr};
+static const AlgoOps kGlpsoOps = {MBX_ALGO_GLPSO, "GL-PSO", false, false, nullptr, glpso_geom, glpso_prepare, glpso_reset, glpso_step, nullptr};
+static const AlgoOps kJde21Ops = {MBX_ALGO_JDE21, "JDE21", false, false, jde21_check, jde21_geom, jde21_prepare, jde21_reset, jde21_step, nullptr};
+static const AlgoOps kMaddeOps = {MBX_ALGO_MADDE, "MadDE", false, false, madde_check, madde_geom, madde_prepare, madde_reset, madde_step, nullptr};
+static const AlgoOps kSdmspsoOps = {MBX_ALGO_SDMSPSO, "sDMS_PSO", false, false, sdmspso_check, sdmspso_geom, sdmspso_prepare, sdmspso_reset, sdmspso_step, nullptr};
 
-// id, name, takes_actions, needs_state_out, check, geom, prepare, reset, step, launch_info.  A new algorithm: its block above, its row here.
-static const AlgoOps kAlgoOps[] = {
-    {MBX_ALGO_RLEPSO, "RLEPSO", true, false, rlepso_check, rlepso_geom, rlepso_prepare, rlepso_reset, rlepso_step, nullptr},
-    {MBX_ALGO_LDE, "LDE", true, true, nullptr, lde_geom, lde_prepare, lde_reset, lde_step, lde_launch_info},
-    {MBX_ALGO_DEDDQN, "DE-DDQN", true, true, nullptr, deddqn_geom, deddqn_prepare, deddqn_reset, deddqn_step, deddqn_launch_info},
-    {MBX_ALGO_RANDOM_SEARCH, "Random_search", false, false, nullptr, rs_geom, rs_prepare, rs_reset, rs_step, nullptr},
-    {MBX_ALGO_RLPSO, "RL-PSO", true, false, nullptr, rlpso_geom, rlpso_prepare, rlpso_reset, rlpso_step, nullptr},
-    {MBX_ALGO_GLEET, "GLEET", true, false, nullptr, gleet_geom, gleet_prepare, gleet_reset, gleet_step, nullptr},
-    {MBX_ALGO_QLPSO, "QLPSO", true, false, nullptr, qlpso_geom, qlpso_prepare, qlpso_reset, qlpso_step, nullptr},
-    {MBX_ALGO_DE, "DE", false, false, nullptr, de_geom, classic_prepare, classic_reset, de_step, nullptr},
-    {MBX_ALGO_PSO, "PSO", false, false, nullptr, pso_geom, classic_prepare, classic_reset, pso_step, nullptr},
-    {MBX_ALGO_CMAES, "CMA-ES", false, false, nullptr, cmaes_geom, classic_prepare, classic_reset, cmaes_step, nullptr},
-    {MBX_ALGO_GLPSO, "GL-PSO", false, false, nullptr, glpso_geom, glpso_prepare, glpso_reset, glpso_step, nullptr},
-    {MBX_ALGO_JDE21, "JDE21", false, false, jde21_check, jde21_geom, jde21_prepare, jde21_reset, jde21_step, nullptr},
-    {MBX_ALGO_MADDE, "MadDE", false, false, madde_check, madde_geom, madde_prepare, madde_reset, madde_step, nullptr},
-    {MBX_ALGO_DEDQN, "DEDQN", true, false, dedqn_check, dedqn_geom, dedqn_prepare_batch, dedqn_reset, dedqn_step, nullptr},
-    {MBX_ALGO_SDMSPSO, "sDMS_PSO", false, false, sdmspso_check, sdmspso_geom, sdmspso_prepare, sdmspso_reset, sdmspso_step, nullptr},
-    {MBX_ALGO_NRLPSO, "NRLPSO", true, false, nrlpso_check, nrlpso_geom, nrlpso_prepare_batch, nrlpso_reset, nrlpso_step, nrlpso_launch_info},
-    {MBX_ALGO_SAHLPSO, "SAHLPSO", false, false, sahlpso_check, sahlpso_geom, sahlpso_prepare_batch, sahlpso_reset, sahlpso_step, nullptr},
-    {MBX_ALGO_LES, "LES", false, false, les_check, les_geom, les_prepare_batch, les_reset, les_step, nullptr},
-    {MBX_ALGO_L2L, "L2L", true, false, l2l_check, l2l_geom, l2l_prepare_batch, l2l_reset, l2l_step, nullptr},
-    {MBX_ALGO_SYMBOL, "SYMBOL", true, false, symbol_check, symbol_geom, symbol_prepare_batch, symbol_reset, symbol_step, nullptr},
-    {MBX_ALGO_RLHPSDE, "RL-HPSDE", true, false, rlhpsde_check, rlhpsde_geom, rlhpsde_prepare_batch, rlhpsde_reset, rlhpsde_step, nullptr},
-    {MBX_ALGO_NLSHADE, "NL_SHADE_LBC", false, false, nlshade_check, nlshade_geom, nlshade_prepare_batch, nlshade_reset, nlshade_step, nullptr},
+// An own-unit algorithm is one mbx_run_*.hip exporting one row (declared in mbx_host.hpp): its entry here, its object in the Makefile, nothing else in this file.
+static const AlgoOps* const kAlgoOps[] = {
+    &kRlepsoOps, &kLdeOps, &kDeddqnOps, &kRsOps, &kRlpsoOps, &kGleetOps, &kQlpsoOps, &kDeOps, &kPsoOps, &kCmaesOps, &kGlpsoOps, &kJde21Ops, &kMaddeOps,
+    &kDedqnOps, &kSdmspsoOps, &kNrlpsoOps, &kSahlpsoOps, &kLesOps, &kL2lOps, &kSymbolOps, &kRlhpsdeOps, &kNlshadeOps,
 };
 
 static const AlgoOps* ops_of(int algo)      // null for the ids that are not assigned (0, 12, 14, 17, 22, 23) and anything out of range
 {
-    for (const AlgoOps& o : kAlgoOps)
-        if (o.id == algo) return &o;
+    for (const AlgoOps* o : kAlgoOps)
+        if (o->id == algo) return o;
     return nullptr;
 }
 
@@ -1416,160 +1129,6 @@ extern "C" int mbx_gleet_policy(mbx_batch* b, const mbx_gleet_actor* net, const 
     const GleetActor g{net->d_weights, net->min_sigma, net->max_sigma};
     hipLaunchKernelGGL(k_gleet_policy, dim3(b->B), dim3(kGpThreads), gleet_policy_lds_bytes(b->cfg.np), (hipStream_t)stream, make_params(b),
                        g, d_state, d_actions, d_mu_sigma);
-    HIP_TRY(hipGetLastError());
-    return MBX_OK;
-}
-
-extern "C" int mbx_dedqn_rollout(mbx_batch* b, const mbx_dedqn_net* net, int n_steps, int32_t* d_traj_actions, double* d_traj_state,
-                                 double* d_traj_reward, int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out,
-                                 void* stream)
-{
-    if (!b || !net || !net->d_weights) return fail(MBX_E_ARG, "mbx_dedqn_rollout: bad arguments");
-    if (b->cfg.algo != MBX_ALGO_DEDQN) return fail(MBX_E_UNSUPPORTED, "mbx_dedqn_rollout: the batch is not a DEDQN batch");
-    if (net->in_dim != MBX_DEDQN_NFEAT || net->hidden != 10 || net->n_act != 3)
-        return fail(MBX_E_UNSUPPORTED, "mbx_dedqn_rollout: only the reference's 4 -> 10 -> 10 -> 3 network is built");
-    if (n_steps < 1) return fail(MBX_E_ARG, "mbx_dedqn_rollout: n_steps must be >= 1");
-    if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_dedqn_rollout: a replay tape holds one step");
-    dedqn_launch_run(make_params(b), b->lds_bytes, (hipStream_t)stream, net->d_weights, n_steps, d_traj_actions, d_traj_state, d_traj_reward,
-                     d_actions_out, d_state_out, d_reward_out, d_done_out);
-    HIP_TRY(hipGetLastError());
-    return MBX_OK;
-}
-
-extern "C" int mbx_nrlpso_rollout(mbx_batch* b, const double* d_q_table, int n_steps, int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward,
-                                  int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
-{
-    if (!b || !d_q_table) return fail(MBX_E_ARG, "mbx_nrlpso_rollout: bad arguments");
-    if (b->cfg.algo != MBX_ALGO_NRLPSO) return fail(MBX_E_UNSUPPORTED, "mbx_nrlpso_rollout: the batch is not an NRLPSO batch");
-    if (n_steps < 1) return fail(MBX_E_ARG, "mbx_nrlpso_rollout: n_steps must be >= 1");
-    if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_nrlpso_rollout: a replay tape holds one step");
-    nrlpso_launch_steps(make_params(b), b->nrlpso_cached, (hipStream_t)stream, nullptr, d_q_table, n_steps, d_traj_actions, d_traj_state, d_traj_reward,
-                        d_actions_out, d_state_out, d_reward_out, d_done_out);
-    HIP_TRY(hipGetLastError());
-    return MBX_OK;
-}
-
-extern "C" int mbx_rlhpsde_rollout(mbx_batch* b, const double* d_q_table, int n_steps, int32_t* d_traj_actions, double* d_traj_state, double* d_traj_reward,
-                                   int32_t* d_actions_out, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
-{
-    if (!b) return fail(MBX_E_ARG, "mbx_rlhpsde_rollout: null batch");
-    if (b->cfg.algo != MBX_ALGO_RLHPSDE) return fail(MBX_E_UNSUPPORTED, "mbx_rlhpsde_rollout: the batch is not an RL-HPSDE batch");
-    if (!d_q_table) return fail(MBX_E_ARG, "mbx_rlhpsde_rollout: no Q-table (d_q_table is NULL)");
-    if (n_steps < 1) return fail(MBX_E_ARG, "mbx_rlhpsde_rollout: n_steps must be >= 1");
-    if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_rlhpsde_rollout: a replay tape holds one step");
-    rlhpsde_launch_run(make_params(b), b->lds_bytes, (hipStream_t)stream, d_q_table, n_steps, d_traj_actions, d_traj_state, d_traj_reward, d_actions_out,
-                       d_state_out, d_reward_out, d_done_out);
-    HIP_TRY(hipGetLastError());
-    return MBX_OK;
-}
-
-extern "C" int mbx_nlshade_run(mbx_batch* b, int n_updates, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
-{
-    if (!b) return fail(MBX_E_ARG, "mbx_nlshade_run: null batch");
-    if (b->cfg.algo != MBX_ALGO_NLSHADE) return fail(MBX_E_UNSUPPORTED, "mbx_nlshade_run: the batch is not an NL_SHADE_LBC batch");
-    if (n_updates < 1) return fail(MBX_E_ARG, "mbx_nlshade_run: n_updates must be >= 1");
-    if (b->d_tape && n_updates != 1) return fail(MBX_E_ARG, "mbx_nlshade_run: a replay tape holds one update");
-    nlshade_launch_run(make_params(b), b->lds_bytes, (hipStream_t)stream, n_updates, d_state_out, d_reward_out, d_done_out);
-    HIP_TRY(hipGetLastError());
-    return MBX_OK;
-}
-
-extern "C" int mbx_les_set_params(mbx_batch* b, const float* d_params, int n_sets, const int32_t* d_set_of_instance)
-{
-    if (!b || !d_params || n_sets < 1) return fail(MBX_E_ARG, "mbx_les_set_params: bad arguments");
-    if (b->cfg.algo != MBX_ALGO_LES) return fail(MBX_E_UNSUPPORTED, "mbx_les_set_params: the batch is not an LES batch");
-    HIP_TRY(hipDeviceSynchronize());
-    if (d_set_of_instance) {                                        // an index outside the table would be read out of bounds on the device
-        std::vector<int32_t> h(b->B);
-        HIP_TRY(hipMemcpy(h.data(), d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int i = 0; i < b->B; ++i)
-            if (h[i] < 0 || h[i] >= n_sets) return fail(MBX_E_ARG, "mbx_les_set_params: set_of_instance[%d] = %d outside [0, %d)", i, h[i], n_sets);
-    }
-    (void)hipFree(b->d_les_params); (void)hipFree(b->d_les_set);
-    b->d_les_params = nullptr; b->d_les_set = nullptr; b->les_n_sets = 0;
-    HIP_TRY(hipMalloc(&b->d_les_params, (size_t)n_sets * MBX_LES_NPARAM * sizeof(float)));
-    HIP_TRY(hipMemcpy(b->d_les_params, d_params, (size_t)n_sets * MBX_LES_NPARAM * sizeof(float), hipMemcpyDeviceToDevice));
-    if (d_set_of_instance) {
-        HIP_TRY(hipMalloc(&b->d_les_set, (size_t)b->B * sizeof(int32_t)));
-        HIP_TRY(hipMemcpy(b->d_les_set, d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToDevice));
-    }
-    b->les_n_sets = n_sets;
-    return MBX_OK;
-}
-
-extern "C" int mbx_les_rollout(mbx_batch* b, int n_gens, int skip, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
-{
-    if (!b) return fail(MBX_E_ARG, "mbx_les_rollout: null batch");
-    if (b->cfg.algo != MBX_ALGO_LES) return fail(MBX_E_UNSUPPORTED, "mbx_les_rollout: the batch is not an LES batch");
-    if (!b->d_les_params) return fail(MBX_E_ARG, "LES: no parameters yet, call mbx_les_set_params first");
-    if (n_gens < 1 || (skip != 0 && skip != 1)) return fail(MBX_E_ARG, "mbx_les_rollout: n_gens must be >= 1 and skip 0 or 1");
-    if (b->d_tape && n_gens != 1) return fail(MBX_E_ARG, "mbx_les_rollout: a replay tape holds one generation");
-    const BatchParams bp = make_params(b);
-    if (b->rollout_per_generation)
-        for (int g = 0; g < n_gens; ++g)
-            les_launch_run(bp, (hipStream_t)stream, b->d_les_params, b->d_les_set, b->les_n_sets, b->d_les_ts, b->les_horizon, 1, skip, g, n_gens, d_state_out,
-                           d_reward_out, d_done_out);
-    else
-        les_launch_run(bp, (hipStream_t)stream, b->d_les_params, b->d_les_set, b->les_n_sets, b->d_les_ts, b->les_horizon, n_gens, skip, 0, n_gens, d_state_out,
-                       d_reward_out, d_done_out);
-    HIP_TRY(hipGetLastError());
-    return MBX_OK;
-}
-
-extern "C" int mbx_l2l_set_params(mbx_batch* b, const double* d_params, int n_sets, const int32_t* d_set_of_instance)
-{
-    if (!b || !d_params || n_sets < 1) return fail(MBX_E_ARG, "mbx_l2l_set_params: bad arguments");
-    if (b->cfg.algo != MBX_ALGO_L2L) return fail(MBX_E_UNSUPPORTED, "mbx_l2l_set_params: the batch is not an L2L batch");
-    HIP_TRY(hipDeviceSynchronize());
-    if (d_set_of_instance) {                                        // an index outside the table would be read out of bounds on the device
-        std::vector<int32_t> h(b->B);
-        HIP_TRY(hipMemcpy(h.data(), d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int i = 0; i < b->B; ++i)
-            if (h[i] < 0 || h[i] >= n_sets) return fail(MBX_E_ARG, "mbx_l2l_set_params: set_of_instance[%d] = %d outside [0, %d)", i, h[i], n_sets);
-    }
-    (void)hipFree(b->d_l2l_params); (void)hipFree(b->d_l2l_set);
-    b->d_l2l_params = nullptr; b->d_l2l_set = nullptr; b->l2l_n_sets = 0;
-    const size_t bytes = (size_t)n_sets * (size_t)MBX_L2L_NPARAM(b->cfg.dim) * sizeof(double);
-    HIP_TRY(hipMalloc(&b->d_l2l_params, bytes));
-    HIP_TRY(hipMemcpy(b->d_l2l_params, d_params, bytes, hipMemcpyDeviceToDevice));
-    if (d_set_of_instance) {
-        HIP_TRY(hipMalloc(&b->d_l2l_set, (size_t)b->B * sizeof(int32_t)));
-        HIP_TRY(hipMemcpy(b->d_l2l_set, d_set_of_instance, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToDevice));
-    }
-    b->l2l_n_sets = n_sets;
-    return MBX_OK;
-}
-
-extern "C" int mbx_l2l_rollout(mbx_batch* b, int n_steps, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream)
-{
-    if (!b) return fail(MBX_E_ARG, "mbx_l2l_rollout: null batch");
-    if (b->cfg.algo != MBX_ALGO_L2L) return fail(MBX_E_UNSUPPORTED, "mbx_l2l_rollout: the batch is not an L2L batch");
-    if (!b->d_l2l_params) return fail(MBX_E_ARG, "L2L: no weights yet, call mbx_l2l_set_params first");
-    if (n_steps < 1) return fail(MBX_E_ARG, "mbx_l2l_rollout: n_steps must be >= 1");
-    if (b->d_tape && n_steps != 1) return fail(MBX_E_ARG, "mbx_l2l_rollout: a replay tape holds one step");
-    const BatchParams bp = make_params(b);
-    const bool generic = generic_geometry(b);
-    if (b->rollout_per_generation)
-        for (int g = 0; g < n_steps; ++g)
-            l2l_launch_run(bp, generic, (hipStream_t)stream, b->d_l2l_params, b->d_l2l_set, b->l2l_n_sets, 1, d_state_out, d_reward_out, d_done_out);
-    else
-        l2l_launch_run(bp, generic, (hipStream_t)stream, b->d_l2l_params, b->d_l2l_set, b->l2l_n_sets, n_steps, d_state_out, d_reward_out, d_done_out);
-    HIP_TRY(hipGetLastError());
-    return MBX_OK;
-}
-
-extern "C" int mbx_symbol_rollout(mbx_batch* b, const int32_t* d_tokens, const double* d_consts, int n_substeps, double* d_state_out, double* d_reward_out,
-                                  uint8_t* d_done_out, int32_t* d_n_bad, void* stream)
-{
-    if (!b || !d_tokens || !d_consts) return fail(MBX_E_ARG, "mbx_symbol_rollout: bad arguments");
-    if (b->cfg.algo != MBX_ALGO_SYMBOL) return fail(MBX_E_UNSUPPORTED, "mbx_symbol_rollout: the batch is not a SYMBOL batch");
-    if (n_substeps < 1 || n_substeps > MBX_SYM_SUB_MAX) return fail(MBX_E_ARG, "mbx_symbol_rollout: n_substeps must be in [1, %d]", MBX_SYM_SUB_MAX);
-    const BatchParams bp = make_params(b);
-    if (b->rollout_per_generation)
-        for (int g = 0; g < n_substeps; ++g)
-            symbol_launch_run(bp, (hipStream_t)stream, d_tokens, d_consts, nullptr, 1, n_substeps, d_state_out, d_reward_out, d_done_out, d_n_bad);
-    else
-        symbol_launch_run(bp, (hipStream_t)stream, d_tokens, d_consts, nullptr, n_substeps, n_substeps, d_state_out, d_reward_out, d_done_out, d_n_bad);
     HIP_TRY(hipGetLastError());
     return MBX_OK;
 }

@@ -1,18 +1,26 @@
-// mbx_run_nlshade.hip — the NL_SHADE_LBC kernels (mbx_nlshade.hpp) and their launch code, a translation unit of their own like mbx_run_rlhpsde.hip; mbx.hip
-// calls the nlshade_* functions declared in mbx_run_kernels.hpp.
+// mbx_run_nlshade.hip — NL_SHADE_LBC: the kernels (mbx_nlshade.hpp), their host code and entry point, a translation unit of their own like
+// mbx_run_rlhpsde.hip; mbx.hip sees the row kNlshadeOps (mbx_host.hpp) and nothing else.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "mbx_device.hpp"
 #include "mbx_rlepso.hpp"
 #include "mbx_nlshade.hpp"
-#include "mbx_run_kernels.hpp"
+#include "mbx_host.hpp"
 
 namespace mbx {
+
+static int nlshade_check(const mbx_algo_cfg& c)
+{
+    if (c.dim < 2 || c.dim > MBX_NLSHADE_DIM_MAX) return fail(MBX_E_ARG, "NL_SHADE_LBC runs dim in [2, %d], not %d", MBX_NLSHADE_DIM_MAX, c.dim);
+    if (c.np != MBX_NLSHADE_NP(c.dim)) return fail(MBX_E_ARG, "NL_SHADE_LBC runs np = 23 dim = %d, not %d", MBX_NLSHADE_NP(c.dim), c.np);
+    if (c.max_fes <= c.np) return fail(MBX_E_ARG, "NL_SHADE_LBC needs max_fes > %d (the initial evaluation), not %d", c.np, c.max_fes);
+    return MBX_OK;
+}
 
 // The population schedule of an episode that runs to the budget (NLPSR, nl_shade_lbc.py:135-147): [0] = the number of updates G, [1 + g] = N after
 // update g (N0 for g = 0).  N = round-half-even(N0 + (4 - N0) x^(1 - x)), x = FEs / MaxFEs, the power in long double, rounded once; FEs advances by
 // the live population, which only ever shrinks.
-std::vector<double> nlshade_schedule(int np, int max_fes)
+static std::vector<double> nlshade_schedule(int np, int max_fes)
 {
     std::vector<double> t{0., (double)np};
     long long fes = np;
@@ -28,28 +36,32 @@ std::vector<double> nlshade_schedule(int np, int max_fes)
     return t;
 }
 
-hipError_t nlshade_prepare(size_t lds_bytes)
+static AlgoGeom nlshade_geom(const mbx_algo_cfg& c) { return MBX_GEOM(NLSHADE, nl_lds_doubles(c.np, c.dim), 1, 0); }
+static int nlshade_prepare(mbx_batch* b, const AlgoGeom& g)
 {
-    hipError_t e = hipFuncSetAttribute((const void*)k_nlshade_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_nlshade_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_nlshade_run, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    return e;
+    if (int rc = allow_lds(lds_of(g), k_nlshade_reset, k_nlshade_step, k_nlshade_run)) return rc;
+    // the population schedule is a function of (dim, max_fes) alone (mbx_nlshade.hpp, quirk 11); the batch's table pointer `pci` carries it
+    const std::vector<double> t = nlshade_schedule(b->cfg.np, b->cfg.max_fes);
+    HIP_TRY(hipMalloc(&b->d_pci, t.size() * sizeof(double)));
+    HIP_TRY(hipMemcpy(b->d_pci, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+    return MBX_OK;
 }
 
-void nlshade_launch_reset(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, double* d_state_out)
-{
-    hipLaunchKernelGGL(k_nlshade_reset, dim3(bp.B), dim3(kThreads), lds_bytes, stream, bp, d_state_out);
-}
+MBX_RESET_FN(nlshade_reset) { MBX_LAUNCH(k_nlshade_reset, kThreads, b->lds_bytes, d_state_out); }
+MBX_STEP_FN(nlshade_step) { MBX_LAUNCH(k_nlshade_step, kThreads, b->lds_bytes, MBX_OUT); return MBX_OK; }
 
-void nlshade_launch_step(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, double* d_state_out, double* d_reward_out, uint8_t* d_done_out)
-{
-    hipLaunchKernelGGL(k_nlshade_step, dim3(bp.B), dim3(kThreads), lds_bytes, stream, bp, d_state_out, d_reward_out, d_done_out);
-}
+MBX_EXPORT_ROW(kNlshadeOps, MBX_ALGO_NLSHADE, "NL_SHADE_LBC", false, false, nlshade_check, nlshade_geom, nlshade_prepare, nlshade_reset, nlshade_step, nullptr);
 
-void nlshade_launch_run(const BatchParams& bp, size_t lds_bytes, hipStream_t stream, int n_updates, double* d_state_out, double* d_reward_out,
-                        uint8_t* d_done_out)
+extern "C" int mbx_nlshade_run(mbx_batch* b, int n_updates, double* d_state_out, double* d_reward_out, uint8_t* d_done_out, void* stream_)
 {
-    hipLaunchKernelGGL(k_nlshade_run, dim3(bp.B), dim3(kThreads), lds_bytes, stream, bp, n_updates, d_state_out, d_reward_out, d_done_out);
+    if (!b) return fail(MBX_E_ARG, "mbx_nlshade_run: null batch");
+    if (b->cfg.algo != MBX_ALGO_NLSHADE) return fail(MBX_E_UNSUPPORTED, "mbx_nlshade_run: the batch is not an NL_SHADE_LBC batch");
+    if (n_updates < 1) return fail(MBX_E_ARG, "mbx_nlshade_run: n_updates must be >= 1");
+    if (b->d_tape && n_updates != 1) return fail(MBX_E_ARG, "mbx_nlshade_run: a replay tape holds one update");
+    const hipStream_t stream = (hipStream_t)stream_;
+    MBX_LAUNCH(k_nlshade_run, kThreads, b->lds_bytes, n_updates, MBX_OUT);
+    HIP_TRY(hipGetLastError());
+    return MBX_OK;
 }
 
 }  // namespace mbx

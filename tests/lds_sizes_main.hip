@@ -78,6 +78,9 @@ static void free_geometry(int NP, int D)
         for (int step = 0; step < 2; ++step)
             for (int cached = 0; cached < 2; ++cached) put("nr", {rows, NP, D, step, cached}, nr_lds_doubles(rows, NP, D, step, cached));
     }
+#ifndef MBX_LDS_SIZES_KERNEL_HEADERS                 // SYMBOL and L2L were born as walks: a tree without mbx_lds.hpp has neither
+    for (int resident = 0; resident < 2; ++resident) put("sym", {NP, D, resident}, sym_lds_doubles(NP, D, resident));
+#endif
 }
 
 static int g_bad = 0;
@@ -161,6 +164,9 @@ int main(int argc, char** argv)
         rows_only(1, D);
         // the fixed populations
         put("les", {D}, les_lds_doubles(D));
+#ifndef MBX_LDS_SIZES_KERNEL_HEADERS
+        put("l2l", {D}, l2l_lds_doubles(D));
+#endif
         for (int rows : {1, MBX_SAHL_NP})
             for (int step = 0; step < 2; ++step) put("sh", {rows, D, step}, sh_lds_doubles(rows, D, step));
         put("jd", {MBX_JDE21_NP, D}, jd_lds_doubles(MBX_JDE21_NP, D));

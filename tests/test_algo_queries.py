@@ -1,7 +1,8 @@
 """The device-free queries of the library (mbx_state_dim, mbx_action_dim, mbx_tape_stride and the text mbx_last_error leaves behind) over every
 algorithm id, pinned to the answers recorded in tests/golden/algo_queries.json.  The file was recorded from the library as it stood before the
-per-algorithm descriptor table (``AlgoOps`` in metabox_amd/csrc/mbx.hip) replaced the if-chains over ``cfg.algo``: the table must answer
-the same, messages and the order of the checks included.  Re-record with ``MBX_LIB=<library> python tests/test_algo_queries.py``.
+per-algorithm descriptor table (``AlgoOps`` in metabox_amd/csrc/mbx_host.hpp, ``kAlgoOps`` in mbx.hip) replaced the if-chains over ``cfg.algo``: the
+table must answer the same, messages and the order of the checks included.  Ids 24 .. 29 and the named cases of ids 24 .. 27 joined later, recorded from the
+library as it stood before the own-unit algorithms' checks moved into their translation units.  Re-record with ``MBX_LIB=<library> python tests/test_algo_queries.py``.
 """
 import ctypes as C
 import json
@@ -14,7 +15,7 @@ if ROOT not in sys.path:
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'algo_queries.json')
 
 SHAPES = ((100, 10), (170, 10), (200, 10), (99, 10), (40, 10), (16, 10), (50, 30), (1000, 10), (100, 65))
-RLEPSO, MADDE, SDMSPSO, SAHLPSO, LES = 1, 15, 18, 20, 21
+RLEPSO, MADDE, SDMSPSO, SAHLPSO, LES, RLHPSDE, NLSHADE, L2L, SYMBOL = 1, 15, 18, 20, 21, 24, 25, 26, 27
 
 
 def _cfg(algo, np_, dim, max_fes=20000, log_interval=400, n_logpoint=50, n_group=5, flags=0):
@@ -22,9 +23,9 @@ def _cfg(algo, np_, dim, max_fes=20000, log_interval=400, n_logpoint=50, n_group
 
 
 def cases():
-    """name -> cfg fields: the grid of every id 0..23 (the unassigned ones included) over SHAPES, then the single-fault cases and one doubly-wrong cfg."""
+    """name -> cfg fields: the grid of every id 0..29 (the unassigned ones included) over SHAPES, then the single-fault cases and one doubly-wrong cfg."""
     out = {}
-    for algo in range(24):
+    for algo in range(30):
         for np_, dim in SHAPES:
             out[f'grid-{algo}-{np_}-{dim}'] = _cfg(algo, np_, dim)
     out['rlepso-n_group-0'] = _cfg(RLEPSO, 100, 10, n_group=0)
@@ -42,6 +43,17 @@ def cases():
     out['flag-bit-9'] = _cfg(RLEPSO, 100, 10, flags=1 << 9)
     out['madde-dim-41'] = _cfg(MADDE, 2 * 41 * 41, 41)
     out['madde-np-wrong-and-dim-65'] = _cfg(MADDE, 100, 65)          # two faults: the algorithm's own limits are checked before the common dim range
+    # ids 24 .. 27: one valid cfg each (the grid's shapes hold none for RL-HPSDE, NL_SHADE_LBC and L2L), then each of their own refusals
+    out['rlhpsde-valid'] = _cfg(RLHPSDE, 180, 10)
+    out['rlhpsde-max_fes-np-and-walk'] = _cfg(RLHPSDE, 180, 10, max_fes=381)
+    out['rlhpsde-dim-41'] = _cfg(RLHPSDE, 18 * 41, 41)
+    out['nlshade-valid'] = _cfg(NLSHADE, 230, 10)
+    out['nlshade-max_fes-np'] = _cfg(NLSHADE, 230, 10, max_fes=230)
+    out['l2l-valid'] = _cfg(L2L, 1, 10)
+    out['l2l-np-2'] = _cfg(L2L, 2, 10)
+    out['l2l-dim-41'] = _cfg(L2L, 1, 41)
+    out['symbol-np-129'] = _cfg(SYMBOL, 129, 10)
+    out['symbol-dim-41'] = _cfg(SYMBOL, 100, 41)
     return out
 
 
@@ -87,7 +99,9 @@ def test_the_examples_of_the_record():
     for n in (8, 16):                                     # the last group of eight would read actions 56 .. 62 of 56, the last of sixteen 240 .. 246 of 112
         assert want[f'rlepso-n_group-{n}'][:3] == [-1, -1, -1] and 'slice' in want[f'rlepso-n_group-{n}'][3], want[f'rlepso-n_group-{n}']
     assert want['rlepso-n_group-0'] == [-1, -1, -1, 'bad n_group 0'] and want['rlepso-n_group-17'] == [-1, -1, -1, 'bad n_group 17']
-    assert len(want) == 24 * len(SHAPES) + 15
+    assert want['l2l-valid'] == [1, 10, 3, ''] and want['l2l-np-2'] == [-1, -1, -1, 'L2L runs np = 1 (one point per step), not 2']
+    assert want['symbol-np-129'] == [-3, -3, -3, 'SYMBOL runs np in [4, 128], not 129']      # every SYMBOL refusal is MBX_E_UNSUPPORTED
+    assert len(want) == 30 * len(SHAPES) + 25
 
 
 if __name__ == '__main__':

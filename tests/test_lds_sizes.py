@@ -54,7 +54,7 @@ def test_the_record_holds_the_sizes_checked_by_hand():
     assert want['sh(1,10,1)'] == 10 + 170 + 512 + 200 + 40 + 2 + 32 + 140 + 1200 + 160 + 128 == 2594
     # QLPSO step, one row, NP = 30, D = 10: X 10 | T 170 | Z 512 | 200 | 5 vectors of 10 | NC 2 | RED 16 | POP 300 | COST 30 | DIST 30 | SC 16
     assert want['ql(1,30,10)'] == 10 + 170 + 512 + 200 + 50 + 2 + 16 + 300 + 30 + 30 + 16 == 1336
-    assert len(want) == 4799
+    assert len(want) == 4799 + 227         # the sym and l2l families joined later, recorded from the tree before their host code moved
 
 
 def test_every_walk_ends_where_the_recorded_formula_did(tmp_path):
