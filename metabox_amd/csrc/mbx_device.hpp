@@ -219,6 +219,8 @@ __device__ __forceinline__ double min_f64_no_nan(double x, double y)
 // selects per round); the index is found afterwards: the lowest lane of the first 64-entry step of `a` that holds an entry equal to the minimum, i.e. the first
 // index of the minimum, np.argmin's.  (Not the lowest LANE of the exchange: lane l has folded entries l, l + 64, ... and would answer l + 64 before l + 1.)
 // A NaN never enters the exchange (x < v is false for it), -0. == 0. holds as it did in wave_argmin's tie rule, and the value handed back is a[imin] itself.
+// PRIO_AT_BARRIER >= 0: s_setprio to that level in front of the first barrier, in straight-line code every wave runs (the resident RLEPSO kernel's third priority level)
+template <int PRIO_AT_BARRIER = -1>
 __device__ __forceinline__ void block_argmin(const double* a, int n, double* red, double& vmin, int& imin)
 {
     const int tid = opaque_tid();
@@ -239,6 +241,7 @@ __device__ __forceinline__ void block_argmin(const double* a, int n, double* red
         }
         if (tid == 0) { red[0] = a[idx]; red[1] = (double)idx; }
     }
+    if constexpr (PRIO_AT_BARRIER >= 0) __builtin_amdgcn_s_setprio(PRIO_AT_BARRIER);
     __syncthreads();
     vmin = red[0]; imin = (int)red[1];
     __syncthreads();

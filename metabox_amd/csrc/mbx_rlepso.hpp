@@ -192,6 +192,9 @@ __device__ unsigned long long g_phase_cycles[8192 * 16];         // [block][phas
 // workgroups share a CU, so the short dependency-bound phases (policy, ranking, move, objective, commit) of one workgroup are served ahead of the other workgroups' scans,
 // which fill whatever is left (docs/EXPERIMENTS.md: -2.3 % / -2.5 % on the headline, no instruction saved).  s_setprio ignores EXEC: all three sit in straight-line code of
 // the generation loop that every wave of the workgroup runs.  0: no s_setprio at all (the A/B switch).  The 512- / 1024-thread kernels own their CU and were not measured.
+// 2: the same, and level 2 around the phases only wave 0 runs (policy draw, block_argmin's index step, thread 0's logging) and the ones only the waves that hold particles
+// run (the ranking's per-particle step, the re-initialisation draw), back to 1 in front of the next barrier: every wave of the workgroup executes each s_setprio (the waves
+// without work in the phase go from 2 to 1 a few instructions later, at the barrier they wait at).  Measured and not shipped (docs/EXPERIMENTS.md).
 #ifndef MBX_RL_PRIO
 #define MBX_RL_PRIO 1
 #endif
@@ -584,7 +587,73 @@ __device__ __noinline__ void fdr_settle_own(const double* __restrict__ NC, const
 // 6.7 % of the wave-passes for a second scan, +10.4 % per generation against +3.5 % of instructions; (b) the flagged lanes' items settled by their own wave right behind
 // the pass (readlane + fdr_settle): the serial ~250-instruction chain then sits inside the scan of a wave the other three wait for, +4.8 % in the driver window against
 // +3.9 % for the list, +10.6 % against +8.8 % over whole episodes.
-template <int W, int UN, bool TIE, int THREADS, int GR = 1>
+//
+// The deal (MBX_FDR_DEAL = 1): P = ceil(NI / THREADS) passes hold P THREADS slots, off = P THREADS - NI more than there are items.  In pass p thread tid sits at slot
+// s = p THREADS + (p odd ? THREADS - 1 - tid : tid) and owns item s - off; the off slots below zero are idle.  So the 64-item chunks are cut from the TOP of the table
+// and the partial chunk is the lowest one, in the first lanes of pass 0: a wave pays for its highest rank, and the chunk that is short of items is then the one that was
+// cheapest anyway.  NP 100 / D 10 (500 items, off = 12): bounds 10, 23, 35, 48 | 99, 87, 74, 61, sum 437 -- against 12, 25, 38, 51 | 99, 87, 74, 61 = 447 with the
+// partial chunk at the top ranks (MBX_FDR_DEAL = 0: passes filled from item 0, the last one short; the A/B switch) -- and 109 / 110 / 109 / 109 per wave.  A wave all of
+// whose slots are idle (NP 100 / D 12: off = 168, waves 0 and 1 of pass 0) skips the scan: its lanes' items are all negative.  Where NI is a multiple of 64 the chunk
+// maxima are the same in both deals, and the table is dealt from item 0 as before (fdr_deal_from_top).  Every item is scanned once, through the same `step`, to a bound >= its own rank and <= NP - 1: same exemplars, same flags; only the
+// order of FL changes, and each flagged coordinate is settled on its own.
+#ifndef MBX_FDR_DEAL
+#define MBX_FDR_DEAL 1
+#endif
+// Which chunk of a pass a wave takes (MBX_FDR_WAVE_DEAL = 1; default 0: chunk w of every pass).  Wave w of every resident workgroup sits on SIMD w, and wave 0 (policy
+// draw, block_argmin's index step, logging) and wave 1 (particles 64 .. 99) carry ~330 / ~210 more non-scan vector instructions per generation than waves 2 and 3; a table
+// per compile-time geometry (WD of fdr_pass; 0: none) can hand wave 0 a lighter pair of chunks.  WD = 1, NP 100 / D 10 on 256 threads: pass 0 chunks 0, 3, 2, 1 and pass 1
+// chunks 1, 3, 2, 0 for waves 0 .. 3, i.e. bounds 10 + 87, 48 + 61, 35 + 74, 23 + 99 = 97 / 109 / 109 / 122 instead of 109 / 110 / 109 / 109: the same eight chunks, so
+// the same items, bounds and results.  Measured and not shipped (docs/EXPERIMENTS.md).  -> the first thread of the chunk the wave of first thread w0 takes in `pass`.
+#ifndef MBX_FDR_WAVE_DEAL
+#define MBX_FDR_WAVE_DEAL 0
+#endif
+template <int WD>
+__device__ __forceinline__ int fdr_deal_chunk(int pass, int w0)
+{
+    if constexpr (WD == 1) {
+        constexpr unsigned tbl[2] = {0x1230u, 0x0231u};           // a nibble per wave
+        return (int)((tbl[pass & 1] >> (w0 >> 4)) & 3u) << 6;      // (w0 >> 6) * 4 bits
+    } else return w0;
+}
+// Is the table dealt from the top?  Not where NI is a multiple of 64: every chunk is whole, both deals cut the same chunks and no bound can fall, and there the short pass
+// stays the last one -- config 5 (NP 128 / D 40 on 1024 threads, 2560 items, off = 512) measured 1.610 -> 1.691 ms per generation with its eight idle waves in pass 0
+// instead of pass 2 (docs/EXPERIMENTS.md).
+__device__ __forceinline__ bool fdr_deal_from_top(int NI) { return MBX_FDR_DEAL != 0 && NI % 64 != 0; }
+// The item of thread tid (of the wave whose first thread is w0) in pass `pass` (fdr_deal_live: does the slot hold one?), for the scan and for the collapsed-swarm branch
+// that settles a lane's own items
+template <int THREADS, int WD = 0>
+__device__ __forceinline__ int fdr_deal_item(int NI, int pass, int tid, int w0)
+{
+    if constexpr (WD != 0) tid = fdr_deal_chunk<WD>(pass, w0) + (tid & 63);
+    if (fdr_deal_from_top(NI)) {
+        const int off = (NI + THREADS - 1) / THREADS * THREADS - NI;
+        return pass * THREADS + ((pass & 1) ? THREADS - 1 - tid : tid) - off;
+    }
+    const int base = pass * THREADS, lim = base + THREADS < NI ? base + THREADS : NI;
+    return (pass & 1) ? lim - 1 - tid : base + tid;
+}
+// Does the slot hold an item?  (From item 0: the parent's own test, on the parent's own expression)
+template <int THREADS>
+__device__ __forceinline__ bool fdr_deal_live(int NI, int pass, int ps)
+{
+    if (fdr_deal_from_top(NI)) return pass > 0 || ps >= 0;        // (off < THREADS: the idle slots are all in pass 0; later passes carry no test)
+    const int base = pass * THREADS, lim = base + THREADS < NI ? base + THREADS : NI;
+    return ps >= base && ps < lim;
+}
+// The highest item of that wave (scalar; from the top, < 0: the whole wave is idle, and then no slot of it is live)
+template <int THREADS, int WD = 0>
+__device__ __forceinline__ int fdr_deal_top(int NI, int pass, int w0)
+{
+    w0 = fdr_deal_chunk<WD>(pass, w0);
+    if (fdr_deal_from_top(NI)) {
+        const int off = (NI + THREADS - 1) / THREADS * THREADS - NI;
+        return pass * THREADS + ((pass & 1) ? THREADS - 1 - w0 : w0 + 63) - off;
+    }
+    const int base = pass * THREADS, lim = base + THREADS < NI ? base + THREADS : NI;
+    return (pass & 1) ? lim - 1 - w0 : (base + w0 + 63 < lim ? base + w0 + 63 : lim - 1);
+}
+
+template <int W, int UN, bool TIE, int THREADS, int GR = 1, int WD = 0>
 __device__ __forceinline__ void fdr_pass(const RlLds& L, const int* ORDER, const int* NLESS, int NP, int D, int tid, double range, unsigned long long* cnt = nullptr)
 {
     const int DW = D / W, NI = NP * DW;
@@ -592,13 +661,12 @@ __device__ __forceinline__ void fdr_pass(const RlLds& L, const int* ORDER, const
     uint32_t mine = 0;                                            // bit p: this thread's item of pass p was flagged
     const int w0 = __builtin_amdgcn_readfirstlane(tid & ~63);     // the wave's first thread, on the scalar unit
     for (int base = 0, pass = 0; base < NI; base += THREADS, ++pass) {
-        const int lim = base + THREADS < NI ? base + THREADS : NI;
-        const int ps = (pass & 1) ? lim - 1 - tid : base + tid;
-        if (ps >= base && ps < lim) {
+        const int ps = fdr_deal_item<THREADS, WD>(NI, pass, tid, w0);
+        if (fdr_deal_live<THREADS>(NI, pass, ps)) {
             const int rk = fw.div(ps), d0 = W * (ps - rk * DW);
             // the scan's trip count, one per wave: the highest rank among the wave's items (consecutive in ps; nless(rank) <= rank), scalar arithmetic from the pass
             // and the wave's place in it (fdr_exact: scanning past a lane's own nless changes nothing)
-            const int top = (pass & 1) ? lim - 1 - w0 : (base + w0 + 63 < lim ? base + w0 + 63 : lim - 1);
+            const int top = fdr_deal_top<THREADS, WD>(NI, pass, w0);
             int bound = __builtin_amdgcn_readfirstlane(fw.div(top));
 #ifdef MBX_FDR_ROUND_BOUND
             // experiment, measured and dropped (docs/EXPERIMENTS.md): the bound rounded up to whole unrolled groups where the table allows it, so that only the waves
@@ -627,10 +695,9 @@ __device__ __forceinline__ void fdr_pass(const RlLds& L, const int* ORDER, const
             }
             __syncthreads();
         } else if (n > 0) {                                       // a collapsed swarm: every lane settles its own items (passes <= 32: NP x D / W <= 32 x THREADS)
-            for (int base = 0, pass = 0; mine != 0u; base += THREADS, ++pass, mine >>= 1) {
+            for (int pass = 0; mine != 0u; ++pass, mine >>= 1) {
                 if (!(mine & 1u)) continue;
-                const int lim = base + THREADS < NI ? base + THREADS : NI;
-                const int ps = (pass & 1) ? lim - 1 - tid : base + tid, rk = fw.div(ps), d0 = W * (ps - rk * DW);
+                const int ps = fdr_deal_item<THREADS, WD>(NI, pass, tid, w0), rk = fw.div(ps), d0 = W * (ps - rk * DW);      // (a flagged pass: the slot held an item)
                 int kb[W];
 #pragma unroll
                 for (int q = 0; q < W; ++q) kb[q] = L.KB[rk * D + d0 + q];
@@ -1202,8 +1269,9 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
     int* RCNT = (int*)(L.RED + 2);  // re-initialisation count of each wave that holds particles (RED[2..9]: up to 16 waves)
     constexpr int PW = (NP + 63) / 64;      // waves that hold particles
 
+    constexpr bool PRIO2 = MBX_RL_PRIO == 2 && THREADS == 256;    // the third priority level (see MBX_RL_PRIO)
     // pbest / gbest bookkeeping of update() and __reinit() (rl_commit with c_cost and the pbest positions in registers)
-    auto commit = [&](bool stagnation, int tid) {
+    auto commit =[&](bool stagnation, int tid) {
         if (tid < NP) {
             const double nc = L.NC[tid];
             if (stagnation) L.PNI[tid] = nc < cc ? 0. : L.PNI[tid] + 1;
@@ -1213,7 +1281,8 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
             cc = nc;
         }
         double cbv; int cb;
-        block_argmin(L.NC, NP, L.RED, cbv, cb);         // contains the barriers that publish IMPR
+        if constexpr (PRIO2) { __builtin_amdgcn_s_setprio(2); block_argmin<1>(L.NC, NP, L.RED, cbv, cb); }      // (wave 0's value exchange and index step at level 2)
+        else block_argmin(L.NC, NP, L.RED, cbv, cb);    // contains the barriers that publish IMPR
         const bool better = cbv < gbest;
         if (better) { gbest = cbv; gbest_idx = cb; }
 #pragma unroll
@@ -1238,6 +1307,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         const Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)gen, episode, true};
         const double pre_gbest = gbest;
         // ---- agent.act: the action of this generation from row fes of the actor table (same draws as mbx_gauss_policy)
+        if constexpr (PRIO2) __builtin_amdgcn_s_setprio(2);
         if (tid < A) {
             int row = fes;
             row = row < ar().table_rows ? row : ar().table_rows - 1;
@@ -1252,8 +1322,9 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         }
         if (tid < NP) ORDER[tid] = tid;
         if (tid == 0) { *EQC = 0; *L.FLN = 0; }
+        if constexpr (PRIO2) __builtin_amdgcn_s_setprio(1);
         __syncthreads();
-        if (tid < G) {                                            // __get_coe (:112-132), float32 like k_rlepso_step
+        if (tid < G) {                                           // __get_coe (:112-132), float32 like k_rlepso_step
             const float* a = ACT + tid * G;
             const float cm = a[0] * 0.01f;
             const float wv = a[1] * 0.8f + 0.1f;
@@ -1296,6 +1367,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
             if (lane < PER && i0 + lane < NP) NLESS[i0 + lane] = res;
         }
         __syncthreads();
+        if constexpr (PRIO2) __builtin_amdgcn_s_setprio(2);
         if (tid < NP) {
             const int i = tid, gi = fg.div(i);
             L.CMUT[i] = NP % G == 0 || gi < G ? L.COEF[gi * 6] * L.PNI[i] : 0.;      // (NP a multiple of G: every particle has a group)
@@ -1305,6 +1377,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
             RANK[i] = rank;
             ORDER[rank] = i; L.NC[rank] = L.PBC[i]; L.NCS[rank] = L.PBC[i];
         }
+        if constexpr (PRIO2) __builtin_amdgcn_s_setprio(1);
         __syncthreads();
         if (tid < NP && ORDER[RANK[tid]] != tid) *EQC = 1;
         // ---- pbest positions -> LDS in rank order, from the owners' registers
@@ -1341,7 +1414,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         __syncthreads();
 #else
         if constexpr (MBX_RL_PRIO && THREADS == 256) __builtin_amdgcn_s_setprio(0);
-        fdr_pass<2, (DC == 40 ? MBX_FDR_UNROLL_D40 : MBX_FDR_UNROLL), TIE, THREADS, (THREADS == 256 ? MBX_FDR_GROUPS : 1)>(L, ORDER, NLESS, NP, D, tid, ub - lb + 1e-5, ar().bp.clk);      // (ends with the barrier that publishes KB)
+        fdr_pass<2, (DC == 40 ? MBX_FDR_UNROLL_D40 : MBX_FDR_UNROLL), TIE, THREADS, (THREADS == 256 ? MBX_FDR_GROUPS : 1), (MBX_FDR_WAVE_DEAL && THREADS == 256 && NPC == 100 && DC == 10 ? 1 : 0)>(L, ORDER, NLESS, NP, D, tid, ub - lb + 1e-5, ar().bp.clk);      // (ends with the barrier that publishes KB)
         if constexpr (MBX_RL_PRIO && THREADS == 256) __builtin_amdgcn_s_setprio(1);
 #endif
         // (Measured and dropped, round 3: dealing config 5's half-empty last pass -- 512 items of the highest ranks on 1024 threads -- as single
@@ -1379,6 +1452,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         // the count: every wave that holds particles counts its lanes' flags on the scalar unit and publishes the sum; ONE barrier (which is also the one that ends
         // update()'s commit) where __syncthreads_count spends three, a block-size look-up and a cross-lane add in all four waves
         int mine = 0;
+        if constexpr (PRIO2) __builtin_amdgcn_s_setprio(2);
         if (tid < NP) {
 #ifndef MBX_ABLATE_REINIT_DRAW
             const U4 w = rng.draw((uint32_t)tid, MBX_SITE_REINIT);
@@ -1390,6 +1464,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         {
             const int cnt = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine != 0));
             if ((tid & 63) == 0 && tid < 64 * PW) RCNT[tid >> 6] = cnt;
+            if constexpr (PRIO2) __builtin_amdgcn_s_setprio(1);
             __syncthreads();
             int n = 0;
 #pragma unroll
@@ -1419,6 +1494,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
         // ---- logging, termination, reward (:241-261): the counters are scalars (see above), the two float64 compares on gbest are made wave-uniform by a ballot;
         // thread 0 writes the curve.  (fes and the log point are integers below 2^31 and 2^62: the integer compare is the reference's float64 one)
 #ifndef MBX_ABLATE_LOG
+        if constexpr (PRIO2) __builtin_amdgcn_s_setprio(2);
         if ((int64_t)fes >= (int64_t)log_index * ar().bp.log_interval) { log_index += 1; if (tid == 0) curve_put(cost, ar().bp.n_logpoint, cost_len, gbest); cost_len += 1; }
         done = fes >= ar().bp.max_fes;
         if (!isnan(P.optimum) && ar().bp.early_stop) done = done || __builtin_amdgcn_ballot_w64(gbest <= 1e-8) != 0ull;
@@ -1433,6 +1509,7 @@ __device__ __forceinline__ void rl_run_body(ARGS ar)
             if (ar().out.traj_reward) ar().out.traj_reward[g * B + b] = improved ? 1. : -1.;
             if (ar().out.traj_done) ar().out.traj_done[g * B + b] = done ? 1 : 0;
         }
+        if constexpr (PRIO2) __builtin_amdgcn_s_setprio(1);
 #endif
     }
     // ---- store the state block once

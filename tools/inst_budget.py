@@ -59,10 +59,15 @@ VARIANTS = {
     'one_group': ['-DMBX_FDR_GROUPS=1'],                       # the scan's loops as before the third budget: one group per trip, indexed remainder
     'two_groups': ['-DMBX_FDR_GROUPS=2'],                      # two groups (8 candidates) per trip instead of the shipped three
     'no_prio': ['-DMBX_RL_PRIO=0'],                            # no s_setprio around the FDR pass (scalar instructions: the vector count is the same; the A/B is one of time)
+    'old_deal': ['-DMBX_FDR_DEAL=0'],                          # the FDR pass dealt from item 0 with the short pass at the top ranks, as before the fourth budget
+    'wave_deal': ['-DMBX_FDR_WAVE_DEAL=1'],                    # wave 0 takes the chunks of bounds 10 + 87 (not shipped; same chunks: the A/B is one of time)
+    'prio2': ['-DMBX_RL_PRIO=2'],                              # a third priority level around the phases of wave 0 / of the particle waves (not shipped; scalar instructions)
 }
 TRIMS = [('tournaments compacted per wave', 'full', 'per_item_tourn'), ('scan bound rounded up to whole groups (not shipped)', 'round_bound', 'full'),
          ('scan: three groups per trip from one pair of address registers, straight-line remainder', 'full', 'one_group'),
-         ('scan: two groups per trip instead of three (not shipped)', 'two_groups', 'full'), ('wave priority 1 outside the FDR pass, 0 inside (scalar instructions: no vector instruction is saved)', 'full', 'no_prio')]
+         ('scan: two groups per trip instead of three (not shipped)', 'two_groups', 'full'), ('wave priority 1 outside the FDR pass, 0 inside (scalar instructions: no vector instruction is saved)', 'full', 'no_prio'),
+         ('FDR pass dealt from the top of the table: the short chunk at the low ranks', 'full', 'old_deal'),
+         ('chunk-to-wave table: wave 0 takes bounds 10 + 87 (not shipped)', 'wave_deal', 'full'), ('third priority level (not shipped; scalar instructions)', 'prio2', 'full')]
 # phase -> (minuend variant, subtrahend variant): instructions of the phase = count(minuend) - count(subtrahend)
 PHASES = [
     ('policy draw', 'full', 'no_policy'),
