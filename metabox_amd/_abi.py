@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/mbx.h, include/mbx_les.h, include/mbx_l2l.h, include/mbx_symbol.h, include/mbx_rlhpsde.h and include/mbx_nlshade.h (libmbx.so).
+"""ctypes binding of the C-ABI in include/mbx.h, include/mbx_les.h, include/mbx_l2l.h, include/mbx_gleet.h, include/mbx_symbol.h, include/mbx_rlhpsde.h and include/mbx_nlshade.h (libmbx.so).
 
 This is the stub a maintainer of the reference would add to reach the HIP path (INTEGRATION.md shows it
 in isolation).  The library is built in-tree by ``__graft_entry__.build()`` / ``make -C metabox_amd/csrc``;
@@ -118,7 +118,7 @@ class MbxError(RuntimeError):
 
 
 def load_lib():
-    """Load libmbx.so and declare the prototypes of every symbol in include/mbx.h, include/mbx_les.h, include/mbx_l2l.h, include/mbx_symbol.h, include/mbx_rlhpsde.h and include/mbx_nlshade.h."""
+    """Load libmbx.so and declare the prototypes of every symbol in include/mbx.h, include/mbx_les.h, include/mbx_l2l.h, include/mbx_gleet.h, include/mbx_symbol.h, include/mbx_rlhpsde.h and include/mbx_nlshade.h."""
     global _lib
     if _lib is not None:
         return _lib
@@ -169,6 +169,8 @@ def load_lib():
         'mbx_les_rollout': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         'mbx_l2l_set_params': (C.c_int, [vp, vp, C.c_int, vp]),
         'mbx_l2l_rollout': (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+        'mbx_gleet_set_params': (C.c_int, [vp, vp, C.c_int, vp, C.c_float, C.c_float]),
+        'mbx_gleet_rollout': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
         'mbx_symbol_rollout': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
         'mbx_rlhpsde_rollout': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
         'mbx_nlshade_run': (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
@@ -209,6 +211,9 @@ LES_SYMBOLS = ('mbx_les_set_params', 'mbx_les_rollout')
 
 # the entry points of include/mbx_l2l.h (L2L)
 L2L_SYMBOLS = ('mbx_l2l_set_params', 'mbx_l2l_rollout')
+
+# the entry points of include/mbx_gleet.h (GLEET's resident rollout)
+GLEET_SYMBOLS = ('mbx_gleet_set_params', 'mbx_gleet_rollout')
 
 # the entry point of include/mbx_symbol.h (SYMBOL)
 SYMBOL_SYMBOLS = ('mbx_symbol_rollout',)

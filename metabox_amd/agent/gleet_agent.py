@@ -399,17 +399,43 @@ class GLEET_Agent(Basic_Agent):
     def rollout_batch(self, env, max_steps=None, policy='hip'):
         """Lock-step rollout of a BatchedPBO_Env, two launches per generation: policy = 'hip' (default) evaluates the attention actor
         with ``mbx_gleet_policy`` (one workgroup per swarm), 'torch' with the PyTorch modules (``act_batch``); then the fused
-        generation kernel.  Both sample the same distribution; 'torch' uses torch's generator instead of the instance's Philox stream."""
+        generation kernel.  Both sample the same distribution; 'torch' uses torch's generator instead of the instance's Philox stream.
+        policy = 'resident': ONE launch for the whole episode, the actor inside the step kernel (``mbx_gleet_rollout``), with the Philox draws of 'hip'."""
         bc = env.batch.cfg
         if max_steps is None:
             max_steps = -(-(bc.max_fes - bc.np) // bc.np)
-        state = env.reset()
         actor = self.actor
+        if policy == 'resident':
+            # the actor inside the step kernel: the weights once, then the whole episode in one launch (``mbx_gleet_rollout``); same Philox draws as 'hip'
+            env.batch.gleet_set_params(actor.packed_weights(), None, actor.min_sigma, actor.max_sigma)
+            env.reset()
+            env.batch.gleet_rollout(max_steps)
+            max_steps = 0
+        else:
+            state = env.reset()
         for _ in range(max_steps):
             if policy == 'hip':
                 actions = env.batch.gleet_policy(actor.packed_weights(), actor.min_sigma, actor.max_sigma)
             else:
                 actions = self.act_batch(state)
             state, _, _ = env.step(actions)
+        res = env.results()
+        return {'cost': res['cost'], 'fes': res['fes'], 'return': res['return'], 'steps': res['steps'], 'cost_len': res['cost_len']}
+
+    @staticmethod
+    def rollout_checkpoints(agents, env):
+        """Whole episodes of a BatchedPBO_Env whose instances are len(agents) equal blocks, block k under the actor of agents[k] -- the checkpoints of a
+        ``--rollout`` table as ONE resident batch: the agents' packed weights are the batch's weight sets, checkpoint-major, and every instance runs
+        under the set of its block.  The agents may live on any device (unpickled ones are on the host): only their packed weights move."""
+        bc = env.batch.cfg
+        if env.B % len(agents):
+            raise ValueError(f'GLEET_Agent.rollout_checkpoints: {env.B} instances are not {len(agents)} equal blocks')
+        sig = {(float(a.actor.min_sigma), float(a.actor.max_sigma)) for a in agents}
+        if len(sig) != 1:
+            raise ValueError(f'GLEET_Agent.rollout_checkpoints: the checkpoints disagree on (min_sigma, max_sigma): {sorted(sig)}')
+        weights = torch.stack([a.actor.packed_weights().detach().cpu() for a in agents])
+        env.batch.gleet_set_params(weights, np.repeat(np.arange(len(agents)), env.B // len(agents)), *sig.pop())
+        env.reset()
+        env.batch.gleet_rollout(-(-(bc.max_fes - bc.np) // bc.np))
         res = env.results()
         return {'cost': res['cost'], 'fes': res['fes'], 'return': res['return'], 'steps': res['steps'], 'cost_len': res['cost_len']}

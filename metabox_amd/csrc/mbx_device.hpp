@@ -13,6 +13,7 @@
 #include "../../include/mbx.h"
 #include "../../include/mbx_les.h"
 #include "../../include/mbx_l2l.h"
+#include "../../include/mbx_gleet.h"
 #include "../../include/mbx_symbol.h"
 #include "../../include/mbx_rlhpsde.h"
 #include "../../include/mbx_nlshade.h"

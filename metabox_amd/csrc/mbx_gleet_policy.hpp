@@ -44,6 +44,9 @@ struct GpOff {
 };
 
 struct GleetActor { const float* w; float min_sigma, max_sigma; };
+// The weights through the constant address space: a uniform load from it is a scalar load whatever the kernel has stored in between.  (A plain pointer's loads are
+// scalar only while no store of the kernel can have clobbered them: true in k_gleet_policy, which stores last, not in a kernel that loops over steps.)
+typedef const float __attribute__((address_space(4)))* GpConstW;
 
 __host__ __device__ inline size_t gleet_policy_lds_bytes(int NP)
 {
@@ -80,11 +83,13 @@ __device__ __forceinline__ void gp_swarm_norm(float (&x)[kGpE], bool live, int N
 
 // MultiHeadEncoder (networks.py:256-340): x <- norm(MHA(keys/values from x, queries from qsrc) + x); x <- norm(FF(x) + x).
 // W points at this layer's weights in LDS; KL / VL are the swarm's key / value rows in LDS.
-__device__ __forceinline__ void gp_encoder_layer(float (&x)[kGpE], const float (&qsrc)[kGpE], const float* __restrict__ W, float* KL, float* VL,
+// WP: how the caller addresses the weights -- const float* (k_gleet_policy), or GpConstW where a kernel stores to global memory before it reads them again.
+template <class WP>
+__device__ __forceinline__ void gp_encoder_layer(float (&x)[kGpE], const float (&qsrc)[kGpE], WP __restrict__ W, float* KL, float* VL,
                                                  bool live, int NP, int i, float* red)
 {
-    const float* Wq = W; const float* Wk = W + GpOff::attn; const float* Wv = W + 2 * GpOff::attn; const float* Wo = W + 3 * GpOff::attn;
-    const float* F1 = W + 4 * GpOff::attn; const float* B1 = F1 + kGpFF * kGpE; const float* F2 = B1 + kGpFF; const float* B2 = F2 + kGpE * kGpFF;
+    WP Wq = W; WP Wk = W + GpOff::attn; WP Wv = W + 2 * GpOff::attn; WP Wo = W + 3 * GpOff::attn;
+    WP F1 = W + 4 * GpOff::attn; WP B1 = F1 + kGpFF * kGpE; WP F2 = B1 + kGpFF; WP B2 = F2 + kGpE * kGpFF;
     float Q[kGpH * kGpDk];
     if (live) {
 #pragma unroll
@@ -168,10 +173,11 @@ __device__ __forceinline__ void gp_encoder_layer(float (&x)[kGpE], const float (
 }
 
 // 16 -> 32 -> 8 -> 1 with LeakyReLU(0.01) (gleet_agent.py:365-370)
-__device__ __forceinline__ float gp_head(const float (&z)[kGpE], const float* __restrict__ W)
+template <class WP>
+__device__ __forceinline__ float gp_head(const float (&z)[kGpE], WP __restrict__ W)
 {
-    const float* W1 = W; const float* B1 = W1 + kGpH1 * kGpE; const float* W2 = B1 + kGpH1; const float* B2 = W2 + kGpH2 * kGpH1;
-    const float* W3 = B2 + kGpH2; const float* B3 = W3 + kGpH2;
+    WP W1 = W; WP B1 = W1 + kGpH1 * kGpE; WP W2 = B1 + kGpH1; WP B2 = W2 + kGpH2 * kGpH1;
+    WP W3 = B2 + kGpH2; WP B3 = W3 + kGpH2;
     float h1[kGpH1];
 #pragma unroll
     for (int o = 0; o < kGpH1; ++o) {
@@ -192,6 +198,42 @@ __device__ __forceinline__ float gp_head(const float (&z)[kGpE], const float* __
     return out;
 }
 
+// The three embeddings of one particle (xi: its 27 state values -- features | exploration memory | exploitation memory) and the decoder's query:
+// h = Embed(features), dq = Embed2([Embed(exploration memory) | Embed(exploitation memory)])
+template <class WP>
+__device__ __forceinline__ void gp_embed(const float* xi, WP __restrict__ W, float (&h)[kGpE], float (&dq)[kGpE])
+{
+    WP We = W + GpOff::we;
+    float e1[kGpE], e2[kGpE];
+#pragma unroll
+    for (int o = 0; o < kGpE; ++o) {
+        float a = 0.f, p = 0.f, g = 0.f;
+#pragma unroll
+        for (int k = 0; k < kGpNode; ++k) { const float w = We[o * kGpNode + k]; a += xi[k] * w; p += xi[kGpNode + k] * w; g += xi[2 * kGpNode + k] * w; }
+        h[o] = a; e1[o] = p; e2[o] = g;
+    }
+    WP Wd = W + GpOff::wd;
+#pragma unroll
+    for (int o = 0; o < kGpE; ++o) {
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < kGpE; ++k) a += e1[k] * Wd[o * 2 * kGpE + k];
+#pragma unroll
+        for (int k = 0; k < kGpE; ++k) a += e2[k] * Wd[o * 2 * kGpE + kGpE + k];
+        dq[o] = a;
+    }
+}
+
+// the two heads, squashed (gleet_agent.py:425-431); the draw is sample_action(rng, i, mu, sigma, MBX_POLICY_RLEPSO): clamp(Normal(mu, sigma), 0, 1)
+template <class WP>
+__device__ __forceinline__ void gp_mu_sigma(const float (&z)[kGpE], WP __restrict__ W, float min_sigma, float max_sigma, float& mu, float& sigma)
+{
+    const float am = gp_head(z, W + GpOff::mu), as = gp_head(z, W + GpOff::sigma);
+    mu = (tanhf(am) + 1.f) / 2.f;
+    sigma = (tanhf(as) + 1.f) / 2.f * (max_sigma - min_sigma) + min_sigma;
+}
+
+#ifndef MBX_GLEET_DEVICE_FUNCTIONS_ONLY
 __global__ __launch_bounds__(kGpThreads) MBX_GP_OCC void k_gleet_policy(BatchParams bp, GleetActor net, const double* __restrict__ state,
                                                              float* __restrict__ actions, float* __restrict__ mu_sigma)
 {
@@ -208,35 +250,15 @@ __global__ __launch_bounds__(kGpThreads) MBX_GP_OCC void k_gleet_policy(BatchPar
     const bool live = i < NP;
     float h[kGpE], dq[kGpE];
     if (live) {
-        const float* xi = X + i * 27;
-        const float* We = W + GpOff::we;
-        float e1[kGpE], e2[kGpE];
-#pragma unroll
-        for (int o = 0; o < kGpE; ++o) {
-            float a = 0.f, p = 0.f, g = 0.f;
-#pragma unroll
-            for (int k = 0; k < kGpNode; ++k) { const float w = We[o * kGpNode + k]; a += xi[k] * w; p += xi[kGpNode + k] * w; g += xi[2 * kGpNode + k] * w; }
-            h[o] = a; e1[o] = p; e2[o] = g;
-        }
-        const float* Wd = W + GpOff::wd;
-#pragma unroll
-        for (int o = 0; o < kGpE; ++o) {
-            float a = 0.f;
-#pragma unroll
-            for (int k = 0; k < kGpE; ++k) a += e1[k] * Wd[o * 2 * kGpE + k];
-#pragma unroll
-            for (int k = 0; k < kGpE; ++k) a += e2[k] * Wd[o * 2 * kGpE + kGpE + k];
-            dq[o] = a;
-        }
+        gp_embed(X + i * 27, W, h, dq);
     }
     __syncthreads();                                                 // X is dead: its storage becomes K / V
     gp_encoder_layer(h, h, W + GpOff::enc, KL, VL, live, NP, i, red);
     __syncthreads();                                                 // every lane is done with the encoder's keys / values
     gp_encoder_layer(h, dq, W + GpOff::dec, KL, VL, live, NP, i, red);
     if (live) {
-        const float am = gp_head(h, W + GpOff::mu), as = gp_head(h, W + GpOff::sigma);
-        const float mu = (tanhf(am) + 1.f) / 2.f;
-        const float sigma = (tanhf(as) + 1.f) / 2.f * (net.max_sigma - net.min_sigma) + net.min_sigma;
+        float mu, sigma;
+        gp_mu_sigma(h, W, net.min_sigma, net.max_sigma, mu, sigma);
         const double* sc = bp.state + (int64_t)b * bp.state_stride + bp.sc_off;
         const uint64_t seed = bp.seeds[b];
         const Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)((int)sc[MBX_SC_GEN] + 1), (uint32_t)(int)sc[MBX_SC_EPISODE]};
@@ -244,6 +266,7 @@ __global__ __launch_bounds__(kGpThreads) MBX_GP_OCC void k_gleet_policy(BatchPar
         if (mu_sigma) { mu_sigma[((int64_t)b * 2) * NP + i] = mu; mu_sigma[((int64_t)b * 2 + 1) * NP + i] = sigma; }
     }
 }
+#endif
 
 #pragma clang fp contract(off)      // back to the translation unit's -ffp-contract=off
 

@@ -45,9 +45,10 @@ struct mbx_batch {
     bool lde_run_kinds_ok = false;         // LDE: every problem of the batch has an objective kind the LEAN instantiations of k_lde_run build (one tile array: lde_run_kind_ok(.., two = false))
     bool lde_run_kinds_two = false;        // ... a kind the instantiations with the second tile array build (F1-F24)
     bool nrlpso_cached = false;            // NRLPSO: the step kernels keep the NP x NP distance matrix in LDS (MBX_F_NRLPSO_RECOMPUTE clear and the matrix fits)
-    mbx::ParamSets sets;                   // LES, L2L: mbx_les_set_params / mbx_l2l_set_params
+    mbx::ParamSets sets;                   // LES, L2L, GLEET: mbx_les_set_params / mbx_l2l_set_params / mbx_gleet_set_params
     float* d_les_ts = nullptr;             // LES: [les_horizon + 1][13] float32 timestamp embedding tanh(t / timestamp - 1), one row per generation counter
     int les_horizon = 0;
+    float gleet_min_sigma = 0.f, gleet_max_sigma = 0.f;   // GLEET: the actor's sigma range, with the weight sets in `sets` (mbx_gleet_set_params)
     bool rollout_per_generation = false;   // MBX_F_ROLLOUT_PER_GENERATION: the mbx_*_rollout entry points take the host-loop route
     int64_t state_stride = 0;
     const double* d_tape = nullptr;

@@ -284,6 +284,29 @@ MBX_LDS_WALK GlLds gl_layout(C& c, int NP, int D)
 __host__ __device__ inline int64_t gl_lds_doubles(int NP, int D) { LdsSize c; gl_layout(c, NP, D); return c.n; }
 __device__ __forceinline__ GlLds gl_carve(double* base, int NP, int D) { LdsCarve c{base}; return gl_layout(c, NP, D); }
 
+// The resident rollout (mbx_gleet_run.hpp): the generation's layout, then the actor's.  Its keys and values (K | V, [NP][16] float32 each: 16 NP doubles) are
+// only alive while the evaluator's scratch T | Z is dead, and lie there wherever that is long enough (D >= 8, or a small swarm); otherwise they get an area
+// of their own behind everything else.  PRED: the actor's block sums, one float per wave.
+struct GlrLds {
+    GlLds g;
+    float *KL, *VL, *PRED;
+};
+
+__host__ __device__ inline int64_t glr_kv_doubles(int NP) { return 16 * (int64_t)NP; }
+__host__ __device__ inline bool glr_kv_in_scratch(int NP, int D) { return glr_kv_doubles(NP) <= eval_t_doubles(NP, D) + eval_z_doubles(NP, D); }
+
+MBX_LDS_WALK GlrLds glr_layout(C& c, int NP, int D)
+{
+    GlrLds L;
+    L.g = gl_layout(c, NP, D);
+    L.PRED = c.template take<float>(2);
+    L.KL = glr_kv_in_scratch(NP, D) ? reinterpret_cast<float*>(L.g.T) : c.template take<float>(glr_kv_doubles(NP));      // T | Z are contiguous (lds_eval_rows)
+    L.VL = L.KL + 16 * NP;
+    return L;
+}
+__host__ __device__ inline int64_t glr_lds_doubles(int NP, int D) { LdsSize c; glr_layout(c, NP, D); return c.n; }
+__device__ __forceinline__ GlrLds glr_carve(double* base, int NP, int D) { LdsCarve c{base}; return glr_layout(c, NP, D); }
+
 // ------------------------------------------------------------------------------------------------ GL-PSO (mbx_glpso.hpp)
 struct GpLds {
     double *X, *Z, *T, *M1T, *M2T, *DSH, *V0, *V1, *V2, *NC, *GB, *PBC, *EXC, *STAG, *RED;

@@ -182,6 +182,39 @@ class Batch:
         _abi.check(self.lib.mbx_gleet_policy(self._h, C.byref(net), _ptr(self.state), _ptr(self._actions), _ptr(ms), _stream()))
         return (self._actions, ms) if want_mu_sigma else self._actions
 
+    def gleet_set_params(self, weights, set_of_instance=None, min_sigma=0.01, max_sigma=0.7):
+        """GLEET's resident rollout: the actor weight sets of the batch and the set of every instance (``mbx_gleet_set_params``).  weights: [n_sets, 5426]
+        (or [5426]) float32 in ``Actor.packed_weights`` order, a tensor on any device or an array.  set_of_instance: [B] integers, or None = set 0 for
+        every instance.  The library keeps copies."""
+        w = weights.detach() if torch.is_tensor(weights) else torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float32))
+        if w.dtype != torch.float32 or w.numel() == 0 or w.numel() % 5426:
+            raise ValueError(f'a GLEET actor has 5426 float32 weights; got {w.numel()} {w.dtype} values')
+        wd = w.reshape(-1, 5426).to(self.device).contiguous()
+        sd = None
+        if set_of_instance is not None:
+            si = np.ascontiguousarray(set_of_instance, dtype=np.int32)
+            assert si.shape == (self.B,)
+            sd = torch.from_numpy(si).to(self.device)
+        _abi.check(self.lib.mbx_gleet_set_params(self._h, _ptr(wd), int(wd.shape[0]), _ptr(sd), float(min_sigma), float(max_sigma)))
+
+    def gleet_rollout(self, n_steps, want_traj=False):
+        """Up to `n_steps` GLEET env steps -- attention actor, draw, generation, features -- of every instance in ONE launch, the features on chip in
+        between (``mbx_gleet_rollout``, after ``gleet_set_params``); bit-identical to step() fed the actions the kernel drew, and to any split of
+        `n_steps` over several calls.  Reads and updates the batch's own state tensor.  Returns (state, reward summed over the executed steps, done)
+        and, with ``want_traj=True``, a dict of per-step records: actions [n_steps, B, np] / mu_sigma [n_steps, B, 2, np] float32, reward
+        [n_steps, B] float64 -- NaN in the rows of steps after an instance's termination, which the kernel does not write."""
+        n_steps = int(n_steps)
+        traj = None
+        if want_traj:
+            nan = float('nan')
+            traj = {'actions': torch.full((n_steps, self.B, self.cfg.np), nan, dtype=torch.float32, device=self.device),
+                    'mu_sigma': torch.full((n_steps, self.B, 2, self.cfg.np), nan, dtype=torch.float32, device=self.device),
+                    'reward': torch.full((n_steps, self.B), nan, dtype=torch.float64, device=self.device)}
+        t = traj or {}
+        _abi.check(self.lib.mbx_gleet_rollout(self._h, n_steps, _ptr(self.state), _ptr(t.get('actions')), _ptr(t.get('mu_sigma')), _ptr(t.get('reward')),
+                                              _ptr(self.reward), _ptr(self.done), _stream()))
+        return (self.state, self.reward, self.done, traj) if want_traj else (self.state, self.reward, self.done)
+
     def qlpso_rollout(self, q_table, n_steps, want_actions=False):
         """`n_steps` QLPSO env steps of every instance in ONE launch, tabular policy evaluated in the kernel (``mbx_qlpso_rollout``).
         q_table: [4, 4] float64 CUDA tensor.  Returns (state, reward summed over the executed steps, done[, last actions int32])."""

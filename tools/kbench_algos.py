@@ -134,9 +134,24 @@ if 'gleet' in which:
     run_kernel(5); dk = timed(run_kernel, 60)
     run(3); dt = timed(run, 30)
     run_hip(5); dh = timed(run_hip, 60)
+    # the resident route (mbx_gleet_rollout, the actor inside the step kernel) against the two-launch route, same batch, a fresh episode (199 steps:
+    # 2 x 2 warm-up + 6 x 2 x 15), alternating windows with a device synchronisation around each; the spread of the windows is the noise
+    env.batch.gleet_set_params(w, None, agent.actor.min_sigma, agent.actor.max_sigma)
+    def run_resident(n):
+        env.batch.gleet_rollout(n)
+    env.reset(); run_hip(2); run_resident(2)
+    alt = {'hip': [], 'resident': []}
+    for _ in range(6):
+        alt['hip'].append(timed(run_hip, 15) / 15 * 1e6); alt['resident'].append(timed(run_resident, 15) / 15 * 1e6)
+    assert int(env.batch.done.sum()) == 0                            # every window ran live instances
+    med = {k: float(np.median(v)) for k, v in alt.items()}
     print(json.dumps({'path': 'GLEET bbob d=10 NP=100, 4096 instances', 'kernel_us_per_step': dk / 60 * 1e6,
                       'kernel_env_steps_per_s': B * 60 / dk, 'with_torch_policy_ms_per_step': dt / 30 * 1e3, 'torch_env_steps_per_s': B * 30 / dt,
-                      'with_hip_policy_us_per_step': dh / 60 * 1e6, 'hip_env_steps_per_s': B * 60 / dh}))
+                      'with_hip_policy_us_per_step': dh / 60 * 1e6, 'hip_env_steps_per_s': B * 60 / dh,
+                      'resident_us_per_step': med['resident'], 'resident_env_steps_per_s': B / med['resident'] * 1e6,
+                      'alternation': {'windows': 6, 'steps_per_window': 15, 'with_hip_policy_us_per_step': [round(v, 1) for v in alt['hip']],
+                                      'resident_us_per_step': [round(v, 1) for v in alt['resident']], 'with_hip_policy_median': med['hip'],
+                                      'spread_us': {k: float(max(v) - min(v)) for k, v in alt.items()}}}))
     env.close()
 if 'qlpso' in which:
     from metabox_amd.optimizer import QLPSO_Optimizer
